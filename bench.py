@@ -102,6 +102,10 @@ def parse():
                    help="two-electron AO integrals of the sym8 legs: packed as PySCF delivers them with aosym='s4' "
                         "(int2e, EVC_FLAG_ERI_S4) and aosym='s2kl' (int2e_ip1, EVC_FLAG_IP1_S2KL), or the full "
                         "(N,N,N,N) / (3,N,N,N,N) arrays; other layouts always take the full arrays")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the LAST timed step of the headline leg computed on rank 0 "
+                        "as DIR/<name>.npy (float64): `energy` (G,) ground-state energies and, unless --energy-only, "
+                        "`grad` (G,A,3) nuclear gradients; the inputs depend only on the arguments")
     return p.parse_args()
 
 
@@ -237,9 +241,11 @@ def main():
             kw = {"device_id": dev} if backend == "nccl" else {}
             dist.init_process_group(backend, init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1, **kw)
 
-    def measure(trd, aos, G, nslots, steps, warmup, sharded_pairs, all_stages=False, pipelined=False, repeats=1):
+    def measure(trd, aos, G, nslots, steps, warmup, sharded_pairs, all_stages=False, pipelined=False, repeats=1,
+                keep_outputs=False):
         """Time `steps` passes over batches of G geometries with `nslots` batches in flight on this rank, `repeats` times.
-        all_stages: time every instrumented stage (two event records per launch), not only K5 and K8."""
+        all_stages: time every instrumented stage (two event records per launch), not only K5 and K8.
+        keep_outputs: return, under "outputs", host copies of what the last timed step computed."""
         mk_stream = lambda: (torch.cuda.Stream(dev) if nslots > 1 else None)
         if G > 1:
             nb = max(1, len(aos) // G)
@@ -283,6 +289,14 @@ def main():
                 step(warmup + rep * steps + k)
             fence()
             dts.append(time.perf_counter() - t0)
+        outputs = None
+        if keep_outputs:
+            # the slot of the last timed step, read before anything else is enqueued on it
+            assert not pipelined and steps >= 1
+            ev_ = evs[(warmup + repeats * steps - 1) % nslots]
+            outputs = {"energy": ev_.energy.reshape(-1, T)[:, 0].cpu().numpy().astype(np.float64)}
+            if not a.energy_only:
+                outputs["grad"] = ev_.grad.reshape(-1, max(A, 1), 3)[:, :A].cpu().numpy().astype(np.float64)
         if world > 1 and not solo_mode[0]:
             # max over ranks, repeat by repeat
             tt = torch.tensor(dts, dtype=torch.float64, device=dev)
@@ -337,7 +351,7 @@ def main():
                 "k8_GBs": (nbytes8 / (k8 * 1e-3) / 1e9) if k8 else None, "last_energy": e_last, "check_energy": e_check,
                 "k5_flops_per_launch": 2.0 * trd.rows_local * trd.cols * gl,
                 "stages": stages, "per_rank": per_rank,
-                "geometries_per_step": job_g}
+                "geometries_per_step": job_g, "outputs": outputs}
 
     def step_roofline(ms_per_step, geoms, k5_per_launch):
         """Whole step against the two rooflines at once: ALGORITHMIC bytes (the resident t-RDMs twice, the AO inputs
@@ -380,7 +394,12 @@ def main():
     run_view = ((lambda lst, phases=False: [x.packed_ip1(eri=True) for x in lst]) if packed_ip1
                 else (lambda lst, phases=False: lst))
     aos_run = run_view(aos, pairs_first)
-    m = measure(trd, aos_run, G, 1 if pairs_first else S, a.steps, a.warmup, pairs_first, repeats=max(1, a.repeats))
+    m = measure(trd, aos_run, G, 1 if pairs_first else S, a.steps, a.warmup, pairs_first, repeats=max(1, a.repeats),
+                keep_outputs=a.dump_outputs is not None)
+    if a.dump_outputs is not None and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in m["outputs"].items():
+            np.save(os.path.join(a.dump_outputs, f"{name}.npy"), arr)
 
     # The headline is quoted on the LDS-ring K5 kernel, which needs >= 250 CUs (csrc/gemv_lds.hip: lds_device_fits); on a
     # smaller or partitioned device the library falls back to the fragment-shaped kernel.  That is a different measurement:
