@@ -9,9 +9,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
 from .ab_initio_gradients_loewdin import get_energy_with_grad
 from .ab_initio_eigenvector_continuation import (approximate_ground_state_OAO, _trdms,  # noqa: F401 (re-export)
-                                                 get_trdm_compression, integrals_have_symmetry)
+                                                 _trdms_auto, get_trdm_compression, integrals_have_symmetry)
 from .electron_integral_utils import get_basis, get_integrals  # noqa: F401 (re-export)
 from .evaluator import ContinuationEvaluator, DeviceAO
 from .hosted import HostedEvaluator
@@ -32,10 +33,11 @@ def get_scanner(mol, one_rdm, two_rdm, overlap, hermitian=True, compress="defaul
 
     ``compress``: storage of the resident training data, ``None``, ``"sym8"``, ``"auto"`` or ``"default"``
     (= ``set_trdm_compression``, "auto" unless changed).  "auto": the 8-fold compressed copy and the packed s4 / s2kl
-    integrals for the per-step ``(E, grad)`` when ``hermitian`` and the first molecule's integrals have the symmetries
-    of real ones (a PySCF ``Mole`` always; array-level molecules are checked once), with ``predicted_two_rdm``
-    still the reference's un-symmetrised 2-RDM (evaluated on the caller's layout when it is read); with ``"sym8"``
-    the stored predicted 2-RDM is the 8-fold symmetrised one.
+    integrals for the per-step ``(E, grad)`` when ``hermitian``, the training set's bra<->ket partner blocks compress
+    alike and the first molecule's integrals have the symmetries of real ones (a PySCF ``Mole`` always; array-level
+    molecules are checked completely once; the packed staging spot-checks every later one and raises), with
+    ``predicted_two_rdm`` still the reference's un-symmetrised 2-RDM (evaluated on the caller's layout when it is
+    read); with ``"sym8"`` the stored predicted 2-RDM is the 8-fold symmetrised one.
     ``device_trdms``: training data already resident on the device (``trdm_io.load_pair_directories`` /
     ``load_checkpoint``, a container's ``device_trdms()``): used instead of uploading the host arrays."""
     if compress == "default":
@@ -127,7 +129,13 @@ def get_scanner(mol, one_rdm, two_rdm, overlap, hermitian=True, compress="defaul
                 if not self._decided:
                     self._compress = "sym8" if integrals_have_symmetry(mol) else None
                     self._decided = True
-                t = device_trdms if device_trdms is not None else _trdms(one_rdm, two_rdm, overlap, self._compress)
+                if device_trdms is not None:
+                    t = device_trdms
+                elif auto:      # (the caller's layout for a training set the compressed one cannot represent)
+                    t = _trdms_auto(one_rdm, two_rdm, overlap, self._compress)
+                    self._compress = "sym8" if t.layout == _lib.LAYOUT_SYM8 else None
+                else:
+                    t = _trdms(one_rdm, two_rdm, overlap, self._compress)
                 sl = aoslices_of(mol)
                 self._hev = HostedEvaluator(t, len(sl), sl, warm_start=True)
             stage_mol(mol, self._hev)

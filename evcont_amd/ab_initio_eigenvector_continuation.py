@@ -45,9 +45,13 @@ def _select(vals, vecs, nroots, ground_state):
 #   "auto" (default)  8-fold compressed (``evaluator.DeviceTRDMs.compress_sym8_``: 3.7x fewer streamed bytes and the
 #                     symmetric AO-side pipeline, the configuration ``bench.py`` measures) whenever that is exact AND
 #                     indistinguishable from the reference for the caller: ``hermitian=True``, no predicted RDMs asked
-#                     for, and AO integrals with the index symmetries of real two-electron integrals -- a PySCF ``Mole``
-#                     has them by construction, an array-level molecule is checked at the first call for a training set
-#                     (``integrals_have_symmetry``).  Everything else (``hermitian=False``,
+#                     for, a training set whose bra<->ket partner blocks compress alike (checked on the device when the
+#                     compressed copy of a training set held as (T,T,...) is made, ``DeviceTRDMs.compress_sym8_``;
+#                     ``_trdms_auto`` then keeps the caller's layout for it), and AO integrals with the index
+#                     symmetries of real two-electron integrals -- a PySCF ``Mole`` has them by construction, an
+#                     array-level molecule is checked completely at the first call for a training set
+#                     (``integrals_have_symmetry``) and, unless it declares ``integral_symmetry``, by a random sample on
+#                     every later call (``spot_check_integral_symmetry``).  Everything else (``hermitian=False``,
 #                     ``return_density_matrices=True``, ``predicted_two_rdm`` of a scanner, general tensors) runs on the
 #                     layout the caller passed, from a second resident copy made on first use;
 #   None / "none"     always the layout the caller passed;
@@ -63,7 +67,8 @@ def _mode_from_env():
 
 
 _COMPRESS = _mode_from_env()
-_auto_decisions = {}   # training-set key -> bool: integrals of its first geometry had the symmetries
+_auto_decisions = {}   # training-set key -> bool: its first geometry's integrals had the symmetries (False as well once
+                       # the compressed layout refused the training set itself, _trdms_auto)
 
 
 def set_trdm_compression(mode) -> None:
@@ -101,9 +106,30 @@ def integrals_have_symmetry(mol_or_ao, tol: float = 1.0e-9) -> bool:
     return True
 
 
-def resolve_compression(mode, one_RDM, two_RDM, S, mol, hermitian=True, want_rdms=False, n=None):
+def _integrals_fit_this_call(mol, need_grad: bool) -> bool:
+    """Per-call part of the "auto" decision: a molecule that declares ``integral_symmetry`` is taken at its word, a
+    PySCF ``Mole`` has the symmetries, any other array-level molecule is spot-checked (``eri_ip1`` only when the call
+    reads it)."""
+    declared = getattr(mol, "integral_symmetry", None)
+    if declared is not None:
+        return bool(declared)
+    if not is_array_mol(mol):
+        return True
+    from .evaluator import _CHECK_SYM, spot_check_integral_symmetry
+    from ._lib import EvcontHipError
+    if _CHECK_SYM == "0":
+        return True
+    ip1 = getattr(mol, "eri_ip1", None) if need_grad else None
+    try:
+        spot_check_integral_symmetry(mol.eri, ip1, int(np.asarray(mol.S).shape[0]))
+    except EvcontHipError:
+        return False
+    return True
+
+
+def resolve_compression(mode, one_RDM, two_RDM, S, mol, hermitian=True, want_rdms=False, n=None, need_grad=True):
     """The storage (``None`` or ``"sym8"``) one call of a mol-level entry point uses under ``mode``
-    (``"default"`` = ``get_trdm_compression()``)."""
+    (``"default"`` = ``get_trdm_compression()``).  ``need_grad=False``: the call reads no ``eri_ip1``."""
     if mode == "default":
         mode = _COMPRESS
     if mode is None:
@@ -121,7 +147,8 @@ def resolve_compression(mode, one_RDM, two_RDM, S, mol, hermitian=True, want_rdm
         if len(_auto_decisions) > 64:
             _auto_decisions.clear()
         _auto_decisions[key] = ok
-    return "sym8" if ok else None
+    # (the decision above was made on the first molecule; every later one must have the symmetries as well)
+    return "sym8" if ok and _integrals_fit_this_call(mol, need_grad) else None
 
 
 def _trdms(one_RDM, two_RDM, S, compress=None) -> DeviceTRDMs:
@@ -133,10 +160,26 @@ def _trdms(one_RDM, two_RDM, S, compress=None) -> DeviceTRDMs:
     return t
 
 
-def _evaluator(one_RDM, two_RDM, S, natm: int, compress=None) -> ContinuationEvaluator:
-    """``compress``: None or "sym8" (what ``resolve_compression`` returned for this call)."""
+def _trdms_auto(one_RDM, two_RDM, S, compress) -> DeviceTRDMs:
+    """``_trdms`` for a storage that mode "auto" chose: a training set the compressed layout cannot represent (its
+    bra<->ket partner blocks differ, ``Sym8NotExact``) is kept in the caller's layout instead, and "auto" remembers
+    that for the training set.  (An explicit "sym8" raises.)"""
+    from .evaluator import Sym8NotExact
+    if compress == "sym8":
+        try:
+            return _trdms(one_RDM, two_RDM, S, "sym8")
+        except Sym8NotExact:
+            _auto_decisions[cache.key_of(one_RDM, two_RDM, S, ("auto",))] = False
+            compress = None
+    return _trdms(one_RDM, two_RDM, S, compress)
+
+
+def _evaluator(one_RDM, two_RDM, S, natm: int, compress=None, auto: bool = False) -> ContinuationEvaluator:
+    """``compress``: None or "sym8" (what ``resolve_compression`` returned for this call); ``auto``: it was chosen by
+    mode "auto" (``_trdms_auto``)."""
     assert compress in (None, "sym8")
-    t = _trdms(one_RDM, two_RDM, S, compress)       # verified against the host arrays, or uploaded again
+    # (verified against the host arrays, or uploaded again)
+    t = _trdms_auto(one_RDM, two_RDM, S, compress) if auto else _trdms(one_RDM, two_RDM, S, compress)
     key = ("evaluator", id(t), int(natm))
     ev = cache.get(key)
     if ev is None or ev.t is not t:
@@ -187,7 +230,8 @@ def _oao(mol, one_RDM, two_RDM, S, nroots, hermitian=True, ground_state=False):
     # (the non-Hermitian branch works on the subspace matrix of the layout the caller passed)
     ev = _evaluator(one_RDM, two_RDM, S, int(np.asarray(ao.aoslices).shape[0]),
                     compress=resolve_compression("default", one_RDM, two_RDM, S, ao if is_array_mol(mol) else mol,
-                                                 hermitian=hermitian))
+                                                 hermitian=hermitian, need_grad=False),
+                    auto=_COMPRESS == "auto")
     dao = DeviceAO.from_arrays(ao, ev.t.device, energy_only=True)
     res = ev.energies(dao, nroots)
     if hermitian:

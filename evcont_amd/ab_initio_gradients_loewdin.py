@@ -8,7 +8,7 @@ import torch
 from . import gradients as G
 from . import ops
 from .ab_initio_eigenvector_continuation import (_evaluator, approximate_ground_state,  # noqa: F401
-                                                 resolve_compression)
+                                                 get_trdm_compression, resolve_compression)
 from .electron_integral_utils import get_loewdin_trafo, restore_electron_exchange_symmetry  # noqa: F401
 from .evaluator import DeviceAO, _dev
 from .integrals import ao_arrays, grad_nuc, is_array_mol
@@ -102,6 +102,7 @@ def get_energy_with_grad(mol, one_RDM, two_RDM, S, hermitian=True, return_densit
     # returns them)
     ev = _evaluator(one_RDM, two_RDM, S, natm,
                     compress=resolve_compression("default", one_RDM, two_RDM, S, mol if not is_array_mol(mol) else ao,
-                                                 hermitian=True, want_rdms=return_density_matrices))
+                                                 hermitian=True, want_rdms=return_density_matrices),
+                    auto=get_trdm_compression() == "auto")
     dao = DeviceAO.from_arrays(ao, ev.t.device)
     return ev.energy_with_grad(dao, return_density_matrices=return_density_matrices)

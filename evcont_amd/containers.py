@@ -91,7 +91,8 @@ class TRDMContainer:
         arrays were replaced (append, prune, or a script assigning ``np.load`` results to the attributes,
         ``md_H30_evcont_from_DMRG.py:72-85``).  ``layout``: "pack2" (pairs x packed electrons, needs the
         bra<->ket symmetric data every container of the reference produces), "pair5", "elec3", "full6", or "sym8"
-        (8-fold compressed on the device from the pack2 form, ``DeviceTRDMs.compress_sym8_``)."""
+        (8-fold compressed on the device from the elec3 form, ``DeviceTRDMs.compress_sym8_``, which checks there that
+        the bra<->ket partner blocks agree and raises ``evaluator.Sym8NotExact`` otherwise)."""
         from .evaluator import DeviceTRDMs
         from .synthetic import pack_rows
         if self.two_rdm is None:
@@ -100,7 +101,7 @@ class TRDMContainer:
         key = key_of(self.one_rdm, self.two_rdm, self.overlap, (layout, str(device)))   # address + content sample
         if self._device is None or self._device_key != key:
             pairs, elec = {"full6": (False, False), "pair5": (True, False), "elec3": (False, True),
-                           "pack2": (True, True), "sym8": (True, True)}[layout]
+                           "pack2": (True, True), "sym8": (False, True)}[layout]
             two = np.asarray(self.two_rdm, dtype=np.float64)
             if two.ndim == 6 and (pairs or elec):
                 two = pack_rows(two, pairs, elec)

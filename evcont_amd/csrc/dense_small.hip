@@ -1661,8 +1661,10 @@ int launch_loewdin(const LoewdinArgs &a_in, int count, hipStream_t st) {
             EVC_LAUNCH_CHECK("loewdin_ns64");
             LoewdinArgs b = a_in;
             b.part = 3;
+            note_kernel(EVC_PROF_LOEWDIN, "loewdin_ns64_kernel part=1");
             return launch_loewdin_big(b, count, st);
         }
+        note_kernel(EVC_PROF_LOEWDIN, "loewdin_big_kernel part=%d", a_in.part);
         return launch_loewdin_big(a_in, count, st);
     }
     LoewdinArgs a = a_in;
@@ -1680,6 +1682,7 @@ int launch_loewdin(const LoewdinArgs &a_in, int count, hipStream_t st) {
     if (int rc = allow_dynamic_lds(loewdin_kernel, attr, 160 * 1024, "loewdin")) return rc;
     hipLaunchKernelGGL(loewdin_kernel, dim3(count), dim3(kThreads), lds, st, a);
     EVC_LAUNCH_CHECK("loewdin");
+    note_kernel(EVC_PROF_LOEWDIN, "loewdin_kernel part=%d", a.part);
     return 0;
 }
 

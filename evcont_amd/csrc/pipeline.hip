@@ -305,8 +305,15 @@ static Side *side_of(void *ws) {
     return &g_side.emplace(ws, sd).first->second;
 }
 
+static void side_set_pending(void *ws) {
+    std::lock_guard<std::mutex> lk(g_side_mu);
+    auto it = g_side.find(ws);
+    if (it != g_side.end()) it->second.pending = true;
+}
+
 // The join: whoever reads U and s of a workspace next (launch_grad_final -- in the same call or, after an energy-only
-// call, in a later evc_phase_gradient on the same workspace) waits for the eigensolver launch that writes them.
+// call, in a later evc_phase_gradient, evc_phase_loewdin_batch or Loewdin launch on the same workspace) waits for the
+// eigensolver launch that writes them.
 static int side_join(void *ws, hipStream_t st) {
     std::lock_guard<std::mutex> lk(g_side_mu);
     auto it = g_side.find(ws);
@@ -410,12 +417,23 @@ static int phase_hamiltonian(const evc_trdm_set *t, const Geo &g_in, Ws &w, bool
             la.part = 2;
             if ((rc = launch_loewdin(la, cnt, sd->s))) return rc;
             EVC_HIP(hipEventRecord(sd->join, sd->s));
-            sd->pending = true;
+            side_set_pending(w.base);
+        } else if ((rc = side_join(w.base, st))) {
+            // this launch reads (warm start) and writes U and s: an eigensolver launch of an earlier energy-only call
+            // on the side stream may still be writing them
+            return rc;
         }
+        char side_ran[sizeof(g_kernel_ran[0])] = "";
+        if (w.split == 1) snprintf(side_ran, sizeof(side_ran), "%s", g_kernel_ran[EVC_PROF_LOEWDIN]);
         la.part = w.split ? 1 : 0;
         const int pr = prof_start(EVC_PROF_LOEWDIN, st);
         if ((rc = launch_loewdin(la, cnt, st))) return rc;
         prof_stop(pr, st);
+        if (w.split == 1) {
+            char main_ran[sizeof(g_kernel_ran[0])];
+            snprintf(main_ran, sizeof(main_ran), "%s", g_kernel_ran[EVC_PROF_LOEWDIN]);
+            note_kernel(EVC_PROF_LOEWDIN, "%s; side stream: %s", main_ran, side_ran);
+        }
         if (w.split == 3) w.la_ride = la;
     }
     // (ab|cd) -> K3[jkl][a] -> h2[ijkl]
@@ -1157,6 +1175,8 @@ extern "C" int evc_phase_loewdin_batch(const evc_trdm_set *t, const evc_geometry
     la.warm = (flags & EVC_FLAG_WARM_START) ? 1 : 0;
     la.scratch = w.B1;
     la.sscratch = w.stride;
+    // (rewrites U and s: after an energy-only call their eigensolver launch may still be running on the side stream)
+    if (int rc = side_join(w.base, as_stream(stream))) return rc;
     return launch_loewdin(la, gb->count, as_stream(stream));
 }
 

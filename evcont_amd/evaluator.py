@@ -108,6 +108,10 @@ def spot_check_integral_symmetry(eri, eri_ip1, n: int, samples: int = 4096, tol:
             "reference layouts (compress=None) for such tensors; EVCONT_AMD_CHECK_SYM=0 disables this check.")
 
 
+class Sym8NotExact(_lib.EvcontHipError):
+    """A training set whose bra<->ket partner blocks differ: the compressed layout would not represent it."""
+
+
 def _host_check_once(tag: str) -> bool:
     """Whether a host-side packing helper should verify the symmetries now (EVCONT_AMD_CHECK_SYM)."""
     if _CHECK_SYM == "0":
@@ -173,6 +177,28 @@ def sym8_column_images(layout: int, n: int):
     images = [(i, j, k, l), (j, i, k, l), (i, j, l, k), (j, i, l, k),
               (k, l, i, j), (l, k, i, j), (k, l, j, i), (l, k, j, i)]
     return [np.ascontiguousarray(col(*im)) for im in images]
+
+
+def sym8_gather_sums(blk: torch.Tensor, idx) -> torch.Tensor:
+    """Per row of ``blk`` (rows of a source layout) the sums over the eight column images ``idx``
+    (``sym8_column_images``): eight times the compressed row."""
+    acc = blk.index_select(1, idx[0])
+    for ix in idx[1:]:
+        acc += blk.index_select(1, ix)
+    return acc
+
+
+# Relative tolerance of the bra<->ket test of compress_sym8_, of the largest sum a row can hold (8 x its largest
+# element): the images of a bra<->ket symmetric pair are summed in different orders, so they agree to rounding only.
+SYM8_BRA_KET_RTOL = 4.0e-13
+
+
+def sym8_rows_differ(blk_ab: torch.Tensor, sums_ab: torch.Tensor, blk_ba: torch.Tensor, idx,
+                     rtol: float = SYM8_BRA_KET_RTOL) -> torch.Tensor:
+    """Bool per row: whether the bra<->ket partner rows ``blk_ba`` (blocks (b,a)) compress to something else than
+    the rows ``blk_ab`` (blocks (a,b); ``sums_ab = sym8_gather_sums(blk_ab, idx)``), beyond rounding."""
+    scale = 8.0 * torch.maximum(blk_ab.abs().amax(1), blk_ba.abs().amax(1))
+    return (sym8_gather_sums(blk_ba, idx) - sums_ab).abs().amax(1) > rtol * scale
 
 
 def _upload_rows(src: np.ndarray, rows: int, cols: int, r0: int, r1: int, device) -> Tuple[torch.Tensor, int]:
@@ -252,7 +278,14 @@ class DeviceTRDMs:
 
         Exact (to rounding) for the Hermitian continuation whenever the AO integrals carry those symmetries
         (``eri`` 8-fold, ``eri_ip1`` symmetric in its last two indices: every PySCF ``int2e`` /
-        ``int2e_ip1``); ``predicted_two_rdm`` then is the symmetrised 2-RDM.  Not for ``hermitian=False``."""
+        ``int2e_ip1``); ``predicted_two_rdm`` then is the symmetrised 2-RDM.  Not for ``hermitian=False``.
+
+        The compressed layout keeps the pairs ``a >= b`` only, with weight ``2 c_a c_b``: that is exact only when the
+        block ``(b,a)`` compresses to the same row as ``(a,b)`` (every container of the reference stores bra<->ket
+        symmetric data).  For the (T,T,...) layouts (ndim 6 / 3), which hold both blocks, the ``(b,a)`` rows are
+        compressed by the same gather and compared with the ``(a,b)`` rows on the device; a training set that fails
+        raises ``Sym8NotExact`` and is left as it was.  (The pair layouts 5 / 2 hold one block per pair: nothing to
+        compare.)"""
         if self.layout == _lib.LAYOUT_SYM8:
             return self
         T, n, d = self.T, self.n, self.device
@@ -261,9 +294,11 @@ class DeviceTRDMs:
                 raise ValueError("compress_sym8_: shard the pair layouts (5, 2), not the (T,T,...) ones")
             a, b = np.tril_indices(T)
             src = torch.from_numpy((a * T + b).astype(np.int64)).to(d)
+            src_ba = torch.from_numpy((b * T + a).astype(np.int64)).to(d)
             r0 = 0
         else:
             src = torch.arange(self.rows_local, dtype=torch.int64, device=d)
+            src_ba = None
             r0 = self.row_offset
         idx = [torch.from_numpy(ix).to(d) for ix in sym8_column_images(self.layout, n)]
         rows8, cols8 = layout_shape(_lib.LAYOUT_SYM8, T, n)
@@ -273,9 +308,18 @@ class DeviceTRDMs:
         step = max(1, (256 << 20) // (self.ld * 8))
         for a0 in range(0, nloc, step):
             blk = self.two.index_select(0, src[a0:a0 + step])
-            acc = blk.index_select(1, idx[0])
-            for ix in idx[1:]:
-                acc += blk.index_select(1, ix)
+            acc = sym8_gather_sums(blk, idx)
+            if src_ba is not None:
+                blk_ba = self.two.index_select(0, src_ba[a0:a0 + step])
+                bad = sym8_rows_differ(blk, acc, blk_ba, idx)
+                if bool(bad.any()):
+                    r = a0 + int(torch.nonzero(bad)[0, 0].item())
+                    raise Sym8NotExact(
+                        f"compress='sym8': the two-body t-RDM block ({int(a[r])},{int(b[r])}) and its bra<->ket "
+                        f"partner ({int(b[r])},{int(a[r])}) differ after the 8-fold symmetrisation: the compressed "
+                        "layout keeps one block per pair and would give wrong forces for this training set.  Use the "
+                        "layout the data is held in (compress=None).")
+                del blk_ba
             out[a0:a0 + acc.shape[0], :cols8] = acc * 0.125
             del blk, acc
         self.two, self.layout = out, _lib.LAYOUT_SYM8

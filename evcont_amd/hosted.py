@@ -15,7 +15,9 @@ produces the AO integrals of every step on the host and the continuation consume
   E and the forces into pinned memory; the PCIe transfer of the 10 MB array overlaps the first half of the device
   work.  DEFAULT: enqueued eagerly every step.  Opt-in (``use_graph=True`` / ``EVCONT_AMD_HOSTED_GRAPH=1``): the same
   enqueue captured once and replayed as ONE HIP graph -- measured slower on MI355X / ROCm 7.2 (0.58 against 0.39 ms at
-  H30, no gain for the small systems), kept correct by ``tests/test_gpu_drivers.py``.
+  H30, no gain for the small systems), kept correct by ``tests/test_gpu_drivers.py``.  A graph keeps the source
+addresses of its copies, so in graph mode every geometry is copied into this evaluator's own staging slabs (never
+uploaded from a producer's pinned buffers).
 
 No CPU fallback: the step only contains HIP work of ``libevcont_hip.so`` and copies.
 """
@@ -141,8 +143,14 @@ class HostedEvaluator:
                 if _CHECK_SYM != "0" and not getattr(ao, "integral_symmetry", False):
                     check_integral_symmetry(np.asarray(ao.eri), np.asarray(ao.eri_ip1), n, what="HostedEvaluator.stage")
                 self._sym_checked = True
-            self._direct_slabs = slabs      # the producer's two pinned slabs ARE the staging buffers of this step
             self._direct = {"eri": None, "eri_ip1": None}
+            if self.use_graph:
+                # (a captured step keeps the source addresses of its copies: it may upload from this evaluator's own
+                #  slabs only)
+                for (hs, _), src in zip(self._slabs, slabs):
+                    hs.copy_(src)
+                return
+            self._direct_slabs = slabs      # the producer's two pinned slabs ARE the staging buffers of this step
             return
         for k in ("S", "hcore", "ipovlp", "dhcore", "gnuc"):
             np.copyto(st[k], np.asarray(getattr(ao, k), dtype=np.float64).reshape(st[k].shape))
@@ -170,7 +178,7 @@ class HostedEvaluator:
             if (not self.zero_copy and src.size == st[k].size and src.dtype == np.float64 and src.flags.c_contiguous
                     and src.flags.writeable and src.nbytes >= (1 << 20)):
                 tsrc = torch.from_numpy(src.reshape(-1))
-                if tsrc.is_pinned():          # the producer's own pinned buffer: uploaded from there
+                if tsrc.is_pinned() and not self.use_graph:   # the producer's own pinned buffer: uploaded from there
                     self._direct[k] = tsrc
                     continue
             np.copyto(st[k], src.reshape(st[k].shape))

@@ -139,17 +139,20 @@ def make_ao_arrays(nao: int, natm: int, seed: int,
                     integral_symmetry=bool(ip1_rs_symmetric or not with_ip1))
 
 
-def make_trdms(nao: int, ntrain: int, seed: int):
-    """(S_train, one_RDM (T,T,N,N), two_RDM (T,T,N,N,N,N)) with the symmetries above."""
+def make_trdms(nao: int, ntrain: int, seed: int, bra_ket_symmetric: bool = True):
+    """(S_train, one_RDM (T,T,N,N), two_RDM (T,T,N,N,N,N)) with the symmetries above.  ``bra_ket_symmetric=False``:
+    the blocks (a,b) and (b,a) are independent (one- and two-body; the two-body blocks keep (pq)<->(rs)) -- data the
+    reference's layouts 6 / 3 accept, but the pair layouts and the compressed one cannot hold."""
     rng = np.random.default_rng(seed)
     n, T = nao, ntrain
     A = rng.standard_normal((T, T))
     S_train = A @ A.T / T + np.eye(T)
     d = rng.standard_normal((T, T, n, n)) / n
-    one = 0.5 * (d + d.transpose(1, 0, 3, 2))
+    one = 0.5 * (d + d.transpose(1, 0, 3, 2)) if bra_ket_symmetric else d
     g = rng.standard_normal((T, T, n, n, n, n)) / (n * n)
     g = 0.5 * (g + g.transpose(0, 1, 4, 5, 2, 3))          # (pq)<->(rs)
-    g = 0.5 * (g + g.transpose(1, 0, 3, 2, 5, 4))          # bra<->ket with p<->q, r<->s
+    if bra_ket_symmetric:
+        g = 0.5 * (g + g.transpose(1, 0, 3, 2, 5, 4))      # bra<->ket with p<->q, r<->s
     return S_train, np.ascontiguousarray(one), np.ascontiguousarray(g)
 
 

@@ -110,7 +110,8 @@ int evc_four_index_transform(const double *in, const double *C, int c_transposed
                              double *out, double *tmp, double *three_quarter, void *stream);
 
 /* ---------------------------------------------------------------------------------
- * K1/K2  Loewdin orthogonalisation on one workgroup (parallel cyclic Jacobi in LDS)
+ * K1/K2  Loewdin orthogonalisation on one workgroup (Jacobi eigensolver: one-sided on one wave, started in FP32 and
+ *        refined in FP64, for n <= 32; two-sided in LDS beyond)
  *   S = U diag(s) U^T ; X = U diag(s>1e-15 ? s^-1/2 : 0) U^T ; h1 = X^T hcore X
  *   replaces get_loewdin_trafo (electron_integral_utils.py:6-18) and the h1 rotation
  *   (:135, ab_initio_gradients_loewdin.py:338).  hcore/h1 may be NULL.  n <= 80 (96 inside the fused pipeline, which lends
@@ -215,12 +216,13 @@ typedef struct evc_outputs {
 #define EVC_FLAG_IP1_S2KL 8     /* geometry.eri_ip1 is (3,N,N,N(N+1)/2) [per geometry of a batch]: int2e_ip1 packed in its
                                    last two AO indices, element (x,p,q,k(k+1)/2+l), k >= l -- what PySCF returns for
                                    mol.intor("int2e_ip1", aosym="s2kl").  Half the bytes of the largest input; the
-                                   contraction then streams dense rows.  Only with EVC_LAYOUT_SYM8 and N <= 32 (the
-                                   path that uses the r <-> s symmetry of int2e_ip1 anyway). */
+                                   contraction then streams dense rows.  Only with EVC_LAYOUT_SYM8 and N <= 64 (the
+                                   path that uses the r <-> s symmetry of int2e_ip1 anyway; beyond 32 orbitals
+                                   together with EVC_FLAG_ERI_S4). */
 #define EVC_FLAG_ERI_S4 16      /* geometry.eri is the dense (Ms,Ms) matrix, Ms = N(N+1)/2 [per geometry of a batch]: int2e
                                    packed in both index pairs, element (p(p+1)/2+q, r(r+1)/2+s), p >= q, r >= s -- what PySCF
                                    returns for mol.intor("int2e", aosym="s4").  A quarter of the bytes.  Fused entry points,
-                                   EVC_LAYOUT_SYM8 and N <= 32 only. */
+                                   EVC_LAYOUT_SYM8 and N <= 64 only. */
 
 #define EVC_FLAG_LOEWDIN_DONE 32 /* the workspace already holds X, U, s and h1 of THESE geometries (evc_phase_loewdin_batch
                                    ran on it): phase A skips the Loewdin kernel.  Lets a host overlap that latency-bound

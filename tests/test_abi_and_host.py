@@ -260,6 +260,78 @@ def test_default_compression_is_decided_per_call():
         aec.set_trdm_compression(old)
 
 
+def test_auto_decision_follows_every_molecule():
+    """"auto" decides once per training set on its first molecule, and then checks every later array-level molecule
+    that declares nothing (a random sample of its integrals): one without the symmetries runs on the caller's layout.
+    A declared molecule is taken at its word (no per-call cost: what the pinned, packed inputs of bench.py declare).
+    Energy-only calls do not read eri_ip1, so a general eri_ip1 keeps them on the compressed layout.  The training set
+    here is pair-packed (ndim 2): no bra<->ket blocks to compare, no device needed."""
+    from evcont_amd import ab_initio_eigenvector_continuation as aec, cache
+    from evcont_amd.synthetic import make_ao_arrays, make_trdms, pack_rows
+    S, one, two = make_trdms(5, 3, 11)
+    two_p = pack_rows(two, True, True)
+    sym = make_ao_arrays(5, 2, 12, ip1_rs_symmetric=True)
+    gen = make_ao_arrays(5, 2, 13)
+    for ao in (sym, gen):
+        ao.integral_symmetry = None
+    rc = lambda m, **kw: aec.resolve_compression("auto", one, two_p, S, m, **kw)
+    aec._auto_decisions.clear()
+    assert rc(sym) == "sym8"
+    assert rc(gen) is None                               # the cached decision does not carry over
+    assert rc(gen, need_grad=False) == "sym8"            # eri is 8-fold symmetric: exact for the energy
+    assert rc(sym) == "sym8"
+    gen.integral_symmetry = True                         # declared: not checked (the caller's promise)
+    assert rc(gen) == "sym8"
+    sym.integral_symmetry = False
+    assert rc(sym) is None
+    bad = make_ao_arrays(5, 2, 14, ip1_rs_symmetric=True)
+    bad.integral_symmetry = None
+    bad.eri = bad.eri + 1.0e-3 * np.random.default_rng(0).standard_normal(bad.eri.shape)   # eri no longer symmetric
+    assert rc(bad) is None and rc(bad, need_grad=False) is None
+    # a training set the compressed layout refused (bra<->ket partner blocks that differ, found on the device when its
+    # compressed copy is made: ab_initio_eigenvector_continuation._trdms_auto) stays on the caller's layout
+    aec._auto_decisions[cache.key_of(one, two_p, S, ("auto",))] = False
+    sym.integral_symmetry = None
+    assert rc(sym) is None
+    assert aec.resolve_compression("sym8", one, two_p, S, sym) == "sym8"
+    aec._auto_decisions.clear()
+
+
+@pytest.mark.parametrize("ndim", [6, 3])
+def test_sym8_bra_ket_rule_on_host(ndim):
+    """The row comparison DeviceTRDMs.compress_sym8_ runs before it keeps one block per pair (evaluator.
+    sym8_rows_differ), on CPU tensors: bra<->ket symmetric data (make_trdms, container data) pass -- the partner rows
+    are summed in another order, so a difference at rounding level is no mismatch --, independent blocks fail, and so
+    does a perturbation far below the data's size but far above rounding."""
+    import torch
+    from evcont_amd.evaluator import sym8_column_images, sym8_gather_sums, sym8_rows_differ
+    from evcont_amd.synthetic import make_trdms, pack_rows
+    n, T = 4, 3
+    idx = [torch.from_numpy(ix) for ix in sym8_column_images(ndim, n)]
+    a, b = np.tril_indices(T)
+
+    def differ(two):
+        m = torch.from_numpy((pack_rows(two, False, True) if ndim == 3 else two).reshape(T * T, -1))
+        ab, ba = m[torch.from_numpy(a * T + b)], m[torch.from_numpy(b * T + a)]
+        return sym8_rows_differ(ab, sym8_gather_sums(ab.clone(), idx), ba, idx).numpy()
+
+    _, _, two = make_trdms(n, T, 21)
+    assert not differ(two).any()
+    # the container form: the SAME matrix in both blocks
+    same = two.copy()
+    for i, j in zip(a, b):
+        same[j, i] = same[i, j]
+    assert not differ(same).any()
+    noisy = two * (1.0 + 2.0e-16 * np.random.default_rng(1).standard_normal(two.shape))   # rounding-level noise
+    assert not differ(noisy).any()
+    _, _, asym = make_trdms(n, T, 22, bra_ket_symmetric=False)
+    assert np.array_equal(differ(asym), a != b)          # the diagonal blocks are their own partners
+    off = two.copy()
+    off[2, 0, 1, 2, 3, 0] += 1.0e-9 * np.abs(two).max()
+    off[2, 0, 3, 0, 1, 2] += 1.0e-9 * np.abs(two).max()  # (keeps (pq)<->(rs))
+    assert np.array_equal(differ(off), (a == 2) & (b == 0))
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 5])
 def test_sym8_column_images_reproduce_the_symmetrised_tensor(n):
     """Host half of DeviceTRDMs.compress_sym8_: the eight gather columns per compressed entry, for the unpacked and
