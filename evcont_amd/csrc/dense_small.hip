@@ -2062,6 +2062,12 @@ __global__ __launch_bounds__(kThreads) void subspace_loewdin_kernel(SolveArgs sa
     else loewdin_body(la, (int64_t)blockIdx.x - count);
 }
 
+// The host's view of the few-roots condition of subspace_body: whether the kernel tries the tridiagonal route (it still
+// falls through to the full eigensolver when the route's own check fails on the device).
+static bool subspace_few_tried(const SolveArgs &a) {
+    return a.few && !(a.warm && a.vstd) && a.fast && a.nroots <= few::kMaxRoots && a.T >= 2;
+}
+
 int launch_subspace_loewdin(const SolveArgs &s_in, const LoewdinArgs &l_in, int count, hipStream_t st) {
     SolveArgs a = s_in;
     LoewdinArgs l = l_in;
@@ -2081,6 +2087,7 @@ int launch_subspace_loewdin(const SolveArgs &s_in, const LoewdinArgs &l_in, int 
     hipLaunchKernelGGL(subspace_loewdin_kernel, dim3(2 * count), dim3(kThreads), lds_s > lds_l ? lds_s : lds_l, st, a, l,
                        count);
     EVC_LAUNCH_CHECK("subspace_loewdin");
+    note_kernel(EVC_PROF_SUBSPACE, "subspace_loewdin_kernel few=%d", subspace_few_tried(a) ? 1 : 0);
     return 0;
 }
 
@@ -2098,6 +2105,7 @@ int launch_subspace_solve(const SolveArgs &a_in, int count, hipStream_t st) {
     if (int rc = allow_dynamic_lds(subspace_kernel, attr, 160 * 1024, "subspace_solve")) return rc;
     hipLaunchKernelGGL(subspace_kernel, dim3(count), dim3(kThreads), lds, st, a);
     EVC_LAUNCH_CHECK("subspace_solve");
+    note_kernel(EVC_PROF_SUBSPACE, "subspace_kernel few=%d", subspace_few_tried(a) ? 1 : 0);
     return 0;
 }
 
@@ -2263,6 +2271,7 @@ int launch_unpack8_prep(const GradPrepArgs &a, const double *packed, int64_t sp,
     hipLaunchKernelGGL(unpack8_prep_kernel, dim3((unsigned)(count + bpg * count)), dim3(kThreads), grad_prep_lds(a.n), st, a,
                        packed, sp, SB, sws, count, pair_ld(a.n));
     EVC_LAUNCH_CHECK("unpack8_prep");
+    note_kernel(EVC_PROF_UNPACK, "unpack8_prep_kernel");
     return 0;
 }
 

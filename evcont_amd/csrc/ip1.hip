@@ -231,6 +231,7 @@ int launch_ip1_dh(const Ip1Args &a, int count, hipStream_t st) {
         default: hipLaunchKernelGGL(ip1_dh_kernel<4>, dim3(blocks, (unsigned)count), dim3(256), 0, st, a); break;
     }
     EVC_LAUNCH_CHECK("ip1_dh");
+    note_kernel(EVC_PROF_IP1, "ip1_dh_kernel<%d> %s", ip1_per_thread(), pair_blocks ? "pairs" : "chunks");
     return 0;
 }
 

@@ -78,6 +78,7 @@ int launch_pack(const double *h2, int64_t sh2, int n, double mult, double *out, 
     hipLaunchKernelGGL(pack_kernel, dim3(grid_for(out_len, 256), (unsigned)count), dim3(256), 0, st, h2, sh2, n, mult,
                        out, sout, M, out_len);
     EVC_LAUNCH_CHECK("pack_pair_sym");
+    note_kernel(EVC_PROF_UNPACK, "pack_kernel");
     return 0;
 }
 
@@ -87,6 +88,7 @@ int launch_pack_sym8(const double *h2, int64_t sh2, int n, double mult, double *
     hipLaunchKernelGGL(pack_sym8_kernel, dim3(grid_for(out_len, 256), (unsigned)count), dim3(256), 0, st, h2, sh2, n,
                        mult, out, sout, M, out_len);
     EVC_LAUNCH_CHECK("pack_sym8");
+    note_kernel(EVC_PROF_UNPACK, "pack_sym8_kernel");
     return 0;
 }
 
@@ -94,6 +96,7 @@ int launch_unpack(const double *p, int64_t sp, int n, double *out, int64_t sout,
     const int64_t n4 = (int64_t)n * n * n * n;
     hipLaunchKernelGGL(unpack_kernel, dim3(grid_for(n4, 256), (unsigned)count), dim3(256), 0, st, p, sp, n, out, sout);
     EVC_LAUNCH_CHECK("unpack_pair_sym");
+    note_kernel(EVC_PROF_UNPACK, "unpack_kernel");
     return 0;
 }
 
@@ -122,6 +125,7 @@ int launch_sym_oao_t(const double *G, int64_t sG, int n, double *out, int64_t so
     hipLaunchKernelGGL(sym_oao_t_kernel, dim3(grid_for(n4, 256), (unsigned)count), dim3(256), 0, st, G, sG, n, out,
                        sout);
     EVC_LAUNCH_CHECK("sym_oao_t");
+    note_kernel(EVC_PROF_UNPACK, "sym_oao_t_kernel");
     return 0;
 }
 
@@ -180,6 +184,7 @@ int launch_unpack_sym(const double *packed, int64_t sp, int n, double *GsT, doub
     hipLaunchKernelGGL(unpack_sym_kernel, dim3((unsigned)(n * n * count)), dim3(256), lds, st, packed, sp, n, GsT, SB,
                        sws, G, sG, count);
     EVC_LAUNCH_CHECK("unpack_sym");
+    note_kernel(EVC_PROF_UNPACK, "unpack_sym_kernel");
     return 0;
 }
 
@@ -287,6 +292,7 @@ int launch_unpack8(const double *packed, int64_t sp, int n, double *SB, int64_t 
         hipLaunchKernelGGL(unpack8_pairs_kernel, dim3((unsigned)(bpg * count)), dim3(256), 0, st, packed, sp, n, SB,
                            sws, count, pair_ld(n));
         EVC_LAUNCH_CHECK("unpack8_pairs");
+        note_kernel(EVC_PROF_UNPACK, "unpack8_pairs_kernel");
         return 0;
     }
     if (lead_half && !G) {
@@ -294,11 +300,13 @@ int launch_unpack8(const double *packed, int64_t sp, int n, double *SB, int64_t 
         hipLaunchKernelGGL(unpack8_half_kernel, dim3((unsigned)(bpg * count)), dim3(256), 0, st, packed, sp, n, SB, sws,
                            count);
         EVC_LAUNCH_CHECK("unpack8_half");
+        note_kernel(EVC_PROF_UNPACK, "unpack8_half_kernel");
         return 0;
     }
     hipLaunchKernelGGL(unpack8_kernel, dim3((unsigned)(n * n * count)), dim3(256), 0, st, packed, sp, n, SB, sws, G, sG,
                        count, lead_half);
     EVC_LAUNCH_CHECK("unpack8");
+    note_kernel(EVC_PROF_UNPACK, "unpack8_kernel lead_half=%d", lead_half);
     return 0;
 }
 

@@ -38,6 +38,16 @@ void note_kernel(int stage, const char *fmt, ...) {
     vsnprintf(g_kernel_ran[stage], sizeof(g_kernel_ran[stage]), fmt, ap);
     va_end(ap);
 }
+// Entry points clear the records of the stages they can launch, so that a stage the call did not run reports "".
+constexpr unsigned kStagesAll = (1u << kProfStages) - 1u;
+constexpr unsigned kStagesHamiltonian =
+    (1u << EVC_PROF_LOEWDIN) | (1u << EVC_PROF_PAIR_TRANSFORM) | (1u << EVC_PROF_ROWS) | (1u << EVC_PROF_UNPACK);
+constexpr unsigned kStagesGradient = (1u << EVC_PROF_COLS) | (1u << EVC_PROF_UNPACK) | (1u << EVC_PROF_Y2) |
+                                     (1u << EVC_PROF_PAIR_TRANSFORM) | (1u << EVC_PROF_IP1);
+static void clear_kernels(unsigned mask) {
+    for (int s = 0; s < kProfStages; ++s)
+        if (mask >> s & 1u) g_kernel_ran[s][0] = '\0';
+}
 constexpr int kProfPerSample = 16;   // event pairs one evaluation can record
 struct Prof {
     std::atomic<bool> on{false};
@@ -1009,6 +1019,7 @@ extern "C" size_t evc_workspace_bytes_batch(const evc_trdm_set *t, int natm, int
 extern "C" int evc_phase_hamiltonian(const evc_trdm_set *t, const evc_geometry *g, int flags, void *ws, size_t ws_bytes,
                                      double **h2rows_local, double **h1rows, void *stream) {
     EVC_SETUP(false);
+    clear_kernels(kStagesHamiltonian);
     w.warm = (flags & EVC_FLAG_WARM_START) != 0;
     Geo gg = geo;
     gg.eri_s4 = (flags & EVC_FLAG_ERI_S4) ? 1 : 0;
@@ -1023,6 +1034,7 @@ extern "C" int evc_phase_solve(const evc_trdm_set *t, const evc_geometry *g, con
                                const evc_outputs *out, int nroots, int flags, void *ws, size_t ws_bytes, void *stream) {
     EVC_SETUP(false);
     EVC_REQUIRE(nroots >= 1 && nroots <= t->ntrain, "nroots=%d out of range 1..%d", nroots, t->ntrain);
+    clear_kernels(1u << EVC_PROF_SUBSPACE);
     w.warm = (flags & EVC_FLAG_WARM_START) != 0;
     return phase_solve(t, geo, h2rows_all ? h2rows_all : w.h2rows, 0, out_single(out), nroots, w, st);
 }
@@ -1042,12 +1054,14 @@ extern "C" int evc_phase_gradient(const evc_trdm_set *t, const evc_geometry *g, 
                                   int flags, void *ws, size_t ws_bytes, void *stream) {
     EVC_SETUP(true);
     EVC_REQUIRE(out && out->grad, "outputs.grad is required");
+    clear_kernels(kStagesGradient);
     return phase_gradient(t, geo, out_single(out), flags, w, st);
 }
 
 extern "C" int evc_energy_with_grad(const evc_trdm_set *t, const evc_geometry *g, const evc_outputs *out,
                                     int nroots, int flags, void *ws, size_t ws_bytes, void *stream) {
     const bool energy_only = (flags & EVC_FLAG_ENERGY_ONLY) != 0;
+    clear_kernels(kStagesAll);
     EVC_SETUP(!energy_only);
     EVC_REQUIRE(out != nullptr, "outputs is NULL");
     EVC_REQUIRE(nroots >= 1 && nroots <= t->ntrain, "nroots=%d out of range 1..%d", nroots, t->ntrain);
@@ -1128,6 +1142,7 @@ extern "C" int evc_energy_with_grad_batch(const evc_trdm_set *t, const evc_geome
                                           const evc_outputs_batch *ob, int nroots, int flags, void *ws,
                                           size_t ws_bytes, void *stream) {
     const bool energy_only = (flags & EVC_FLAG_ENERGY_ONLY) != 0;
+    clear_kernels(kStagesAll);
     Ws w;
     Geo g;
     Out o;
@@ -1152,6 +1167,7 @@ extern "C" int evc_energy_with_grad_batch(const evc_trdm_set *t, const evc_geome
 
 extern "C" int evc_phase_loewdin_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, int flags, void *ws,
                                        size_t ws_bytes, void *stream) {
+    clear_kernels(1u << EVC_PROF_LOEWDIN);
     if (check_set(t)) return -1;
     EVC_REQUIRE(gb && gb->count >= 1 && gb->count <= 4096 && gb->S && gb->hcore,
                 "evc_phase_loewdin_batch: batch descriptor / S / hcore missing");
@@ -1183,6 +1199,7 @@ extern "C" int evc_phase_loewdin_batch(const evc_trdm_set *t, const evc_geometry
 extern "C" int evc_phase_hamiltonian_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, int flags,
                                            double *rows_out, int64_t ld_rows_out, void *ws, size_t ws_bytes,
                                            void *stream) {
+    clear_kernels(kStagesHamiltonian);
     Ws w;
     Geo g;
     Out o;
@@ -1199,6 +1216,7 @@ extern "C" int evc_phase_hamiltonian_batch(const evc_trdm_set *t, const evc_geom
 extern "C" int evc_phase_solve_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, const double *h2rows_all,
                                      int64_t ld_rows_all, const evc_outputs_batch *ob, int nroots, int flags,
                                      void *ws, size_t ws_bytes, void *stream) {
+    clear_kernels(1u << EVC_PROF_SUBSPACE);
     Ws w;
     Geo g;
     Out o;
@@ -1216,6 +1234,7 @@ extern "C" int evc_phase_solve_batch(const evc_trdm_set *t, const evc_geometry_b
 extern "C" int evc_phase_gradient_batch(const evc_trdm_set *t, const evc_geometry_batch *gb,
                                         const evc_outputs_batch *ob, int flags, void *ws, size_t ws_bytes,
                                         void *stream) {
+    clear_kernels(kStagesGradient);
     Ws w;
     Geo g;
     Out o;

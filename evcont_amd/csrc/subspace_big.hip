@@ -960,6 +960,9 @@ int launch_subspace_big(const SolveArgs &a_in, int count, hipStream_t st) {
         hipLaunchKernelGGL(subspace_big_kernel<false>, dim3(count), dim3(kBT), big_aux_bytes(a.T), st, a);
     }
     EVC_LAUNCH_CHECK("subspace_big");
+    // (few: the tridiagonal route is tried -- the LDS-resident kernel only)
+    note_kernel(EVC_PROF_SUBSPACE, "subspace_big_kernel<%d> few=%d", big_fits_lds(a.T) ? 1 : 0,
+                big_fits_lds(a.T) && a.few && a.nroots <= kFewRoots && a.T <= 128 ? 1 : 0);
     return 0;
 }
 

@@ -115,6 +115,7 @@ static int qt_launch(const double *in, int64_t sin, const double *C, int64_t sC,
     hipLaunchKernelGGL(qt_kernel<NPAD>, dim3((unsigned)blocks, (unsigned)count), dim3(256), 0, st, in, sin, C, sC, ct,
                        n, rows, out, sout);
     EVC_LAUNCH_CHECK("quarter_transform");
+    note_kernel(EVC_PROF_PAIR_TRANSFORM, "qt_kernel<%d>", NPAD);
     return 0;
 }
 

@@ -361,6 +361,7 @@ int launch_y2_sb(const double *SB, const double *K3, int n, double *partial, int
         default: set_error("y2: n=%d not supported by the gradient path (1..128)", n); return -1;
     }
     EVC_LAUNCH_CHECK("y2_sb");
+    note_kernel(EVC_PROF_Y2, "y2_sb_kernel<%d>", nt > 4 ? 4 : nt);
     return 0;
 }
 
@@ -377,6 +378,7 @@ int launch_y2(const double *GsT, const double *K3, int n, double *partial, int64
         default: set_error("y2: n=%d not supported by the gradient path (1..128)", n); return -1;
     }
     EVC_LAUNCH_CHECK("y2");
+    note_kernel(EVC_PROF_Y2, "y2_kernel<%d>", nt > 4 ? 4 : nt);
     return 0;
 }
 

@@ -382,7 +382,9 @@ int evc_profile_stage(int stage, double *ms, int *launches);
 int evc_profile_select(unsigned stage_mask);
 /* Name (with template arguments) of the kernel the library most recently launched for a stage, e.g.
  * "gemv_rows_lds_kernel<2,7,2> G=32" (K5 / EVC_PROF_ROWS: followed by the geometries that launch contracted): what a
- * measurement of that stage timed.  "" before the first launch.  Process-wide. */
+ * measurement of that stage timed.  Every entry point first clears the stages it can launch (evc_energy_with_grad and
+ * evc_energy_with_grad_batch all eight, an evc_phase_* call the stages of its phase), so a stage the last call did not
+ * run reads "".  Process-wide: not meaningful while calls run concurrently on several host threads. */
 const char *evc_profile_kernel(int stage);
 
 #ifdef __cplusplus

@@ -56,7 +56,9 @@ def _full_size_case(n, A, T, sizes, seed, G, slots, packed_inputs=True):
     run = [a.packed_ip1(eri=True) for a in aos] if packed_inputs else aos
     got["sym8"] = be.energies_with_grads(DeviceAOBatch.stack(run))
     from evcont_amd import _lib
-    ran = {k: _lib.load().evc_profile_kernel(i).decode() for i, k in enumerate(("k5", "k8", "pair_transform"))}
+    # (what the sym8 call above launched: every stage clears its record on entry, so "" = the stage did not run)
+    ran = {k: _lib.load().evc_profile_kernel(i).decode()
+           for i, k in enumerate(("k5", "k8", "pair_transform", "ip1", "y2", "unpack", "loewdin", "subspace"))}
     worst = {"kernels": ran}
     for leg, (E, grad) in got.items():
         de = max(abs(E[k] - want[k][0]) for k in slots)
@@ -77,6 +79,22 @@ def test_h30_bench_default_against_oracle():
         assert ran["pair_transform"].startswith("ptd_kernel"), ran
     for leg, (de, dg) in worst.items():
         assert de < 1e-10 and dg < 1e-9, (leg, de, dg)     # what the kernels actually deliver
+
+
+def test_h2o_vtz_bench_config_against_oracle():
+    """``bench.py --workload H2Ovtz`` as it builds it: N=58, A=3 (AO slices 30/14/14), T=8, seed 1234 + 6, geometries
+    seed * 1000 + k, 32 per batch, sym8 from the pack2 rows with int2e / int2e_ip1 packed (s4 / s2kl): the 64-wide
+    symmetric pipeline (pt64_kernel, y2_64_kernel) and, at 32 geometries per call, the one-kernel Loewdin step.  Slots
+    0, 15, 16 and 31 against the oracle (both legs)."""
+    worst = _full_size_case(58, 3, 8, (30, 14, 14), 1240, 32, (0, 15, 16, 31))
+    ran = worst.pop("kernels")
+    want = {"pair_transform": "pt64_kernel<0>", "y2": "y2_64_kernel", "ip1": "ip1_dh_kernel<8> pairs",
+            "unpack": "unpack8_pairs_kernel", "loewdin": "loewdin_big_kernel part=0", "subspace": "subspace_kernel",
+            "k5": "gemv_rows_", "k8": "gemv_cols_"}
+    bad = {k: (ran[k], v) for k, v in want.items() if not ran[k].startswith(v)}
+    assert not bad, (bad, ran)
+    for leg, (de, dg) in worst.items():
+        assert de < 1e-10 and dg < 1e-9, (leg, de, dg)
 
 
 def test_zundel_shape_against_oracle():
