@@ -16,7 +16,7 @@ from .ab_initio_eigenvector_continuation import (approximate_ground_state_OAO, _
 from .electron_integral_utils import get_basis, get_integrals  # noqa: F401 (re-export)
 from .evaluator import ContinuationEvaluator, DeviceAO
 from .hosted import HostedEvaluator
-from .integrals import ao_arrays, aoslices_of, energy_nuc, grad_nuc, stage_mol
+from .integrals import ao_arrays, aoslices_of, energy_nuc, grad_nuc, is_array_mol, stage_mol
 
 
 def _grad_scanner_base():
@@ -142,6 +142,72 @@ def get_scanner(mol, one_rdm, two_rdm, overlap, hermitian=True, compress="defaul
             en, grad = self._hev.run()
             self._last = [mol, None, None]
             return en, grad
+
+    return Scanner()
+
+
+def get_state_scanner(mol, one_rdm, two_rdm, overlap, root, hermitian=True):
+    """``get_scanner`` for the continuation eigenstate ``root`` (0 = ground state): ``scanner(mol)`` returns
+    ``(E_root, grad_root)`` and ``scanner.base.predicted_one_rdm`` / ``predicted_two_rdm`` are that root's predicted
+    RDMs.  Each call evaluates the lowest ``root + 1`` energies and the gradient of ``root`` alone (one slot of
+    ``evc_phase_gradient_roots``); consecutive calls warm-start the eigensolvers.  Drives excited-state NVE through
+    ``nve_velocity_verlet(scanner, mol, ...)``.  At (near-)degenerate roots the forces follow whichever eigenvector
+    the solver returned: a trajectory through a crossing does not follow a diabatic state."""
+    from .ab_initio_eigenvector_continuation import resolve_compression
+    from .ab_initio_gradients_loewdin import get_multistate_energy_with_grad
+    root = int(root)
+    if root < 0:
+        raise ValueError(f"root={root} must be >= 0")
+
+    class Base:
+        converged = True
+        ovlp = overlap
+        one_trdm = one_rdm
+        two_trdm = two_rdm
+
+        def __init__(self, owner):
+            self._owner = owner
+
+        @property
+        def predicted_one_rdm(self):
+            return None if self._owner._last is None else self._owner._last[1]
+
+        @property
+        def predicted_two_rdm(self):
+            return self._owner._two()
+
+    class Scanner(_grad_scanner_base()):
+        def __init__(self):
+            self.mol = mol
+            self.root = root
+            self.base = Base(self)
+            self._ev = None
+            self._last = None         # (mol, D, G) of the last call; G on first access
+
+        def _two(self):
+            if self._last is None:
+                return None
+            if self._last[2] is None:
+                r = get_multistate_energy_with_grad(self._last[0], one_rdm, two_rdm, overlap, root + 1,
+                                                    hermitian=hermitian, return_density_matrices=True)
+                self._last[2] = r[-1][root]
+            return self._last[2]
+
+        def __call__(self, mol):
+            self.mol = mol
+            ao = ao_arrays(mol, need_grad=True)
+            if self._ev is None:
+                compress = resolve_compression("default", one_rdm, two_rdm, overlap,
+                                               ao if is_array_mol(mol) else mol, hermitian=hermitian)
+                t = _trdms_auto(one_rdm, two_rdm, overlap, compress) if get_trdm_compression() == "auto" else \
+                    _trdms(one_rdm, two_rdm, overlap, compress)
+                self._ev = ContinuationEvaluator(t, int(np.asarray(ao.aoslices).shape[0]), warm_start=True,
+                                                 want_two_rdm=False)
+            ev = self._ev
+            e, _, grads, D, _ = ev._roots(DeviceAO.from_arrays(ao, ev.t.device), root + 1, [(root, root)], True,
+                                          False, hermitian)
+            self._last = [mol, D[0].cpu().numpy(), None]
+            return float(e[root]), grads[0, : ev.natm].cpu().numpy()
 
     return Scanner()
 

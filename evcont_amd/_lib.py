@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(HERE, "libevcont_hip.so")
 LAYOUT_FULL6, LAYOUT_PAIR5, LAYOUT_ELEC3, LAYOUT_PACK2 = 6, 5, 3, 2
 LAYOUT_SYM8 = 8   # device-side 8-fold compressed layout (include/evcont_hip.h EVC_LAYOUT_SYM8)
 FLAG_ENERGY_ONLY, FLAG_PARTIAL_RANK, FLAG_WARM_START, FLAG_IP1_S2KL, FLAG_ERI_S4, FLAG_LOEWDIN_DONE = 1, 2, 4, 8, 16, 32
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 c_double_p = C.c_void_p  # device pointers travel as integers
 
@@ -51,6 +51,10 @@ class OutputsBatch(C.Structure):
                 ("d_pred", C.c_void_p), ("g_pred", C.c_void_p), ("hmat", C.c_void_p)]
 
 
+class OutputsRoots(C.Structure):
+    _fields_ = [("grad", C.c_void_p), ("d_pred", C.c_void_p), ("g_pred", C.c_void_p)]
+
+
 # symbol -> (restype, argtypes); also the list the CPU test checks against the header
 SIGNATURES = {
     "evc_abi_version": (C.c_int, []),
@@ -84,6 +88,10 @@ SIGNATURES = {
     "evc_phase_gradient": (C.c_int, [C.POINTER(TrdmSet), C.POINTER(Geometry), C.POINTER(Outputs), C.c_int,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_phase_set_coeffs": (C.c_int, [C.POINTER(TrdmSet), C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_workspace_bytes_roots": (C.c_size_t, [C.POINTER(TrdmSet), C.c_int, C.c_int]),
+    "evc_phase_gradient_roots": (C.c_int, [C.POINTER(TrdmSet), C.POINTER(Geometry), C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_int, C.POINTER(OutputsRoots), C.c_int, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
     "evc_energy_with_grad": (C.c_int, [C.POINTER(TrdmSet), C.POINTER(Geometry), C.POINTER(Outputs), C.c_int,
                                        C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_workspace_bytes_batch": (C.c_size_t, [C.POINTER(TrdmSet), C.c_int, C.c_int]),

@@ -106,3 +106,43 @@ def get_energy_with_grad(mol, one_RDM, two_RDM, S, hermitian=True, return_densit
                     auto=get_trdm_compression() == "auto")
     dao = DeviceAO.from_arrays(ao, ev.t.device)
     return ev.energy_with_grad(dao, return_density_matrices=return_density_matrices)
+
+
+def get_multistate_energy_with_grad(mol, one_RDM, two_RDM, S, nroots=1, hermitian=True, return_couplings=False,
+                                    return_density_matrices=False):
+    """Total energies ``E[nroots]`` and nuclear gradients ``grad[nroots,A,3]`` of the lowest ``nroots`` continuation
+    states at ``mol``'s geometry: ``get_energy_with_grad`` with the eigenvector c_k of root k in place of c_0
+    (S_train does not depend on the geometry, so dE_k/dR = c_k^T dH/dR c_k), all roots in one device pass.
+
+    ``return_couplings``: also ``h[nroots,nroots,A,3]``, the interstate coupling vectors c_k^T dH/dR c_l (symmetric in
+    k, l; the diagonal is the electronic gradient of root k; the derivative coupling is h_kl / (E_l - E_k)).
+    ``return_density_matrices``: also the predicted RDMs of every root, ``D[nroots,N,N]`` and ``G[nroots,N,N,N,N]``,
+    as ``get_energy_with_grad`` returns them.  Storage of the resident training data as for ``get_energy_with_grad``.
+    At (near-)degenerate roots the forces follow whichever eigenvectors the solver returned."""
+    nroots = int(nroots)
+    ao = ao_arrays(mol, need_grad=True)
+    natm = int(np.asarray(ao.aoslices).shape[0])
+    if not hermitian:
+        ev = _evaluator(one_RDM, two_RDM, S, natm, compress=None)
+    else:
+        ev = _evaluator(one_RDM, two_RDM, S, natm,
+                        compress=resolve_compression("default", one_RDM, two_RDM, S,
+                                                     mol if not is_array_mol(mol) else ao, hermitian=True,
+                                                     want_rdms=return_density_matrices),
+                        auto=get_trdm_compression() == "auto")
+    pairs = [(k, k) for k in range(nroots)]
+    if return_couplings:
+        pairs += [(k, l) for k in range(nroots) for l in range(k + 1, nroots)]
+    res = ev.energies_with_grads(DeviceAO.from_arrays(ao, ev.t.device), nroots, pairs,
+                                 return_density_matrices=return_density_matrices, hermitian=hermitian)
+    e, grads = res[0], res[2]
+    out = (e, grads[:nroots].copy())
+    if return_couplings:
+        h = np.zeros((nroots, nroots) + grads.shape[1:])
+        for p, (k, l) in enumerate(pairs):
+            h[k, l] = h[l, k] = grads[p]
+        h[np.arange(nroots), np.arange(nroots)] -= np.asarray(ao.gnuc, dtype=np.float64)
+        out += (h,)
+    if return_density_matrices:
+        out += (res[3][:nroots], res[4][:nroots])
+    return out

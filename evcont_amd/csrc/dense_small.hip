@@ -9,6 +9,7 @@
 // coalesced loads first, inner loops carry no integer division, and the 256 threads are
 // used as a 16x16 grid (tj = row group, tk = column group).
 #include <stdlib.h>
+#include <string.h>
 
 #include "common.hpp"
 #include "kernels.hpp"
@@ -2109,37 +2110,90 @@ int launch_subspace_solve(const SolveArgs &a_in, int count, hipStream_t st) {
     return 0;
 }
 
-// Row weights from a coefficient vector the caller supplies (the non-Hermitian branch: the T x T pencil is solved
-// with scipy.linalg.eig on the host, as the reference does, and its eigenvector comes back here).
-__global__ __launch_bounds__(256) void pair_weights_kernel(const double *__restrict__ c, int T, int pairs,
-                                                           double *__restrict__ w1, double *__restrict__ w2,
-                                                           int64_t w2_offset, int64_t w2_count) {
+// Row weights from coefficient vectors the caller supplies (the non-Hermitian branch: the T x T pencil is solved
+// with scipy.linalg.eig on the host, as the reference does, and its eigenvector comes back here), or of the symmetric
+// weighting W = (c_k c_l^T + c_l c_k^T) / 2 of a pair of roots (evc_phase_gradient_roots), one slot per blockIdx.y.
+// k == l evaluates exactly the single-vector expressions c_a c_b.
+__global__ __launch_bounds__(256) void pair_weights_kernel(PairWeightsArgs a) {
+    const int slot = (int)blockIdx.y, g = a.slot0 + slot;
+    const int T = a.T;
+    const double *ck = a.c + (int64_t)a.k[slot] * T, *cl = a.c + (int64_t)a.l[slot] * T;
+    const bool diag = a.k[slot] == a.l[slot];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (w1 && i < (int64_t)T * T) {
-        const int ia = (int)(i / T);
-        w1[i] = c[ia] * c[i - (int64_t)ia * T];
+    // transposed copies: [row][slot] in the workspace of the first slot of the group of kMaxBatchG (csrc/kernels.hpp)
+    const int64_t gt = (int64_t)(g - g % kMaxBatchG) * a.sw;
+    const int col = g % kMaxBatchG;
+    if (a.w1 && i < (int64_t)T * T) {
+        const int ia = (int)(i / T), ib = (int)(i - (int64_t)ia * T);
+        const double w = diag ? ck[ia] * ck[ib] : 0.5 * (ck[ia] * cl[ib] + cl[ia] * ck[ib]);
+        a.w1[(int64_t)g * a.sw + i] = w;
+        if (a.w1t) a.w1t[gt + i * kMaxBatchG + col] = w;
     }
-    if (w2 && i < w2_count) {
-        const int64_t g = i + w2_offset;
+    if (a.w2 && i < a.w2_count) {
+        const int64_t r = i + a.w2_offset;
         double w;
-        if (pairs) {
-            const int ia = (int)tri_row(g), ib = (int)(g - (int64_t)ia * (ia + 1) / 2);
-            w = (ia == ib) ? c[ia] * c[ia] : 2.0 * c[ia] * c[ib];
+        if (a.pairs) {
+            const int ia = (int)tri_row(r), ib = (int)(r - (int64_t)ia * (ia + 1) / 2);
+            if (diag) w = (ia == ib) ? ck[ia] * ck[ia] : 2.0 * ck[ia] * ck[ib];
+            else w = (ia == ib) ? ck[ia] * cl[ia] : ck[ia] * cl[ib] + cl[ia] * ck[ib];
         } else {
-            const int ia = (int)(g / T);
-            w = c[ia] * c[g - (int64_t)ia * T];
+            const int ia = (int)(r / T), ib = (int)(r - (int64_t)ia * T);
+            w = diag ? ck[ia] * ck[ib] : 0.5 * (ck[ia] * cl[ib] + cl[ia] * ck[ib]);
         }
-        w2[i] = w;
+        a.w2[(int64_t)g * a.sw + i] = w;
+        if (a.w2t) a.w2t[gt + i * kMaxBatchG + col] = w;
     }
+}
+
+static int pair_weights_launch(PairWeightsArgs &a, int nslots, hipStream_t st) {
+    const int64_t nmax = (int64_t)a.T * a.T > a.w2_count ? (int64_t)a.T * a.T : a.w2_count;
+    hipLaunchKernelGGL(pair_weights_kernel, dim3((unsigned)ceil_div(nmax, 256), (unsigned)nslots), dim3(256), 0, st, a);
+    EVC_LAUNCH_CHECK("pair_weights");
+    return 0;
+}
+
+static int layout_pairs(int layout) {
+    return (layout == EVC_LAYOUT_PAIR5 || layout == EVC_LAYOUT_PACK2 || layout == EVC_LAYOUT_SYM8) ? 1 : 0;
 }
 
 int launch_pair_weights(const double *c, int T, int layout, double *w1, double *w2, int64_t w2_offset,
                         int64_t w2_count, hipStream_t st) {
-    const int pairs = (layout == EVC_LAYOUT_PAIR5 || layout == EVC_LAYOUT_PACK2 || layout == EVC_LAYOUT_SYM8) ? 1 : 0;
-    const int64_t nmax = (int64_t)T * T > w2_count ? (int64_t)T * T : w2_count;
-    hipLaunchKernelGGL(pair_weights_kernel, dim3((unsigned)ceil_div(nmax, 256)), dim3(256), 0, st, c, T, pairs, w1, w2,
-                       w2_offset, w2_count);
-    EVC_LAUNCH_CHECK("pair_weights");
+    PairWeightsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.c = c;
+    a.T = T;
+    a.pairs = layout_pairs(layout);
+    a.w1 = w1;
+    a.w2 = w2;
+    a.w2_offset = w2_offset;
+    a.w2_count = w2_count;
+    return pair_weights_launch(a, 1, st);
+}
+
+int launch_pair_weights_slots(const double *c, int T, int layout, const int32_t *pairs, int npairs, double *w1,
+                              double *w2, double *w1t, double *w2t, int64_t sw, int64_t w2_offset, int64_t w2_count,
+                              hipStream_t st) {
+    PairWeightsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.c = c;
+    a.T = T;
+    a.pairs = layout_pairs(layout);
+    a.w1 = w1;
+    a.w2 = w2;
+    a.w1t = w1t;
+    a.w2t = w2t;
+    a.sw = sw;
+    a.w2_offset = w2_offset;
+    a.w2_count = w2_count;
+    for (int s0 = 0; s0 < npairs; s0 += kPairWeightsSlots) {
+        const int ns = npairs - s0 < kPairWeightsSlots ? npairs - s0 : kPairWeightsSlots;
+        a.slot0 = s0;
+        for (int s = 0; s < ns; ++s) {
+            a.k[s] = (int16_t)pairs[2 * (s0 + s)];
+            a.l[s] = (int16_t)pairs[2 * (s0 + s) + 1];
+        }
+        if (int rc = pair_weights_launch(a, ns, st)) return rc;
+    }
     return 0;
 }
 

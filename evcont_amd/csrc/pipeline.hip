@@ -825,7 +825,7 @@ static int phase_gradient(const evc_trdm_set *t, const Geo &g_in, const Out &out
     if (s2kl) {
         EVC_REQUIRE(is_sym8(t->layout) && (use_pair_transform(n) || use_pair64(t->layout, n, true)),
                     "EVC_FLAG_IP1_S2KL needs the compressed layout (EVC_LAYOUT_SYM8) and N <= 64");
-        if (cnt > 1) g.sip1 = (int64_t)3 * n * n * (n * (n + 1) / 2);
+        if (cnt > 1 && g.sip1) g.sip1 = (int64_t)3 * n * n * (n * (n + 1) / 2);   // (0: one geometry shared by the slots)
     }
     const int64_t sw = w.stride;
     int rc;
@@ -1080,6 +1080,125 @@ extern "C" int evc_energy_with_grad(const evc_trdm_set *t, const evc_geometry *g
     if ((rc = phase_solve(t, gg, nullptr, 0, o, nroots, w, st))) return rc;
     if (energy_only) return 0;
     return phase_gradient(t, gg, o, flags & ~EVC_FLAG_PARTIAL_RANK, w, st);
+}
+
+// ---- several roots of ONE geometry: evc_phase_gradient_roots ---------------------------------------------------
+// Slot p of the call is a batch "geometry" whose weights are those of the pair pairs[p] = (k, l); the geometry inputs
+// are shared (stride 0) and the per-geometry state phases A+B left in slot 0 (X, U, s, h1, K3) is copied into the
+// other slots, so that the batched gradient chain runs unchanged for count = npairs: K8 reads the t-RDM once per
+// kMaxBatchG slots.  Behind the npairs slot workspaces: the per-slot nuclear term (grad_nuc on the diagonal slots).
+constexpr int kMaxRootPairs = 4096;
+static size_t roots_gnuc_bytes(int natm, int npairs) {
+    return align_up((size_t)npairs * (natm > 0 ? natm : 1) * 3 * sizeof(double), 256);
+}
+
+extern "C" size_t evc_workspace_bytes_roots(const evc_trdm_set *t, int natm, int npairs) {
+    if (check_set(t)) return 0;
+    if (npairs < 1 || npairs > kMaxRootPairs) {
+        set_error("evc_workspace_bytes_roots: npairs=%d out of range 1..%d", npairs, kMaxRootPairs);
+        return 0;
+    }
+    Ws w;
+    carve(t, natm, nullptr, w);
+    return w.bytes * (size_t)npairs + roots_gnuc_bytes(natm, npairs);
+}
+
+// dst[s * pitch] = src[0] for s = 1 .. count-1 (bytes at a pitch of `pitch` bytes): log2(count) copies, each
+// doubling the filled prefix.
+static int fan_out(char *base, size_t bytes, size_t pitch, int count, hipStream_t st) {
+    if (pitch > (size_t)INT32_MAX) {   // (beyond the pitch a 2-D copy takes: one copy per slot)
+        for (int s = 1; s < count; ++s)
+            EVC_HIP(hipMemcpyAsync(base + (size_t)s * pitch, base, bytes, hipMemcpyDeviceToDevice, st));
+        return 0;
+    }
+    for (int have = 1; have < count;) {
+        const int m = count - have < have ? count - have : have;
+        EVC_HIP(hipMemcpy2DAsync(base + (size_t)have * pitch, pitch, base, pitch, bytes, (size_t)m,
+                                 hipMemcpyDeviceToDevice, st));
+        have += m;
+    }
+    return 0;
+}
+
+extern "C" int evc_phase_gradient_roots(const evc_trdm_set *t, const evc_geometry *g, const double *coeffs, int nvec,
+                                        const int32_t *pairs, int npairs, const evc_outputs_roots *out, int flags,
+                                        void *ws, size_t ws_bytes, void *stream) {
+    clear_kernels(kStagesGradient);
+    if (check_set(t)) return -1;
+    if (check_geometry(g, true)) return -1;
+    EVC_REQUIRE(coeffs && pairs, "evc_phase_gradient_roots: coeffs / pairs is NULL");
+    EVC_REQUIRE(out && out->grad, "evc_phase_gradient_roots: outputs.grad is required");
+    EVC_REQUIRE(!(flags & EVC_FLAG_PARTIAL_RANK), "evc_phase_gradient_roots: EVC_FLAG_PARTIAL_RANK is not supported");
+    EVC_REQUIRE(!(flags & ~EVC_FLAG_IP1_S2KL), "evc_phase_gradient_roots: flags=%d (only EVC_FLAG_IP1_S2KL is accepted)",
+                flags);
+    EVC_REQUIRE(npairs >= 1 && npairs <= kMaxRootPairs, "evc_phase_gradient_roots: npairs=%d out of range 1..%d", npairs,
+                kMaxRootPairs);
+    EVC_REQUIRE(nvec >= 1 && nvec <= t->ntrain, "evc_phase_gradient_roots: nvec=%d out of range 1..%d (T)", nvec,
+                t->ntrain);
+    for (int p = 0; p < npairs; ++p) {
+        const int k = pairs[2 * p], l = pairs[2 * p + 1];
+        EVC_REQUIRE(0 <= k && k <= l && l < nvec, "evc_phase_gradient_roots: pair %d = (%d, %d) outside 0 <= k <= l < nvec=%d",
+                    p, k, l, nvec);
+    }
+    EVC_REQUIRE(ws && aligned16(ws), "evc_phase_gradient_roots: workspace NULL or misaligned");
+    Ws w;
+    carve(t, g->natm, static_cast<char *>(ws), w);
+    const size_t need = w.bytes * (size_t)npairs + roots_gnuc_bytes(g->natm, npairs);
+    EVC_REQUIRE(ws_bytes >= need, "evc_phase_gradient_roots: workspace too small: %zu < %zu", ws_bytes, need);
+    replan(t, w, npairs);
+    hipStream_t st = as_stream(stream);
+    const int64_t sw = w.stride, A3 = (int64_t)g->natm * 3;
+    int rc;
+    // (1) row weights of every slot (+ the transposed group copies the batched K8 reads)
+    if ((rc = launch_pair_weights_slots(coeffs, t->ntrain, t->layout, pairs, npairs, w.w1, w.w2,
+                                        npairs > 1 ? w.w1t : nullptr, npairs > 1 ? w.w2t : nullptr, sw, t->row_offset,
+                                        t->rows2, st)))
+        return rc;
+    // (2) slot 0's geometry state into the other slots; U and s may still come from the side stream (phase A of an
+    //     energy-only call)
+    if ((rc = side_join(w.base, st))) return rc;
+    char *b0 = static_cast<char *>(ws);
+    const size_t pitch = w.bytes;
+    if (npairs > 1) {
+        // X, U, s, lflag, h1 (consecutive at the head of a slot) and K3: what phase A left there for Y2, the dense
+        // (pair, pair) intermediate of its first pair step where Y2 recomputes the half-transformed integrals
+        const int n = t->n;
+        const bool pairs_route = use_pair_transform(n) || use_pair64(t->layout, n, (flags & EVC_FLAG_IP1_S2KL) != 0);
+        const size_t k3 = (pairs_route && use_fused_y2(is_sym8(t->layout), n)) ? (size_t)pair_ld(n) * pair_ld(n)
+                                                                                 : (size_t)n * n * n * n;
+        if ((rc = fan_out(b0, (size_t)((char *)(w.h1 + (size_t)n * n) - (char *)w.X), pitch, npairs, st))) return rc;
+        if ((rc = fan_out((char *)w.K3, sizeof(double) * k3, pitch, npairs, st))) return rc;
+    }
+    // (3) nuclear term on the diagonal slots only
+    double *gnuc = nullptr;
+    if (g->gnuc) {
+        gnuc = reinterpret_cast<double *>(b0 + w.bytes * (size_t)npairs);
+        bool all_diag = true;
+        for (int p = 0; p < npairs; ++p) all_diag = all_diag && pairs[2 * p] == pairs[2 * p + 1];
+        if (all_diag) {
+            EVC_HIP(hipMemcpyAsync(gnuc, g->gnuc, sizeof(double) * A3, hipMemcpyDeviceToDevice, st));
+            if ((rc = fan_out((char *)gnuc, sizeof(double) * A3, sizeof(double) * A3, npairs, st))) return rc;
+        } else {
+            EVC_HIP(hipMemsetAsync(gnuc, 0, sizeof(double) * A3 * npairs, st));
+            for (int p = 0; p < npairs; ++p)
+                if (pairs[2 * p] == pairs[2 * p + 1])
+                    EVC_HIP(hipMemcpyAsync(gnuc + p * A3, g->gnuc, sizeof(double) * A3, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    // (4) the gradient chain for count = npairs slots of one geometry (every geometry stride 0)
+    Geo gg = geo_single(g);
+    gg.count = npairs;
+    gg.gnuc = gnuc;
+    gg.sgn = A3;
+    Out o;
+    memset(&o, 0, sizeof(o));
+    o.grad = out->grad;
+    o.sg = A3;
+    o.d_pred = out->d_pred;
+    o.sd = (int64_t)t->n * t->n;
+    o.g_pred = out->g_pred;
+    o.sG = o.sd * o.sd;
+    return phase_gradient(t, gg, o, flags, w, st);
 }
 
 // Shared argument checking / descriptor set-up of the batch entry points.

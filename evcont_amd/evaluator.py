@@ -738,7 +738,8 @@ class ContinuationEvaluator:
             raise _lib.EvcontHipError("evc_workspace_bytes: " + self.lib.evc_last_error().decode())
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=d)   # (zero-filled: see BatchedEvaluator)
         self.ws_bytes = nbytes
-        weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr()).atexit = False
+        self._ws_release = weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr())
+        self._ws_release.atexit = False
         self.energy = torch.zeros(T, dtype=F64, device=d)
         self.coeffs = torch.zeros((T, T), dtype=F64, device=d)
         self.grad = torch.zeros((max(self.natm, 1), 3), dtype=F64, device=d)
@@ -859,6 +860,94 @@ class ContinuationEvaluator:
                 raise _lib.EvcontHipError("this evaluator was built with want_two_rdm=False")
             return e + ao.enuc, g, self.d_pred.cpu().numpy().copy(), self.g_pred.cpu().numpy().copy()
         return e + ao.enuc, g
+
+    # -- several roots of one geometry (evc_phase_gradient_roots) ------------------------------------------
+    def _grow_workspace(self, nbytes: int) -> None:
+        """Enlarge the workspace to ``nbytes`` (never shrinks).  Slot 0 keeps its place and its contents (the cached
+        factorisation of S_train, the warm-start eigenvectors); the rest is zero-filled."""
+        if nbytes <= self.ws_bytes:
+            return
+        st = self.stream if self.stream is not None else torch.cuda.current_stream(self.t.device)
+        self._ws_release()          # waits for a side-stream launch into the old workspace, drops its events
+        ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.t.device)
+        with torch.cuda.stream(st):
+            ws[: self.ws_bytes].copy_(self.ws)
+        st.synchronize()
+        self.ws, self.ws_bytes = ws, nbytes
+        self._ws_release = weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr())
+        self._ws_release.atexit = False
+
+    def _roots(self, ao: DeviceAO, nroots: int, pairs, want_d: bool, want_g: bool, hermitian: bool):
+        """Enqueue energies + the gradient slots of ``pairs``; returns host E, C and the device output tensors."""
+        T, n = self.t.T, self.t.n
+        nroots = int(nroots)
+        if not 1 <= nroots <= T:
+            raise ValueError(f"nroots={nroots} out of range 1..{T}")
+        if pairs is None:
+            pairs = [(k, k) for k in range(nroots)]
+        P = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        npairs = P.shape[0]
+        nbytes = self.lib.evc_workspace_bytes_roots(C.byref(self.t.cstruct), self.natm, npairs)
+        if nbytes == 0:
+            raise _lib.EvcontHipError("evc_workspace_bytes_roots: " + self.lib.evc_last_error().decode())
+        self._grow_workspace(nbytes)
+        if hermitian:
+            _check_sym_first_call(self, ao)           # (with eri_ip1: the energy-only call below checks eri alone)
+            self.enqueue(ao, nroots, energy_only=True)
+            coeffs = self.coeffs                      # rows 0 .. nroots-1 as the solver wrote them
+        else:
+            # the reference's eig branch for every root: 2-norm eigenvectors, real part, |Im| < 1e-5, ascending
+            from .ab_initio_eigenvector_continuation import _eig_nonhermitian, _select
+            if self.t.layout == _lib.LAYOUT_SYM8:
+                raise _lib.EvcontHipError("hermitian=False needs the training data in the layout the caller holds, "
+                                          "not sym8")
+            if (self.t.row_offset, self.t.rows_local) != (0, self.t.rows_total):
+                raise _lib.EvcontHipError("hermitian=False needs the complete t-RDM on this device")
+            rows = self.phase_hamiltonian(ao)
+            self.phase_solve(ao, rows, 1)
+            self.synchronize()
+            vals, vecs = _eig_nonhermitian(self.hmat.cpu().numpy(), self.t.S.cpu().numpy(), self.t.layout)
+            e, c = _select(vals, vecs, nroots, False)
+            e = np.asarray(e, dtype=np.float64) + ao.enuc
+            c = np.ascontiguousarray(c, dtype=np.float64)
+            coeffs = torch.from_numpy(c).to(self.t.device)
+            self._primed = False      # the workspace no longer holds a converged Hermitian solve
+        d = self.t.device
+        grads = torch.zeros((npairs, max(self.natm, 1), 3), dtype=F64, device=d)
+        D = torch.zeros((npairs, n, n), dtype=F64, device=d) if want_d else None
+        G = torch.zeros((npairs, n, n, n, n), dtype=F64, device=d) if want_g else None
+        p = lambda t: (t.data_ptr() if t is not None else None)
+        out = _lib.OutputsRoots(grad=p(grads), d_pred=p(D), g_pred=p(G))
+        g = ao.cstruct()
+        rc = self.lib.evc_phase_gradient_roots(C.byref(self.t.cstruct), C.byref(g), coeffs.data_ptr(), nroots,
+                                               P.ctypes.data, npairs, C.byref(out),
+                                               _ip1_flag(self.t, ao) & _lib.FLAG_IP1_S2KL, self.ws.data_ptr(),
+                                               self.ws_bytes, self._sp())
+        check(rc, "evc_phase_gradient_roots")
+        self.synchronize()        # (coeffs of the eig branch live until here)
+        if hermitian:
+            e = self.energy[:nroots].cpu().numpy().copy()
+            self._raise_if_nan(e[0])
+            c = self.coeffs.reshape(-1)[: nroots * T].reshape(nroots, T).cpu().numpy().copy()
+        return e, c, grads, D, G
+
+    def energies_with_grads(self, ao: DeviceAO, nroots: int, pairs=None, return_density_matrices: bool = False,
+                            hermitian: bool = True):
+        """Lowest ``nroots`` total energies ``E (nroots,)``, their coefficient rows ``C (nroots,T)`` and one gradient
+        per slot ``grads (P,A,3)`` in ONE pass of the gradient chain (``evc_phase_gradient_roots``).  ``pairs``: (P,2)
+        root pairs k <= l < nroots, default ``[(k, k) for k < nroots]``; slot (k,k) is the total gradient of root k,
+        slot (k,l) the electronic coupling vector c_k^T dH/dR c_l.  ``return_density_matrices``: also ``D (P,N,N)``
+        and ``Gamma (P,N,N,N,N)``, the predicted (transition) RDMs of each slot.  ``hermitian=False``: the roots of
+        the reference's ``eig`` branch (host solve of the T x T pencil), every root as ``get_energy_with_grad``
+        takes root 0.  At (near-)degenerate roots the forces follow whichever eigenvectors the solver returned."""
+        if return_density_matrices and self.g_pred is None:
+            raise _lib.EvcontHipError("this evaluator was built with want_two_rdm=False")
+        e, c, grads, D, G = self._roots(ao, nroots, pairs, return_density_matrices, return_density_matrices,
+                                        hermitian)
+        gr = grads[:, : self.natm].cpu().numpy().copy()
+        if return_density_matrices:
+            return e, c, gr, D.cpu().numpy(), G.cpu().numpy()
+        return e, c, gr
 
     def phase_gradient(self, ao: DeviceAO, partial_rank: bool) -> None:
         g = ao.cstruct()

@@ -29,14 +29,15 @@
 extern "C" {
 #endif
 
-#define EVC_ABI_VERSION 9 /* 2: batched phases, evc_subspace_solve_batch, evc_integrals_oao_batch, EVC_FLAG_WARM_START;
+#define EVC_ABI_VERSION 10 /* 2: batched phases, evc_subspace_solve_batch, evc_integrals_oao_batch, EVC_FLAG_WARM_START;
                              3: EVC_LAYOUT_SYM8; 4: evc_profile_stage/_select, EVC_FLAG_IP1_S2KL, EVC_FLAG_ERI_S4;
                              5: evc_phase_set_coeffs; 6: evc_phase_loewdin_batch, EVC_FLAG_LOEWDIN_DONE;
                              7: training sets of up to 512 states (evc_subspace_solve[_batch] take a workspace,
                                 evc_subspace_solve_ws_bytes), `flags` argument of the phase A / B entry points;
                              8: evc_profile_kernel; the workspace of the compressed layout's pipeline holds its dense
                                 (pair, pair) intermediates at the pitch N(N+1)/2 rounded up to 16 doubles;
-                             9: evc_release_workspace (a workspace may own a side stream) */
+                             9: evc_release_workspace (a workspace may own a side stream);
+                             10: evc_phase_gradient_roots, evc_workspace_bytes_roots, evc_outputs_roots */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -244,7 +245,7 @@ int evc_phase_hamiltonian(const evc_trdm_set *t, const evc_geometry *g, int flag
 /* Phase B: eigensolve from the complete row vector h2rows_all[rows2_total].  flags: EVC_FLAG_WARM_START. */
 int evc_phase_solve(const evc_trdm_set *t, const evc_geometry *g, const double *h2rows_all,
                     const evc_outputs *out, int nroots, int flags, void *ws, size_t ws_bytes, void *stream);
-/* Phase C: predicted RDMs of root 0 + Loewdin-response nuclear gradient. */
+/* Phase C: predicted RDMs of root 0 + Loewdin-response nuclear gradient (other roots: evc_phase_gradient_roots). */
 int evc_phase_gradient(const evc_trdm_set *t, const evc_geometry *g, const evc_outputs *out,
                        int flags, void *ws, size_t ws_bytes, void *stream);
 /* Between B and C, optional: replace the row weights phase B left in the workspace by those of a coefficient vector
@@ -254,6 +255,36 @@ int evc_phase_gradient(const evc_trdm_set *t, const evc_geometry *g, const evc_o
  * the predicted RDMs and the gradient from ITS eigenvector.  `natm` as passed to evc_workspace_bytes. */
 int evc_phase_set_coeffs(const evc_trdm_set *t, const double *coeffs, int natm, void *ws, size_t ws_bytes,
                          void *stream);
+/* Phase C for several roots of ONE geometry in one pass: forces on excited-state surfaces and interstate couplings.
+ * The overlap matrix of the training states does not depend on the geometry, so for every eigenpair of H c = E S c
+ * (c^T S c = 1) dE_k/dR = c_k^T (dH/dR) c_k (ab_initio_gradients_loewdin.py:341-379 with c_k in place of c_0), and the
+ * interstate coupling vector h_kl = c_k^T (dH/dR) c_l is the same functional of the symmetric weighting
+ * W = (c_k c_l^T + c_l c_k^T) / 2 (the gradient is linear in the predicted RDMs).  The derivative coupling is
+ * h_kl / (E_l - E_k); dividing by the gap is the caller's business.
+ *
+ * Slot p of the call evaluates the pair (k, l) = (pairs[2p], pairs[2p+1]) of rows of coeffs (nvec, T), device: every
+ * stage of the gradient chain covers all slots in one launch, and the t-RDM is streamed once per 32 slots (the batched
+ * K8 of evc_energy_with_grad_batch) instead of once per root.
+ *   pairs   HOST array (npairs, 2), 0 <= k <= l < nvec, 1 <= npairs <= 4096; nvec <= T.
+ *   ws      at least evc_workspace_bytes_roots(t, natm, npairs) bytes; slot 0 holds phases A+B of THIS geometry: the
+ *           state an evc_energy_with_grad(..., nroots, EVC_FLAG_ENERGY_ONLY, ...) call (or evc_phase_hamiltonian +
+ *           evc_phase_solve) on the same workspace leaves.  Hermitian branch: coeffs = that call's outputs.coeffs;
+ *           hermitian=False: the caller's host-solved eigenvectors.  The call overwrites slots 1 .. npairs-1 (and the
+ *           row weights of slot 0).
+ *   flags   EVC_FLAG_IP1_S2KL only (as for evc_phase_gradient); EVC_FLAG_PARTIAL_RANK is rejected.
+ * WARNING: at (near-)degenerate roots the eigenvectors are not unique; the forces and couplings then follow whichever
+ * eigenvectors the solver returned (no degeneracy treatment). */
+typedef struct evc_outputs_roots {
+    double *grad;    /* (npairs,A,3): slot (k,k) = total gradient of root k (electronic + grad_nuc);
+                        slot (k,l), k != l = electronic coupling vector c_k^T dH/dR c_l (no nuclear term) */
+    double *d_pred;  /* (npairs,N,N) or NULL: predicted (transition) 1-RDM of the slot's weighting */
+    double *g_pred;  /* (npairs,N^4) or NULL: predicted 2-RDM, unpacked, as for evc_outputs.g_pred */
+} evc_outputs_roots;
+
+size_t evc_workspace_bytes_roots(const evc_trdm_set *t, int natm, int npairs);
+int evc_phase_gradient_roots(const evc_trdm_set *t, const evc_geometry *g, const double *coeffs, int nvec,
+                             const int32_t *pairs, int npairs, const evc_outputs_roots *out, int flags, void *ws,
+                             size_t ws_bytes, void *stream);
 /* A+B(+C) back to back on one device. */
 int evc_energy_with_grad(const evc_trdm_set *t, const evc_geometry *g, const evc_outputs *out,
                          int nroots, int flags, void *ws, size_t ws_bytes, void *stream);
