@@ -240,6 +240,16 @@ AMU2AU = 1822.888486209      # atomic mass unit in electron masses (CODATA 2018)
 KB_HARTREE = 3.166811563e-6   # Boltzmann constant in Hartree / K
 
 
+def _vv_drift(R, v, a, dt):
+    """Velocity-Verlet position update (any leading axes: one or many trajectories)."""
+    return R + dt * v + 0.5 * dt * dt * a
+
+
+def _vv_kick(v, a, g, m, dt):
+    """Velocity-Verlet velocity update from the start acceleration ``a`` and the end-point gradient ``g``."""
+    return v + 0.5 * dt * (a - np.asarray(g) / m)
+
+
 def nve_velocity_verlet(scanner, init_mol, dt=10.0, steps=10, veloc=None, trajectory_output=None,
                         energy_output=None, callback=None, thermostat=None):
     """Velocity-Verlet NVE propagation of an array-level molecule with ``scanner(mol) -> (E, grad)``.
@@ -273,10 +283,10 @@ def nve_velocity_verlet(scanner, init_mol, dt=10.0, steps=10, veloc=None, trajec
         if k == steps - 1:
             break
         a = -np.asarray(g) / m
-        R = R + dt * v + 0.5 * dt * dt * a
+        R = _vv_drift(R, v, a, dt)
         mol = init_mol.with_coords(R)
         e, g = scanner(mol)
-        v = v + 0.5 * dt * (a - np.asarray(g) / m)
+        v = _vv_kick(v, a, g, m, dt)
         if thermostat is not None:
             T_target, taut = thermostat
             T_now = float(np.sum(m * v * v)) / (3 * R.shape[0] * KB_HARTREE)
@@ -296,3 +306,39 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
     return _impl(EVCont_obj, init_mol, steps=steps, dt=dt, convergence_thresh=convergence_thresh,
                  prune_irrelevant_data=prune_irrelevant_data, trn_times=list(trn_times),
                  data_addition=data_addition, **kwargs)
+
+
+def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_veloc=None):
+    """Velocity-Verlet NVE of G trajectories on the continuation surface ``root`` (0 = ground state), advanced in lock
+    step: every step is ONE batched call for all G geometries (``get_multistate_energies_with_grads``, all trajectories'
+    roots 0 .. root in one pass).  ``mols``: the G initial geometries of one array-level molecule that can be rebuilt at
+    new coordinates (``with_coords``, as ``get_trajectory``'s native path takes); ``init_veloc``: (G,A,3) or None.
+    Conventions of ``nve_velocity_verlet`` (Bohr, atomic time units, frame 0 = the initial geometries); returns one
+    frame per step with ``coord``/``veloc`` (G,A,3), ``epot``/``ekin`` (G,) and ``time``.  Plain adiabatic dynamics:
+    no surface hopping, and at (near-)degenerate roots the forces follow whichever eigenvector the solver returned."""
+    from .ab_initio_gradients_loewdin import get_multistate_energies_with_grads
+    mols = list(mols)
+    root = int(root)
+    if root < 0:
+        raise ValueError(f"root={root} must be >= 0")
+    R = np.array([m_.atom_coords() for m_ in mols], dtype=np.float64)
+    m = (np.asarray(mols[0].atom_mass_list(), dtype=np.float64) * AMU2AU)[:, None]
+    v = np.zeros_like(R) if init_veloc is None else np.array(init_veloc, dtype=np.float64).reshape(R.shape)
+
+    def evaluate(ms):
+        E, grads = get_multistate_energies_with_grads(ms, one_rdm, two_rdm, overlap, root + 1)
+        return E[:, root], grads[:, root]
+
+    e, g = evaluate(mols)
+    frames = []
+    for k in range(steps):
+        frames.append({"coord": R.copy(), "veloc": v.copy(), "epot": e.copy(),
+                       "ekin": 0.5 * np.sum(m * v * v, axis=(1, 2)), "time": k * dt})
+        if k == steps - 1:
+            break
+        a = -g / m
+        R = _vv_drift(R, v, a, dt)
+        mols = [m_.with_coords(r) for m_, r in zip(mols, R)]
+        e, g = evaluate(mols)
+        v = _vv_kick(v, a, g, m, dt)
+    return frames

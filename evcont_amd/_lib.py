@@ -92,6 +92,10 @@ SIGNATURES = {
     "evc_phase_gradient_roots": (C.c_int, [C.POINTER(TrdmSet), C.POINTER(Geometry), C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_int, C.POINTER(OutputsRoots), C.c_int, C.c_void_p, C.c_size_t,
                                            C.c_void_p]),
+    "evc_workspace_bytes_roots_batch": (C.c_size_t, [C.POINTER(TrdmSet), C.c_int, C.c_int, C.c_int]),
+    "evc_phase_gradient_roots_batch": (C.c_int, [C.POINTER(TrdmSet), C.POINTER(GeometryBatch), C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_int, C.POINTER(OutputsRoots), C.c_int, C.c_void_p,
+                                                 C.c_size_t, C.c_void_p]),
     "evc_energy_with_grad": (C.c_int, [C.POINTER(TrdmSet), C.POINTER(Geometry), C.POINTER(Outputs), C.c_int,
                                        C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_workspace_bytes_batch": (C.c_size_t, [C.POINTER(TrdmSet), C.c_int, C.c_int]),

@@ -146,3 +146,77 @@ def get_multistate_energy_with_grad(mol, one_RDM, two_RDM, S, nroots=1, hermitia
     if return_density_matrices:
         out += (res[3][:nroots], res[4][:nroots])
     return out
+
+
+# Workspace bytes one call of get_multistate_energies_with_grads may hold (the list is split into chunks below this and
+# below 4096 slots of geometries x root pairs).
+BATCH_WORKSPACE_BUDGET = 8 << 30
+
+
+def _batched_evaluator(t, natm: int, count: int):
+    from . import cache
+    from .evaluator import BatchedEvaluator
+    key = ("batched_evaluator", id(t), int(natm), int(count))
+    ev = cache.get(key)
+    if ev is None or ev.t is not t:
+        ev = cache.put(key, BatchedEvaluator(t, natm, count))
+    return ev
+
+
+def get_multistate_energies_with_grads(mols, one_RDM, two_RDM, S, nroots=1, hermitian=True, return_couplings=False):
+    """``get_multistate_energy_with_grad`` for a list of geometries of ONE molecule, evaluated in batches (every
+    geometry of a batch and all its roots in one pass of the gradient chain, ``evc_phase_gradient_roots_batch``).
+
+    Returns stacked arrays ``E[G,nroots]`` and ``grad[G,nroots,A,3]``, with ``return_couplings`` also
+    ``h[G,nroots,nroots,A,3]`` (symmetric in k, l; the diagonal is the electronic gradient of root k), with the storage
+    of the training data and the coupling conventions of ``get_multistate_energy_with_grad``.  The list is split so
+    that a batch holds at most 4096 (geometry, root pair) slots and ``BATCH_WORKSPACE_BUDGET`` bytes of workspace."""
+    import ctypes as C
+    from . import _lib
+    from .ab_initio_eigenvector_continuation import _trdms, _trdms_auto
+    from .evaluator import DeviceAOBatch
+    mols = list(mols)
+    if not mols:
+        raise ValueError("no geometries")
+    nroots = int(nroots)
+    aos = [ao_arrays(m, need_grad=True) for m in mols]
+    natm = int(np.asarray(aos[0].aoslices).shape[0])
+    if any(int(np.asarray(a.aoslices).shape[0]) != natm or a.S.shape != aos[0].S.shape for a in aos):
+        raise ValueError("get_multistate_energies_with_grads: the geometries must be of one molecule")
+    if not hermitian:
+        t = _trdms(one_RDM, two_RDM, S, None)
+    else:
+        compress = resolve_compression("default", one_RDM, two_RDM, S, mols[0] if not is_array_mol(mols[0]) else aos[0],
+                                       hermitian=True, want_rdms=False)
+        t = _trdms_auto(one_RDM, two_RDM, S, compress) if get_trdm_compression() == "auto" else \
+            _trdms(one_RDM, two_RDM, S, compress)
+    pairs = [(k, k) for k in range(nroots)]
+    if return_couplings:
+        pairs += [(k, l) for k in range(nroots) for l in range(k + 1, nroots)]
+    npairs = len(pairs)
+    lib = _lib.load()
+    per_slot = lib.evc_workspace_bytes_roots_batch(C.byref(t.cstruct), natm, 1, 1)
+    if per_slot == 0:
+        raise _lib.EvcontHipError("evc_workspace_bytes_roots_batch: " + lib.evc_last_error().decode())
+    chunk = max(1, min(len(mols), 4096 // npairs, BATCH_WORKSPACE_BUDGET // (per_slot * npairs)))
+    if chunk * npairs > 4096:
+        raise ValueError(f"nroots={nroots}: {npairs} root pairs exceed the 4096 slots of one call")
+    E, grads = [], []
+    for c0 in range(0, len(mols), chunk):
+        part = aos[c0: c0 + chunk]
+        ev = _batched_evaluator(t, natm, len(part))
+        aob = DeviceAOBatch.from_arrays(part, t.device)
+        e, _, g = ev.multistate_energies_with_grads(aob, nroots, pairs, hermitian=hermitian)
+        E.append(e)
+        grads.append(g)
+    E, grads = np.concatenate(E), np.concatenate(grads)
+    out = (E, grads[:, :nroots].copy())
+    if return_couplings:
+        h = np.zeros((len(mols), nroots, nroots) + grads.shape[2:])
+        for p, (k, l) in enumerate(pairs):
+            h[:, k, l] = h[:, l, k] = grads[:, p]
+        gnuc = np.stack([np.asarray(a.gnuc, dtype=np.float64) for a in aos])
+        for k in range(nroots):
+            h[:, k, k] -= gnuc
+        out += (h,)
+    return out

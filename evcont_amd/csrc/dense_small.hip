@@ -2117,7 +2117,8 @@ int launch_subspace_solve(const SolveArgs &a_in, int count, hipStream_t st) {
 __global__ __launch_bounds__(256) void pair_weights_kernel(PairWeightsArgs a) {
     const int slot = (int)blockIdx.y, g = a.slot0 + slot;
     const int T = a.T;
-    const double *ck = a.c + (int64_t)a.k[slot] * T, *cl = a.c + (int64_t)a.l[slot] * T;
+    const double *c = a.c + geo_of(g, a.geo_period) * a.sc;   // (geo_period = 0: one coefficient block)
+    const double *ck = c + (int64_t)a.k[slot] * T, *cl = c + (int64_t)a.l[slot] * T;
     const bool diag = a.k[slot] == a.l[slot];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     // transposed copies: [row][slot] in the workspace of the first slot of the group of kMaxBatchG (csrc/kernels.hpp)
@@ -2173,9 +2174,19 @@ int launch_pair_weights(const double *c, int T, int layout, double *w1, double *
 int launch_pair_weights_slots(const double *c, int T, int layout, const int32_t *pairs, int npairs, double *w1,
                               double *w2, double *w1t, double *w2t, int64_t sw, int64_t w2_offset, int64_t w2_count,
                               hipStream_t st) {
+    return launch_pair_weights_geo(c, 0, 0, T, layout, pairs, npairs, w1, w2, w1t, w2t, sw, w2_offset, w2_count, st);
+}
+
+// Slots s = p * geo_period + g (geo_period > 0; npairs counts the root pairs, the launch covers npairs * geo_period
+// slots): pair p of coefficient block g.  geo_period = 0: slot p = pair p of the one block c.
+int launch_pair_weights_geo(const double *c, int64_t sc, int geo_period, int T, int layout, const int32_t *pairs,
+                            int npairs, double *w1, double *w2, double *w1t, double *w2t, int64_t sw, int64_t w2_offset,
+                            int64_t w2_count, hipStream_t st) {
     PairWeightsArgs a;
     memset(&a, 0, sizeof(a));
     a.c = c;
+    a.sc = sc;
+    a.geo_period = geo_period;
     a.T = T;
     a.pairs = layout_pairs(layout);
     a.w1 = w1;
@@ -2185,12 +2196,13 @@ int launch_pair_weights_slots(const double *c, int T, int layout, const int32_t 
     a.sw = sw;
     a.w2_offset = w2_offset;
     a.w2_count = w2_count;
-    for (int s0 = 0; s0 < npairs; s0 += kPairWeightsSlots) {
-        const int ns = npairs - s0 < kPairWeightsSlots ? npairs - s0 : kPairWeightsSlots;
+    const int per = geo_period > 0 ? geo_period : 1, nslots = npairs * per;
+    for (int s0 = 0; s0 < nslots; s0 += kPairWeightsSlots) {
+        const int ns = nslots - s0 < kPairWeightsSlots ? nslots - s0 : kPairWeightsSlots;
         a.slot0 = s0;
         for (int s = 0; s < ns; ++s) {
-            a.k[s] = (int16_t)pairs[2 * (s0 + s)];
-            a.l[s] = (int16_t)pairs[2 * (s0 + s) + 1];
+            a.k[s] = (int16_t)pairs[2 * ((s0 + s) / per)];
+            a.l[s] = (int16_t)pairs[2 * ((s0 + s) / per) + 1];
         }
         if (int rc = pair_weights_launch(a, ns, st)) return rc;
     }
@@ -2204,7 +2216,7 @@ __device__ __forceinline__ void grad_prep_body(GradPrepArgs a, int64_t g) {
     const int n = a.n;
     {
         a.X += g * a.sws;
-        a.hcore += g * a.sh;
+        a.hcore += geo_of(g, a.geo_period) * a.sh;
         a.D += g * a.sD;
         a.Pao += g * a.sws;
         a.Y1 += g * a.sws;
@@ -2354,7 +2366,7 @@ __global__ __launch_bounds__(kThreads) void grad_final_kernel(GradFinalArgs a) {
         a.y2 += g * a.sws;
         a.t2part += g * a.sws;
         a.term3 += g * a.sws;
-        a.ipovlp += g * a.sip;
+        a.ipovlp += geo_of(g, a.geo_period) * a.sip;
         if (a.gnuc) a.gnuc += g * a.sgn;
         a.grad += g * a.sgrad;
     }

@@ -28,21 +28,130 @@ int ip1_chunks(int n) {
     return c > n ? c : n;
 }
 
-template <int kIp1PerThread>
+// Pair blocks of the packed route for several root-pair slots of ONE geometry (evc_phase_gradient_roots_batch): the
+// launch has geo_period * slots slots s = p * geo_period + g; the int2e_ip1 rows of geometry g are read once per chunk
+// of kSlots of its slots instead of once per slot.  Work item w of geometry g (chunk q = w / npr, pair pidx = w % npr)
+// goes to the block (x, y = p * geo_period + g) with w = p * per + x, per = ceil(npr * chunks / slots), so that every row
+// y of the grid carries about the same number of pair blocks.  Each slot's sums run in the order of the one-slot form
+// below (the same fma chain per lane and the same reduction): its t2part is bitwise the one-slot result.
+template <int kSlots>
+__device__ __forceinline__ void ip1_pair_slots(const Ip1Args &a, int per) {
+    const int n = a.n, nchunk = a.nchunk, npr = n * (n + 1) / 2;
+    const int count = a.geo_period, P = a.slots, chunks = (P + kSlots - 1) / kSlots;
+    const int y = (int)blockIdx.y, g = y % count, p = y / count;
+    const int w = p * per + (int)blockIdx.x;
+    if (w >= npr * chunks) return;
+    const int q = w / npr, pidx = w - q * npr;
+    const int ns = P - q * kSlots < kSlots ? P - q * kSlots : kSlots;   // live slots of the chunk
+    const double *__restrict__ ip1 = a.ip1 + (int64_t)g * a.sip1;
+    const int hi = tri_row_small(pidx), lo = pidx - hi * (hi + 1) / 2;
+    const int64_t len = (int64_t)n * npr;
+    const double *__restrict__ qh = ip1 + ((int64_t)hi * n + lo) * npr;
+    const double *__restrict__ ql = ip1 + ((int64_t)lo * n + hi) * npr;
+    const bool both = hi != lo;
+    // row pidx of each slot's AO-basis 2-RDM (the tail of a short chunk repeats its first slot and is not written)
+    const double *gr[kSlots];
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j) {
+        const int64_t slot = (int64_t)(q * kSlots + (j < ns ? j : 0)) * count + g;
+        gr[j] = a.Gao + slot * a.sws + (int64_t)pidx * pair_ld(n);
+    }
+    double ah[kSlots][3], al[kSlots][3];
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) ah[j][x] = al[j][x] = 0.0;
+    typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
+    for (int v = 2 * threadIdx.x; v < npr; v += 512) {
+        const int vc = tri_row_small(v), vc1 = tri_row_small(v + 1);
+        const double w0 = v == vc * (vc + 3) / 2 ? 1.0 : 2.0, w1 = (v + 1) == vc1 * (vc1 + 3) / 2 ? 1.0 : 2.0;
+        if (v + 1 < npr) {
+            d2u qv[3], rv[3];
+#pragma unroll
+            for (int x = 0; x < 3; ++x) {
+                qv[x] = *reinterpret_cast<const d2u *>(qh + (int64_t)x * n * len + v);
+                rv[x] = both ? *reinterpret_cast<const d2u *>(ql + (int64_t)x * n * len + v) : qv[x];
+            }
+#pragma unroll
+            for (int j = 0; j < kSlots; ++j) {
+                const d2u gg = *reinterpret_cast<const d2u *>(gr[j] + v);
+                const double g0 = gg[0] * w0, g1 = gg[1] * w1;
+#pragma unroll
+                for (int x = 0; x < 3; ++x) {
+                    ah[j][x] = fma(qv[x][1], g1, fma(qv[x][0], g0, ah[j][x]));
+                    al[j][x] = fma(rv[x][1], g1, fma(rv[x][0], g0, al[j][x]));
+                }
+            }
+        } else {
+            double qv[3], rv[3];
+#pragma unroll
+            for (int x = 0; x < 3; ++x) {
+                qv[x] = qh[(int64_t)x * n * len + v];
+                rv[x] = both ? ql[(int64_t)x * n * len + v] : qv[x];
+            }
+#pragma unroll
+            for (int j = 0; j < kSlots; ++j) {
+                const double g0 = gr[j][v] * w0;
+#pragma unroll
+                for (int x = 0; x < 3; ++x) {
+                    ah[j][x] = fma(qv[x], g0, ah[j][x]);
+                    al[j][x] = fma(rv[x], g0, al[j][x]);
+                }
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ double pr6[kSlots][6][4];
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) {
+            const double sh = wave_sum(ah[j][x]), sl = wave_sum(al[j][x]);
+            if (lane == 0) {
+                pr6[j][x][wave] = sh;
+                pr6[j][3 + x][wave] = sl;
+            }
+        }
+    __syncthreads();
+    if ((int)threadIdx.x < 6 * ns) {
+        const int j = threadIdx.x / 6, r = threadIdx.x - 6 * j, x = r % 3, role = r / 3;
+        const double t = (pr6[j][r][0] + pr6[j][r][1]) + (pr6[j][r][2] + pr6[j][r][3]);
+        double *tp = a.t2part + ((int64_t)(q * kSlots + j) * count + g) * a.sws;
+        if (role == 0) tp[((int64_t)hi * 3 + x) * nchunk + lo] = t;
+        else if (both) tp[((int64_t)lo * 3 + x) * nchunk + hi] = t;
+    }
+    if (lo == 0 && nchunk > n) {   // slots behind the n partners (only if the chunk count exceeds n)
+        for (int j = 0; j < ns; ++j) {
+            double *tp = a.t2part + ((int64_t)(q * kSlots + j) * count + g) * a.sws;
+            for (int idx = threadIdx.x; idx < 3 * (nchunk - n); idx += 256)
+                tp[((int64_t)hi * 3 + idx / (nchunk - n)) * nchunk + n + idx % (nchunk - n)] = 0.0;
+        }
+    }
+}
+
+// pair blocks per grid row of the multi-slot form
+static __host__ __device__ inline int ip1_slots_per_row(int n, int slots, int kslots) {
+    const int npr = n * (n + 1) / 2, chunks = (slots + kslots - 1) / kslots;
+    return (npr * chunks + slots - 1) / slots;
+}
+
+template <int kIp1PerThread, int kSlots>
 __global__ __launch_bounds__(256) void ip1_dh_kernel(Ip1Args a) {
     __shared__ double scr[3][4];
     __shared__ double part[4][64];
     const int n = a.n, nchunk = a.nchunk;
     const int64_t n2 = (int64_t)n * n, n3 = n2 * n, n4 = n2 * n2;
-    const int64_t g = blockIdx.y;
+    const int64_t g = blockIdx.y, gi = geo_of(g, a.geo_period);   // slot, and the geometry whose inputs it reads
     const bool pair_blocks = a.presym && a.fold_cd && a.ip1_s2kl;
-    const int nb1 = pair_blocks ? n * (n + 1) / 2 : n * nchunk;
-    if (pair_blocks && (int)blockIdx.x < nb1) {
+    const int nb1 = kSlots > 1 ? ip1_slots_per_row(n, a.slots, kSlots) : pair_blocks ? n * (n + 1) / 2 : n * nchunk;
+    if (kSlots > 1 && (int)blockIdx.x < nb1) {
+        ip1_pair_slots<kSlots>(a, nb1);
+    } else if (kSlots == 1 && pair_blocks && (int)blockIdx.x < nb1) {
         // int2e_ip1 packed in (c,d), c >= d, against the dense (pair, pair) AO-basis 2-RDM G[tri(m,b)][v] (rows at the
         // pitch pair_ld(n); the weight 2 of c != d is applied here): one block per unordered pair {m, b} -- the row G[tri(hi,lo)][:]
         // is read once and contracted with ip1[x][hi][lo][:] (-> t2[x][hi], filed under partner lo) and, for
         // hi != lo, with ip1[x][lo][hi][:] (-> t2[x][lo], partner hi): 7 contiguous streams of n(n+1)/2 doubles
-        const double *__restrict__ ip1 = a.ip1 + g * a.sip1;
+        const double *__restrict__ ip1 = a.ip1 + gi * a.sip1;
         const double *__restrict__ G = a.Gao + g * a.sws;
         const int npr = n * (n + 1) / 2;
         const int pidx = blockIdx.x, hi = tri_row_small(pidx), lo = pidx - hi * (hi + 1) / 2;
@@ -103,8 +212,8 @@ __global__ __launch_bounds__(256) void ip1_dh_kernel(Ip1Args a) {
             for (int idx = threadIdx.x; idx < 3 * (nchunk - n); idx += 256)
                 tp[((int64_t)hi * 3 + idx / (nchunk - n)) * nchunk + n + idx % (nchunk - n)] = 0.0;
         }
-    } else if ((int)blockIdx.x < nb1) {
-        const double *__restrict__ ip1 = a.ip1 + g * a.sip1;
+    } else if (kSlots == 1 && (int)blockIdx.x < nb1) {
+        const double *__restrict__ ip1 = a.ip1 + gi * a.sip1;
         const double *__restrict__ G = a.Gao + g * a.sws;
         const int m = blockIdx.x / nchunk, ch = blockIdx.x % nchunk;
         double a0 = 0.0, a1 = 0.0, a2 = 0.0;
@@ -191,7 +300,7 @@ __global__ __launch_bounds__(256) void ip1_dh_kernel(Ip1Args a) {
         }
     } else if ((int)blockIdx.x < nb1 + a.natm * 3) {
         const int ax = blockIdx.x - nb1;  // A*3 + x
-        const double *p = a.dh + g * a.sdh + (int64_t)ax * n2;
+        const double *p = a.dh + gi * a.sdh + (int64_t)ax * n2;
         const double *Pao = a.Pao + g * a.sws;
         double s = 0.0;
         for (int64_t e = threadIdx.x; e < n2; e += 256) s = fma(p[e], Pao[e], s);
@@ -222,16 +331,45 @@ __global__ __launch_bounds__(256) void ip1_dh_kernel(Ip1Args a) {
     }
 }
 
+// Slots of one geometry that share one read of its int2e_ip1 rows: the largest of 8, 4, 2 not above the slot count
+// (more slots go in chunks of that many; 1: the one-slot form).  Only the packed pair-block route has the multi-slot form.
+static int ip1_kslots(const Ip1Args &a, int count) {
+    const bool pair_blocks = a.presym && a.fold_cd && a.ip1_s2kl;
+    if (!pair_blocks || a.geo_period <= 0 || a.slots < 2 || count != a.geo_period * a.slots) return 1;
+    int k = kIp1MaxSlots;
+    while (k > a.slots) k /= 2;
+    return k;
+}
+
+template <int kSlots>
+static void ip1_launch(const Ip1Args &a, int count, hipStream_t st) {
+    const bool pair_blocks = a.presym && a.fold_cd && a.ip1_s2kl;
+    const int nb1 = kSlots > 1 ? ip1_slots_per_row(a.n, a.slots, kSlots)
+                               : pair_blocks ? a.n * (a.n + 1) / 2 : a.n * a.nchunk;
+    const int blocks = nb1 + a.natm * 3 + (a.n * a.n + 63) / 64;
+    if constexpr (kSlots > 1) {   // (the pair-block form has no per-thread element count: one instance)
+        hipLaunchKernelGGL((ip1_dh_kernel<8, kSlots>), dim3(blocks, (unsigned)count), dim3(256), 0, st, a);
+    } else {
+        switch (ip1_per_thread()) {
+            case 16: hipLaunchKernelGGL((ip1_dh_kernel<16, 1>), dim3(blocks, (unsigned)count), dim3(256), 0, st, a); break;
+            case 8: hipLaunchKernelGGL((ip1_dh_kernel<8, 1>), dim3(blocks, (unsigned)count), dim3(256), 0, st, a); break;
+            default: hipLaunchKernelGGL((ip1_dh_kernel<4, 1>), dim3(blocks, (unsigned)count), dim3(256), 0, st, a); break;
+        }
+    }
+}
+
 int launch_ip1_dh(const Ip1Args &a, int count, hipStream_t st) {
     const bool pair_blocks = a.presym && a.fold_cd && a.ip1_s2kl;
-    const int blocks = (pair_blocks ? a.n * (a.n + 1) / 2 : a.n * a.nchunk) + a.natm * 3 + (a.n * a.n + 63) / 64;
-    switch (ip1_per_thread()) {
-        case 16: hipLaunchKernelGGL(ip1_dh_kernel<16>, dim3(blocks, (unsigned)count), dim3(256), 0, st, a); break;
-        case 8: hipLaunchKernelGGL(ip1_dh_kernel<8>, dim3(blocks, (unsigned)count), dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL(ip1_dh_kernel<4>, dim3(blocks, (unsigned)count), dim3(256), 0, st, a); break;
+    const int ks = ip1_kslots(a, count);
+    switch (ks) {
+        case 8: ip1_launch<8>(a, count, st); break;
+        case 4: ip1_launch<4>(a, count, st); break;
+        case 2: ip1_launch<2>(a, count, st); break;
+        default: ip1_launch<1>(a, count, st); break;
     }
     EVC_LAUNCH_CHECK("ip1_dh");
-    note_kernel(EVC_PROF_IP1, "ip1_dh_kernel<%d> %s", ip1_per_thread(), pair_blocks ? "pairs" : "chunks");
+    if (ks > 1) note_kernel(EVC_PROF_IP1, "ip1_dh_kernel<8> pairs slots=%d", ks);
+    else note_kernel(EVC_PROF_IP1, "ip1_dh_kernel<%d> %s", ip1_per_thread(), pair_blocks ? "pairs" : "chunks");
     return 0;
 }
 

@@ -142,11 +142,15 @@ int launch_y2(const double *GsT, const double *K3, int n, double *partial, int64
 // ip1 contraction with on-the-fly AO symmetrisation (gradients_loewdin.py:234-252), dhcore:P_ao dots
 // and the fixed-order sum of the Y2 slabs (three block families of one launch)
 int ip1_chunks(int n);
+// Geometry of slot g of a gradient launch: geo_period = 0 -> g (one slot per geometry); otherwise g % geo_period (the
+// root-pair-major slots s = p * count + g of evc_phase_gradient_roots_batch, geo_period = count).  Applies to the
+// caller's per-geometry inputs only (hcore, int2e_ip1, dhcore, ipovlp); the workspace is per slot.
+__host__ __device__ inline int64_t geo_of(int64_t g, int geo_period) { return geo_period > 0 ? g % geo_period : g; }
 struct Ip1Args {
-    const double *ip1;     // (3,n^4)      + g*sip1
+    const double *ip1;     // (3,n^4)      + geo_of(g)*sip1
     const double *Gao;     // (n^4)        + g*sws
     double *t2part;        // (n,3,nchunk) + g*sws
-    const double *dh;      // (A,3,n,n)    + g*sdh      (may be NULL with natm = 0)
+    const double *dh;      // (A,3,n,n)    + geo_of(g)*sdh      (may be NULL with natm = 0)
     const double *Pao;     // (n,n)        + g*sws
     double *term3;         // (A*3)        + g*sws
     const double *y2part;  // (nslab,n,n)  + g*sws
@@ -160,7 +164,12 @@ struct Ip1Args {
                            // (EVC_FLAG_IP1_S2KL); sip1 is the packed size and Gao the dense (pair, pair) matrix
                            // Gao[tri(m,b)][tri(c,d)] at the pitch pair_ld(n), WITHOUT the multiplicity of (c,d): the
                            // dot weighs it (2 for c != d)
+    int geo_period;        // geo_of (0: slot g reads geometry g)
+    int slots;             // (pair-block route, geo_period > 0) root-pair slots per geometry: the launch has
+                           // geo_period * slots slots, and one block reads the int2e_ip1 rows of a geometry once for up
+                           // to kIp1MaxSlots of its slots (launch_ip1_dh); 0 or 1: one slot per block
 };
+constexpr int kIp1MaxSlots = 8;
 int launch_ip1_dh(const Ip1Args &a, int count, hipStream_t st);
 
 // ---- dense_small.hip ---------------------------------------------------------------
@@ -240,23 +249,28 @@ int launch_pair_weights_slots(const double *c, int T, int layout, const int32_t 
                               double *w2, double *w1t, double *w2t, int64_t sw, int64_t w2_offset, int64_t w2_count,
                               hipStream_t st);
 constexpr int kPairWeightsSlots = 256;   // slots per launch (their (k, l) travel in the kernel arguments)
+// evc_phase_gradient_roots_batch: slot s takes its rows from coeffs + geo_of(s, geo_period) * sc ((count, T, T) blocks).
+int launch_pair_weights_geo(const double *c, int64_t sc, int geo_period, int T, int layout, const int32_t *pairs,
+                            int npairs, double *w1, double *w2, double *w1t, double *w2t, int64_t sw, int64_t w2_offset,
+                            int64_t w2_count, hipStream_t st);
 struct PairWeightsArgs {
-    const double *c;          // (nvec, T) rows
+    const double *c;          // (nvec, T) rows  + geo_of(g, geo_period)*sc
     double *w1, *w2;          // + g*sw, g = slot0 + blockIdx.y
     double *w1t, *w2t;        // (rows, kMaxBatchG) + (g - g % kMaxBatchG)*sw, or NULL
-    int64_t sw, w2_offset, w2_count;
-    int T, pairs, slot0;
+    int64_t sw, w2_offset, w2_count, sc;
+    int T, pairs, slot0, geo_period;
     int16_t k[kPairWeightsSlots], l[kPairWeightsSlots];
 };
 struct GradPrepArgs {
     int n;
     const double *X;      // + g*sws
-    const double *hcore;  // + g*sh
+    const double *hcore;  // + geo_of(g)*sh
     const double *D;      // predicted 1-RDM (n,n)  + g*sD
     double *Pao;          // X D X^T                + g*sws
     double *Y1;           // hcore X (D + D^T)      + g*sws
     int64_t sws, sh, sD;
     double scale1;        // 1 on the rank that owns the one-body part, else 0
+    int geo_period;       // geo_of
 };
 int launch_grad_prep(const GradPrepArgs &a, int count, hipStream_t st);
 // grad_prep and the unpack of the packed predicted 2-RDM into the dense (pair, pair) SB in ONE launch (dense_small.hip)
@@ -267,7 +281,7 @@ struct GradFinalArgs {
     const double *U, *s;          // eigen-decomposition of S_AO   + g*sws
     const double *Y1;             // (n,n) [a][i]                  + g*sws
     const double *y2;             // (n,n) [i][a]                  + g*sws
-    const double *ipovlp;         // (3,n,n)                       + g*sip
+    const double *ipovlp;         // (3,n,n)                       + geo_of(g)*sip
     const int64_t *aoslices;      // (A,2) shared
     const double *t2part;         // (n,3,nchunk)                  + g*sws
     int nchunk;
@@ -276,6 +290,7 @@ struct GradFinalArgs {
     double scale1;                // 1: include term3 + gnuc
     double *grad;                 // (A,3)                         + g*sgrad
     int64_t sws, sip, sgn, sgrad;
+    int geo_period;               // geo_of (gnuc is per slot)
 };
 int launch_grad_final(const GradFinalArgs &a, int count, hipStream_t st);
 

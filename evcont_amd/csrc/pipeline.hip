@@ -83,6 +83,7 @@ struct Geo {
     double enuc;             // used when enuc_dev == NULL
     const double *enuc_dev;  // [count]
     int eri_s4;              // eri is the dense (pair, pair) matrix (EVC_FLAG_ERI_S4); set from the call's flags
+    int geo_period;          // gradient chain: slot g reads geometry geo_of(g, geo_period) (kernels.hpp; 0: g)
 };
 struct Out {
     double *energy, *coeffs, *grad, *d_pred, *g_pred, *hmat;
@@ -655,6 +656,7 @@ static int gradient_from_rdms(int n, const Geo &g, const double *D, int64_t sD, 
     p.sh = g.sh;
     p.sD = sD;
     p.scale1 = scale1;
+    p.geo_period = g.geo_period;
     // (symmetric pipeline without a request for the unpacked 2-RDM: grad_prep rides in the unpack launch below)
     // (n <= 32 only: every block of the shared launch reserves grad_prep's LDS -- 52 KB there, 108 KB at n = 58, where
     //  the unpack blocks would run one per CU)
@@ -667,6 +669,8 @@ static int gradient_from_rdms(int n, const Geo &g, const double *D, int64_t sD, 
     int y2_slabs_used = y2_slabs(n);   // (the fused kernel: per chunk of geometries, set where it is launched)
     auto ip1_stage = [&](const double *gao_, int c0, int cc) -> int {
         const int64_t o = (int64_t)c0 * sw;
+        // (slots that map to geometries: the launch must start at geometry 0 and cover whole blocks of slots)
+        EVC_REQUIRE(g.geo_period == 0 || (c0 == 0 && cc == cnt), "gradient: geometry-mapped slots in chunks");
         Ip1Args ia;
         ia.ip1 = g.eri_ip1 + (int64_t)c0 * g.sip1;
         ia.Gao = gao_ + o;
@@ -686,6 +690,8 @@ static int gradient_from_rdms(int n, const Geo &g, const double *D, int64_t sD, 
         ia.natm = g.natm;
         ia.nslab = y2_slabs_used;
         ia.nchunk = ip1_chunks(n);
+        ia.geo_period = g.geo_period;
+        ia.slots = g.geo_period > 0 ? cnt / g.geo_period : 1;
         return launch_ip1_dh(ia, cc, st);
     };
     bool ip1_done = false;
@@ -815,6 +821,7 @@ static int gradient_from_rdms(int n, const Geo &g, const double *D, int64_t sD, 
     f.sip = g.sip;
     f.sgn = g.sgn;
     f.sgrad = sgrad;
+    f.geo_period = g.geo_period;
     return launch_grad_final(f, cnt, st);
 }
 
@@ -1103,21 +1110,26 @@ extern "C" size_t evc_workspace_bytes_roots(const evc_trdm_set *t, int natm, int
     return w.bytes * (size_t)npairs + roots_gnuc_bytes(natm, npairs);
 }
 
-// dst[s * pitch] = src[0] for s = 1 .. count-1 (bytes at a pitch of `pitch` bytes): log2(count) copies, each
-// doubling the filled prefix.
-static int fan_out(char *base, size_t bytes, size_t pitch, int count, hipStream_t st) {
-    if (pitch > (size_t)INT32_MAX) {   // (beyond the pitch a 2-D copy takes: one copy per slot)
-        for (int s = 1; s < count; ++s)
-            EVC_HIP(hipMemcpyAsync(base + (size_t)s * pitch, base, bytes, hipMemcpyDeviceToDevice, st));
+// Block b of `rows` rows (row r at base + (b * rows + r) * pitch, `bytes` bytes each) := block 0, for b = 1 .. blocks-1:
+// log2(blocks) 2-D copies, each doubling the filled prefix.
+static int fan_out_blocks(char *base, size_t bytes, size_t pitch, int rows, int blocks, hipStream_t st) {
+    if (pitch > (size_t)INT32_MAX) {   // (beyond the pitch a 2-D copy takes: one copy per row)
+        for (int s = rows; s < rows * blocks; ++s)
+            EVC_HIP(hipMemcpyAsync(base + (size_t)s * pitch, base + (size_t)(s % rows) * pitch, bytes,
+                                   hipMemcpyDeviceToDevice, st));
         return 0;
     }
-    for (int have = 1; have < count;) {
-        const int m = count - have < have ? count - have : have;
-        EVC_HIP(hipMemcpy2DAsync(base + (size_t)have * pitch, pitch, base, pitch, bytes, (size_t)m,
+    for (int have = 1; have < blocks;) {
+        const int m = blocks - have < have ? blocks - have : have;
+        EVC_HIP(hipMemcpy2DAsync(base + (size_t)have * rows * pitch, pitch, base, pitch, bytes, (size_t)m * rows,
                                  hipMemcpyDeviceToDevice, st));
         have += m;
     }
     return 0;
+}
+// dst[s * pitch] = src[0] for s = 1 .. count-1
+static int fan_out(char *base, size_t bytes, size_t pitch, int count, hipStream_t st) {
+    return fan_out_blocks(base, bytes, pitch, 1, count, st);
 }
 
 extern "C" int evc_phase_gradient_roots(const evc_trdm_set *t, const evc_geometry *g, const double *coeffs, int nvec,
@@ -1199,6 +1211,123 @@ extern "C" int evc_phase_gradient_roots(const evc_trdm_set *t, const evc_geometr
     o.g_pred = out->g_pred;
     o.sG = o.sd * o.sd;
     return phase_gradient(t, gg, o, flags, w, st);
+}
+
+// ---- several roots of SEVERAL geometries: evc_phase_gradient_roots_batch -------------------------------------------
+// Root-pair-major slots s = p * count + g (pair p of geometry g): block p = 0 is the workspace the batched energy-only
+// call left (geometries 0 .. count-1), the blocks p >= 1 are filled from it as evc_phase_gradient_roots fills its
+// slots from slot 0.  The gradient chain then runs for npairs * count slots with geo_period = count: slot s reads the
+// caller's inputs of geometry s % count (kernels.hpp geo_of).  Behind the slots: the per-slot nuclear term.
+extern "C" size_t evc_workspace_bytes_roots_batch(const evc_trdm_set *t, int natm, int count, int npairs) {
+    if (check_set(t)) return 0;
+    if (count < 1 || npairs < 1 || (int64_t)count * npairs > kMaxRootPairs) {
+        set_error("evc_workspace_bytes_roots_batch: count=%d, npairs=%d (need count >= 1, npairs >= 1, count * npairs <= %d)",
+                  count, npairs, kMaxRootPairs);
+        return 0;
+    }
+    Ws w;
+    carve(t, natm, nullptr, w);
+    return w.bytes * (size_t)count * npairs + roots_gnuc_bytes(natm, count * npairs);
+}
+
+extern "C" int evc_phase_gradient_roots_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, const double *coeffs,
+                                              int nvec, const int32_t *pairs, int npairs, const evc_outputs_roots *out,
+                                              int flags, void *ws, size_t ws_bytes, void *stream) {
+    const char *who = "evc_phase_gradient_roots_batch";
+    clear_kernels(kStagesGradient);
+    if (check_set(t)) return -1;
+    EVC_REQUIRE(gb, "%s: null batch descriptor", who);
+    EVC_REQUIRE(gb->count >= 1 && gb->count <= 4096, "%s: batch count=%d out of range", who, gb->count);
+    EVC_REQUIRE(gb->S && gb->hcore && gb->eri && gb->enuc, "%s: batch geometry: S/hcore/eri/enuc must be given", who);
+    EVC_REQUIRE(aligned16(gb->eri) && (!gb->eri_ip1 || aligned16(gb->eri_ip1)),
+                "%s: batch geometry: eri / eri_ip1 must be 16-byte aligned", who);
+    EVC_REQUIRE(gb->natm >= 1 && gb->ipovlp && gb->dhcore && gb->eri_ip1 && gb->aoslices && gb->gnuc,
+                "%s: batch geometry: ipovlp/dhcore/eri_ip1/gnuc/aoslices are required for the gradient", who);
+    EVC_REQUIRE(coeffs && pairs, "%s: coeffs / pairs is NULL", who);
+    EVC_REQUIRE(out && out->grad, "%s: outputs.grad is required", who);
+    EVC_REQUIRE(!(flags & EVC_FLAG_PARTIAL_RANK), "%s: EVC_FLAG_PARTIAL_RANK is not supported", who);
+    EVC_REQUIRE(!(flags & ~EVC_FLAG_IP1_S2KL), "%s: flags=%d (only EVC_FLAG_IP1_S2KL is accepted)", who, flags);
+    EVC_REQUIRE(npairs >= 1 && npairs <= kMaxRootPairs, "%s: npairs=%d out of range 1..%d", who, npairs, kMaxRootPairs);
+    const int count = gb->count;
+    EVC_REQUIRE((int64_t)count * npairs <= kMaxRootPairs, "%s: count * npairs = %d * %d exceeds %d slots", who, count,
+                npairs, kMaxRootPairs);
+    EVC_REQUIRE(nvec >= 1 && nvec <= t->ntrain, "%s: nvec=%d out of range 1..%d (T)", who, nvec, t->ntrain);
+    for (int p = 0; p < npairs; ++p) {
+        const int k = pairs[2 * p], l = pairs[2 * p + 1];
+        EVC_REQUIRE(0 <= k && k <= l && l < nvec, "%s: pair %d = (%d, %d) outside 0 <= k <= l < nvec=%d", who, p, k, l,
+                    nvec);
+    }
+    EVC_REQUIRE(ws && aligned16(ws), "%s: workspace NULL or misaligned", who);
+    const int nslots = count * npairs;
+    Ws w;
+    carve(t, gb->natm, static_cast<char *>(ws), w);
+    const size_t need = w.bytes * (size_t)nslots + roots_gnuc_bytes(gb->natm, nslots);
+    EVC_REQUIRE(ws_bytes >= need, "%s: workspace too small: %zu < %zu", who, ws_bytes, need);
+    replan(t, w, nslots);
+    hipStream_t st = as_stream(stream);
+    const int n = t->n;
+    const int64_t sw = w.stride, A3 = (int64_t)gb->natm * 3, T = t->ntrain;
+    int rc;
+    // (1) row weights of every slot: pair p of coefficient block g (+ the transposed group copies of the batched K8)
+    if ((rc = launch_pair_weights_geo(coeffs, T * T, count, (int)T, t->layout, pairs, npairs, w.w1, w.w2,
+                                      nslots > 1 ? w.w1t : nullptr, nslots > 1 ? w.w2t : nullptr, sw, t->row_offset,
+                                      t->rows2, st)))
+        return rc;
+    // (2) block 0 (the count geometries' state of phases A+B) into the blocks p >= 1; U and s may still come from the
+    //     side stream (phase A of an energy-only call)
+    if ((rc = side_join(w.base, st))) return rc;
+    char *b0 = static_cast<char *>(ws);
+    const size_t pitch = w.bytes;
+    if (npairs > 1) {
+        // the same regions as evc_phase_gradient_roots: X, U, s, lflag, h1 and K3
+        const bool pairs_route = use_pair_transform(n) || use_pair64(t->layout, n, (flags & EVC_FLAG_IP1_S2KL) != 0);
+        const size_t k3 = (pairs_route && use_fused_y2(is_sym8(t->layout), n)) ? (size_t)pair_ld(n) * pair_ld(n)
+                                                                                 : (size_t)n * n * n * n;
+        if ((rc = fan_out_blocks(b0, (size_t)((char *)(w.h1 + (size_t)n * n) - (char *)w.X), pitch, count, npairs, st)))
+            return rc;
+        if ((rc = fan_out_blocks((char *)w.K3, sizeof(double) * k3, pitch, count, npairs, st))) return rc;
+    }
+    // (3) nuclear term: the geometry's grad_nuc on the diagonal pairs, zero on the couplings
+    double *gnuc = reinterpret_cast<double *>(b0 + w.bytes * (size_t)nslots);
+    const size_t blk = sizeof(double) * A3 * count;   // one pair's (count, A, 3)
+    bool any_coupling = false;
+    for (int p = 0; p < npairs; ++p) any_coupling = any_coupling || pairs[2 * p] != pairs[2 * p + 1];
+    if (any_coupling) EVC_HIP(hipMemsetAsync(gnuc, 0, blk * npairs, st));
+    for (int p = 0; p < npairs; ++p)
+        if (pairs[2 * p] == pairs[2 * p + 1])
+            EVC_HIP(hipMemcpyAsync(reinterpret_cast<char *>(gnuc) + blk * p, gb->gnuc, blk, hipMemcpyDeviceToDevice, st));
+    // (4) the gradient chain for npairs * count slots; slot s reads geometry s % count
+    Geo g;
+    memset(&g, 0, sizeof(g));
+    const int64_t n2 = (int64_t)n * n, n4 = n2 * n2;
+    g.natm = gb->natm;
+    g.count = nslots;
+    g.geo_period = count;
+    g.S = gb->S;
+    g.sS = n2;
+    g.hcore = gb->hcore;
+    g.sh = n2;
+    g.eri = gb->eri;
+    g.seri = n4;
+    g.ipovlp = gb->ipovlp;
+    g.sip = 3 * n2;
+    g.dhcore = gb->dhcore;
+    g.sdh = A3 * n2;
+    g.eri_ip1 = gb->eri_ip1;
+    g.sip1 = 3 * n4;   // (phase_gradient: the packed size with EVC_FLAG_IP1_S2KL)
+    g.gnuc = gnuc;
+    g.sgn = A3;
+    g.aoslices = gb->aoslices;
+    g.enuc_dev = gb->enuc;
+    Out o;
+    memset(&o, 0, sizeof(o));
+    o.grad = out->grad;
+    o.sg = A3;
+    o.d_pred = out->d_pred;
+    o.sd = n2;
+    o.g_pred = out->g_pred;
+    o.sG = n4;
+    return phase_gradient(t, g, o, flags, w, st);
 }
 
 // Shared argument checking / descriptor set-up of the batch entry points.

@@ -552,7 +552,8 @@ class BatchedEvaluator:
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=d)
         self.ws_bytes = nbytes
         # (the library may attach a side stream to the workspace, include/evcont_hip.h evc_release_workspace)
-        weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr()).atexit = False
+        self._ws_release = weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr())
+        self._ws_release.atexit = False
         G = self.count
         # energies and gradients share one buffer: a caller that wants both on the host fetches them with ONE copy
         na = max(self.natm, 1)
@@ -641,6 +642,101 @@ class BatchedEvaluator:
                                             self.ws.data_ptr(), self.ws_bytes, self._sp())
         check(rc, "evc_phase_solve_batch")
         self._primed = True
+
+    # -- several roots of every geometry (evc_phase_gradient_roots_batch) -----------------------------------------
+    def _grow_workspace(self, nbytes: int) -> None:
+        """Enlarge the workspace to ``nbytes`` (never shrinks).  Geometries 0 .. count-1 keep their place and contents
+        (``ContinuationEvaluator._grow_workspace``); the rest is zero-filled."""
+        if nbytes <= self.ws_bytes:
+            return
+        st = self.stream if self.stream is not None else torch.cuda.current_stream(self.t.device)
+        self._ws_release()          # waits for a side-stream launch into the old workspace, drops its events
+        ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.t.device)
+        with torch.cuda.stream(st):
+            ws[: self.ws_bytes].copy_(self.ws)
+        st.synchronize()
+        self.ws, self.ws_bytes = ws, nbytes
+        self._ws_release = weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr())
+        self._ws_release.atexit = False
+
+    def _host_coeffs(self, aob: DeviceAOBatch, nroots: int):
+        """hermitian=False: H(R) of every geometry assembled on the device, the T x T pencils solved on the host as
+        ``ContinuationEvaluator._roots`` does; returns host E (G, nroots), C (G, nroots, T) and the device (G, T, T)
+        coefficient blocks the gradient call reads."""
+        from .ab_initio_eigenvector_continuation import _eig_nonhermitian, _select
+        if self.t.layout == _lib.LAYOUT_SYM8:
+            raise _lib.EvcontHipError("hermitian=False needs the training data in the layout the caller holds, not sym8")
+        if (self.t.row_offset, self.t.rows_local) != (0, self.t.rows_total):
+            raise _lib.EvcontHipError("hermitian=False needs the complete t-RDM on this device")
+        G, T, d = self.count, self.t.T, self.t.device
+        if self.hmat is None:
+            self.hmat = torch.zeros((G, T, T), dtype=F64, device=d)
+            self.out.hmat = self.hmat.data_ptr()
+        rows = torch.zeros((G, max(self.t.rows_total, 1)), dtype=F64, device=d)
+        self.phase_hamiltonian(aob, rows)
+        self.phase_solve(aob, rows, 1)
+        self.synchronize()
+        H, S = self.hmat.cpu().numpy(), self.t.S.cpu().numpy()
+        enuc = aob.enuc.cpu().numpy()
+        E = np.zeros((G, nroots))
+        Cs = np.zeros((G, nroots, T))
+        for g in range(G):
+            vals, vecs = _eig_nonhermitian(H[g], S, self.t.layout)
+            e, c = _select(vals, vecs, nroots, False)
+            E[g], Cs[g] = np.asarray(e, dtype=np.float64) + enuc[g], c
+        blocks = np.zeros((G, T, T))
+        blocks[:, :nroots] = Cs
+        self._primed = False      # the workspace no longer holds a converged Hermitian solve
+        return E, Cs, torch.from_numpy(blocks).to(d)
+
+    def multistate_energies_with_grads(self, aob: DeviceAOBatch, nroots: int, pairs=None,
+                                       return_density_matrices: bool = False, hermitian: bool = True):
+        """``ContinuationEvaluator.energies_with_grads`` for every geometry of the batch in one pass of the gradient
+        chain (``evc_energy_with_grad_batch`` energy-only + ``evc_phase_gradient_roots_batch``): ``E (G,nroots)``,
+        ``C (G,nroots,T)`` and ``grads (G,P,A,3)`` -- slot (k,k) the total gradient of root k, slot (k,l) the electronic
+        coupling vector c_k^T dH/dR c_l, ``pairs`` the same (P,2) list for every geometry (default: the diagonal) --,
+        with ``return_density_matrices`` also ``D (G,P,N,N)`` and ``Gamma (G,P,N^4)``.  ``hermitian=False``: the host
+        eig selection per geometry (not on sym8).  G * P <= 4096."""
+        assert aob.count == self.count, "batch size is fixed at construction"
+        G, T, n = self.count, self.t.T, self.t.n
+        nroots = int(nroots)
+        if not 1 <= nroots <= T:
+            raise ValueError(f"nroots={nroots} out of range 1..{T}")
+        if pairs is None:
+            pairs = [(k, k) for k in range(nroots)]
+        P = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        npairs = P.shape[0]
+        nbytes = self.lib.evc_workspace_bytes_roots_batch(C.byref(self.t.cstruct), self.natm, G, npairs)
+        if nbytes == 0:
+            raise _lib.EvcontHipError("evc_workspace_bytes_roots_batch: " + self.lib.evc_last_error().decode())
+        self._grow_workspace(nbytes)
+        if hermitian:
+            self.enqueue(aob, nroots, energy_only=True)     # (checks the integrals' symmetry on the first call)
+            coeffs = self.coeffs
+        else:
+            E, Cs, coeffs = self._host_coeffs(aob, nroots)
+        d, want = self.t.device, bool(return_density_matrices)
+        grads = torch.zeros((npairs, G, max(self.natm, 1), 3), dtype=F64, device=d)
+        D = torch.zeros((npairs, G, n, n), dtype=F64, device=d) if want else None
+        Gm = torch.zeros((npairs, G, n ** 4), dtype=F64, device=d) if want else None
+        p = lambda t: (t.data_ptr() if t is not None else None)
+        out = _lib.OutputsRoots(grad=p(grads), d_pred=p(D), g_pred=p(Gm))
+        g = aob.cstruct()
+        rc = self.lib.evc_phase_gradient_roots_batch(C.byref(self.t.cstruct), C.byref(g), coeffs.data_ptr(), nroots,
+                                                     P.ctypes.data, npairs, C.byref(out),
+                                                     _ip1_flag(self.t, aob) & _lib.FLAG_IP1_S2KL, self.ws.data_ptr(),
+                                                     self.ws_bytes, self._sp())
+        check(rc, "evc_phase_gradient_roots_batch")
+        self.synchronize()        # (coeffs of the eig branch live until here)
+        if hermitian:
+            E = self.energy[:, :nroots].cpu().numpy().copy()
+            if not np.all(np.isfinite(E[:, 0])):
+                raise np.linalg.LinAlgError("generalised eigenproblem failed for at least one geometry of the batch")
+            Cs = self.coeffs[:, :nroots].cpu().numpy().copy()
+        res = (E, Cs, grads[:, :, : self.natm].transpose(0, 1).cpu().numpy().copy())
+        if want:
+            res += (D.transpose(0, 1).cpu().numpy().copy(), Gm.transpose(0, 1).cpu().numpy().copy())
+        return res
 
     def phase_gradient(self, aob: DeviceAOBatch, partial_rank: bool) -> None:
         g = aob.cstruct()

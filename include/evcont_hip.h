@@ -37,7 +37,9 @@ extern "C" {
                              8: evc_profile_kernel; the workspace of the compressed layout's pipeline holds its dense
                                 (pair, pair) intermediates at the pitch N(N+1)/2 rounded up to 16 doubles;
                              9: evc_release_workspace (a workspace may own a side stream);
-                             10: evc_phase_gradient_roots, evc_workspace_bytes_roots, evc_outputs_roots */
+                             10: evc_phase_gradient_roots, evc_workspace_bytes_roots, evc_outputs_roots;
+                                 later additions under 10 (no existing signature or behaviour changed):
+                                 evc_phase_gradient_roots_batch, evc_workspace_bytes_roots_batch */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -334,6 +336,27 @@ int evc_release_workspace(void *ws);
 int evc_energy_with_grad_batch(const evc_trdm_set *t, const evc_geometry_batch *gb,
                                const evc_outputs_batch *ob, int nroots, int flags, void *ws,
                                size_t ws_bytes, void *stream);
+
+/* Phase C of evc_phase_gradient_roots for EVERY geometry of a batch in one pass: the same host list of root pairs
+ * (k, l) for each of the gb->count geometries.  Slot (k,k) = total gradient of root k, slot (k,l), k != l = electronic
+ * coupling vector c_k^T dH/dR c_l of that geometry (semantics, degeneracy warning: evc_phase_gradient_roots).
+ *   coeffs  DEVICE (count,T,T), as evc_energy_with_grad_batch writes outputs.coeffs: rows 0 .. nvec-1 of block g are
+ *           the coefficient vectors of geometry g (hermitian=False: the caller's host-solved eigenvectors, same layout).
+ *   pairs   HOST array (npairs, 2), 0 <= k <= l < nvec; 1 <= count * npairs <= 4096; nvec <= T.
+ *   ws      at least evc_workspace_bytes_roots_batch(t, natm, count, npairs) bytes; geometries 0 .. count-1 of it hold
+ *           phases A+B of THESE geometries: the state evc_energy_with_grad_batch(..., nroots >= nvec,
+ *           EVC_FLAG_ENERGY_ONLY, ...) (or evc_phase_hamiltonian_batch + evc_phase_solve_batch) on the same workspace
+ *           leaves.  The call overwrites the slots behind them (and the row weights of the first count).
+ *   flags   EVC_FLAG_IP1_S2KL only; EVC_FLAG_PARTIAL_RANK is rejected.
+ * Outputs (evc_outputs_roots) are ROOT-PAIR-MAJOR: grad (npairs,count,A,3), d_pred (npairs,count,N,N) or NULL,
+ * g_pred (npairs,count,N^4) or NULL -- entry [p][g] is pair p of geometry g.
+ * The slots s = p * count + g go through the gradient chain of the batch entry points together (the t-RDM is streamed
+ * once per 32 slots); on the packed int2e_ip1 route (EVC_FLAG_IP1_S2KL) each geometry's int2e_ip1 is read once per up
+ * to 8 of its root pairs. */
+size_t evc_workspace_bytes_roots_batch(const evc_trdm_set *t, int natm, int count, int npairs);
+int evc_phase_gradient_roots_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, const double *coeffs, int nvec,
+                                   const int32_t *pairs, int npairs, const evc_outputs_roots *out, int flags, void *ws,
+                                   size_t ws_bytes, void *stream);
 
 /* Phase L: Loewdin orthogonalisation of the batch alone (electron_integral_utils.py:6-18,135): reads gb->S and
  * gb->hcore only, leaves X, U, s, h1 in the workspace for a following call with EVC_FLAG_LOEWDIN_DONE.
