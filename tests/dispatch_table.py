@@ -15,7 +15,12 @@ Fields of a case:
                    ``evc_phase_gradient`` call that follows it on the same workspace
   warm             two calls, the second warm-started; ``expect`` holds the second call's records
   nroots           roots asked for
-  api              "single" (evc_energy_with_grad, ContinuationEvaluator) or "batch" (evc_energy_with_grad_batch)
+  api              "single" (evc_energy_with_grad, ContinuationEvaluator) or "batch" (evc_energy_with_grad_batch);
+                   "roots" (ContinuationEvaluator.energies_with_grads: an energy-only evc_energy_with_grad, then
+                   evc_phase_gradient_roots) or "roots_batch" (BatchedEvaluator.multistate_energies_with_grads: an
+                   energy-only evc_energy_with_grad_batch, then evc_phase_gradient_roots_batch); ``expect`` holds the
+                   records after both calls (the gradient stages from the roots call)
+  pairs            (roots APIs) the root pairs (k, l), k <= l < nroots, of every geometry
   keep             the predicted 1- and 2-RDMs are requested as outputs (and checked)
   env              knobs the branch needs; they are read once per process, so such rows are run by the test named in
                    ``covered_by`` in a process of its own, not here
@@ -35,12 +40,17 @@ L_BIG = "loewdin_big_kernel part=0"                                     # n > 64
 
 
 def case(id, n, T, A, G, layout, expect, packed=False, energy_only=False, warm=False, nroots=1, api="batch",
-         keep=False, env=None, covered_by=None, expect_grad=None):
+         keep=False, env=None, covered_by=None, expect_grad=None, pairs=None):
     assert set(expect) == set(STAGES), id
     assert expect_grad is None or set(expect_grad) == set(STAGES), id
     return dict(id=id, n=n, T=T, A=A, G=G, layout=layout, packed=packed, energy_only=energy_only, warm=warm,
                 nroots=nroots, api=api, keep=keep, env=env or {}, covered_by=covered_by, expect=expect,
-                expect_grad=expect_grad)
+                expect_grad=expect_grad, pairs=pairs)
+
+
+def all_pairs(nroots):
+    """The diagonal pairs, then the couplings k < l."""
+    return [(k, k) for k in range(nroots)] + [(k, l) for k in range(nroots) for l in range(k + 1, nroots)]
 
 
 def st(rows, cols, pt, ip1, y2, unpack, loewdin, subspace):
@@ -200,6 +210,38 @@ CASES = [
     case("n65_sym8_full_single", 65, 1, 1, 1, "sym8", api="single",
          expect=st("gemv_rows_kernel<8,1> G=1", "gemv_cols_kernel<1>", "qt_kernel<80>", "ip1_dh_kernel<8> chunks",
                    "y2_sb_kernel<4>", "unpack8_kernel lead_half=0", L_BIG, "subspace_kernel few=0")),
+    # ---- excited-state forces and couplings: every root pair of a geometry is a slot of the gradient chain.  IP1 of
+    #      the packed pair-block route reads a geometry's int2e_ip1 rows once for up to kIp1MaxSlots of its slots
+    #      (roots_batch, P >= 2: "slots=K", K the largest power of two <= min(P, 8)); else one slot per block.  K8 runs
+    #      the G * P slots (single geometry: P) in its batched groups
+    case("roots_n6_sym8_packed_single_P3", 6, 5, 2, 1, "sym8", packed=True, api="roots", nroots=2,
+         pairs=all_pairs(2),
+         expect=st("gemv_rows_kernel<8,1> G=1", "gemv_cols_rs_kernel<1>", "pt_pipe4_kernel<16,0>",
+                   "ip1_dh_kernel<8> pairs", "y2_fused_kernel<16>", "unpack8_prep_kernel", L_RIDE,
+                   "subspace_loewdin_kernel few=1")),
+    case("roots_batch_n6_sym8_packed_G2_P1", 6, 5, 2, 2, "sym8", packed=True, api="roots_batch", nroots=2,
+         pairs=[(0, 1)],
+         expect=st("gemv_rows_kernel<8,2> G=2", "gemv_cols_rs_kernel<2>", "pt_pipe4_kernel<16,0>",
+                   "ip1_dh_kernel<8> pairs", "y2_fused_kernel<16>", "unpack8_prep_kernel", L_RIDE,
+                   "subspace_loewdin_kernel few=1")),
+    case("roots_batch_n6_sym8_packed_G2_P3", 6, 5, 2, 2, "sym8", packed=True, api="roots_batch", nroots=2,
+         pairs=all_pairs(2),
+         expect=st("gemv_rows_kernel<8,2> G=2", "gemv_cols_rs_kernel<2>", "pt_pipe_kernel<16,0>",
+                   "ip1_dh_kernel<8> pairs slots=2", "y2_fused_kernel<16>", "unpack8_prep_kernel", L_RIDE,
+                   "subspace_loewdin_kernel few=1")),
+    case("roots_batch_n10_sym8_packed_G3_P6", 10, 5, 2, 3, "sym8", packed=True, api="roots_batch", nroots=3,
+         pairs=all_pairs(3),
+         expect=st("gemv_rows_kernel<8,1> G=1", "gemv_cols_mfma_rs_kernel<8,3,2>", "pt_pipe_kernel<16,0>",
+                   "ip1_dh_kernel<8> pairs slots=4", "y2_fused_kernel<16>", "unpack8_prep_kernel", L_RIDE,
+                   "subspace_loewdin_kernel few=1")),
+    case("roots_batch_n6_sym8_packed_G2_P10", 6, 5, 2, 2, "sym8", packed=True, api="roots_batch", nroots=4,
+         pairs=all_pairs(4),
+         expect=st("gemv_rows_kernel<8,2> G=2", "gemv_cols_mfma_rs_kernel<8,3,2>", "pt_pipe_kernel<16,0>",
+                   "ip1_dh_kernel<8> pairs slots=8", "y2_fused_kernel<16>", "unpack8_prep_kernel", L_RIDE,
+                   "subspace_loewdin_kernel few=1")),
+    case("roots_batch_n6_pack2_G2_P3", 6, 5, 2, 2, "pack2", api="roots_batch", nroots=2, pairs=all_pairs(2),
+         expect=st("gemv_rows_kernel<8,2> G=2", "gemv_cols_rs_kernel<2>", "pt_kernel<16,0>", "ip1_dh_kernel<8> chunks",
+                   "y2_kernel<1>", "unpack_sym_kernel", L_RIDE, "subspace_loewdin_kernel few=1")),
 ]
 
 # Branches only a knob reaches.  The knobs are read once per process: these rows are run by the test named in

@@ -60,7 +60,13 @@ def test_table_is_well_formed():
     for c in CASES + KNOB_CASES:
         assert c["layout"] in ("full6", "pair5", "elec3", "pack2", "sym8"), c["id"]
         assert not c["packed"] or (c["layout"] == "sym8" and c["n"] <= 64), c["id"]
-        assert c["api"] == "batch" or c["G"] == 1, c["id"]
+        assert c["api"] in ("single", "batch", "roots", "roots_batch"), c["id"]
+        assert c["api"] in ("batch", "roots_batch") or c["G"] == 1, c["id"]
+        if c["api"] in ("roots", "roots_batch"):     # root pairs k <= l < nroots, no flags of the other entries
+            assert c["pairs"] and all(0 <= k <= l < c["nroots"] for k, l in c["pairs"]), c["id"]
+            assert not (c["energy_only"] or c["warm"] or c["keep"]), c["id"]
+        else:
+            assert c["pairs"] is None, c["id"]
         assert (c["expect_grad"] is not None) == c["energy_only"], c["id"]
         assert bool(c["env"]) == bool(c["covered_by"]), c["id"]
         assert 1 <= c["nroots"] <= c["T"], c["id"]
@@ -79,6 +85,21 @@ def test_knob_rows_name_existing_tests():
         assert f"def {test.split('[')[0]}(" in src, c["covered_by"]
         for k, v in c["env"].items():
             assert f'"{k}": "{v}"' in src, (c["id"], k)
+
+
+def test_every_ip1_slot_count_is_in_the_table():
+    """Every multi-slot instance of the int2e_ip1 pair-block form, 2, 4, ... kIp1MaxSlots slots per block
+    (csrc/kernels.hpp, csrc/ip1.hip ip1_kslots), is the expected IP1 record of some row."""
+    with open(os.path.join(CSRC, "kernels.hpp")) as f:
+        m = re.search(r"constexpr\s+int\s+kIp1MaxSlots\s*=\s*(\d+)\s*;", f.read())
+    assert m, "kIp1MaxSlots not found in csrc/kernels.hpp"
+    kmax = int(m.group(1))
+    assert kmax >= 2 and kmax & (kmax - 1) == 0, kmax
+    records = {exp["ip1"] for c in CASES + KNOB_CASES for exp in (c["expect"], c["expect_grad"] or {}) if exp}
+    found = {int(r) for rec in records for r in re.findall(r"\bslots=(\d+)$", rec)}
+    want = {1 << k for k in range(1, kmax.bit_length())}
+    assert want <= found, f"IP1 slot counts without a dispatch-table row: {sorted(want - found)}"
+    assert found <= want, f"IP1 slot counts the library cannot launch: {sorted(found - want)}"
 
 
 def test_every_launched_kernel_is_in_the_table():

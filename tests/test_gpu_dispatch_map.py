@@ -1,7 +1,9 @@
 """Every row of tests/dispatch_table.py that needs no knob: the call runs once, each of the eight stages reports the
 kernel the table names for it (``evc_profile_kernel``; a stage the call did not run reports ""), and the results of the
 first, a middle and the last slot match ``oracle.energy_with_grad`` on the original pack2 rows and full integral arrays:
-|dE| <= 1e-10 Ha, |dgrad| <= 1e-9 Ha/Bohr, and the predicted 1- and 2-RDMs to 1e-10 where the case asks for them."""
+|dE| <= 1e-10 Ha, |dgrad| <= 1e-9 Ha/Bohr, and the predicted 1- and 2-RDMs to 1e-10 where the case asks for them.
+The rows of the roots APIs hold every root pair of the first, a middle and the last geometry to the per-slot oracle
+of tests/test_gpu_excited_forces.py (root k's total gradient on (k, k), the coupling vector on (k, l))."""
 import numpy as np
 import pytest
 import torch
@@ -25,8 +27,10 @@ def _records():
 
 
 def _assert_records(got, want, what):
+    # (an expected IP1 record without "slots=" names the one-slot form: the multi-slot record does not match it)
     bad = {k: (got[k], want[k]) for k in STAGES
-           if (got[k] != "" if want[k] == "" else not got[k].startswith(want[k]))}
+           if (got[k] != "" if want[k] == "" else not got[k].startswith(want[k]))
+           or ("slots=" in got[k]) != ("slots=" in want[k])}
     assert not bad, (what, bad, got)
 
 
@@ -44,7 +48,10 @@ def _bundle(ao):
                         eri_ip1=c(ao.eri_ip1), aoslices=c(ao.aoslices), enuc=ao.enuc, gnuc=c(ao.gnuc))
 
 
-@pytest.mark.parametrize("c", [c for c in CASES if not c["env"]], ids=lambda c: c["id"])
+ROOTS_APIS = ("roots", "roots_batch")
+
+
+@pytest.mark.parametrize("c", [c for c in CASES if not c["env"] and c["api"] not in ROOTS_APIS], ids=lambda c: c["id"])
 def test_dispatch_case(c):
     from evcont_amd import cache
     from evcont_amd.evaluator import BatchedEvaluator, ContinuationEvaluator, DeviceAOBatch, DeviceTRDMs
@@ -105,3 +112,40 @@ def test_dispatch_case(c):
                 Go = _sym8(Go)
             assert float(np.abs(d_pred[k] - Do).max()) <= RDM_TOL, (k, float(np.abs(d_pred[k] - Do).max()))
             assert float(np.abs(g_pred[k] - Go).max()) <= RDM_TOL, (k, float(np.abs(g_pred[k] - Go).max()))
+
+
+@pytest.mark.parametrize("c", [c for c in CASES if not c["env"] and c["api"] in ROOTS_APIS], ids=lambda c: c["id"])
+def test_dispatch_roots_case(c):
+    from evcont_amd import cache
+    from evcont_amd.evaluator import BatchedEvaluator, ContinuationEvaluator, DeviceAO, DeviceAOBatch, DeviceTRDMs
+    from evcont_amd.synthetic import make_ao_arrays
+    from test_gpu_excited_forces import Oracle
+    cache.clear()
+    dev = torch.device("cuda:0")
+    n, T, A, G, nroots, pairs = c["n"], c["T"], c["A"], c["G"], c["nroots"], c["pairs"]
+    seed = 31000 + 97 * n + 7 * T + G
+    S, one, two = make_trdms(n, T, seed)
+    two_p = pack_rows(two, True, True)
+    two_l = pack_rows(two, *LAYOUT_PACK[c["layout"]]) if c["layout"] != "full6" else two
+    del two
+    trd = DeviceTRDMs(one, two_l, S, dev, compress="sym8" if c["layout"] == "sym8" else None)
+    del two_l
+    # (host-generated geometries: their root gaps are known, so the per-root oracle is well defined)
+    aos = [make_ao_arrays(n, A, seed * 100 + k, ip1_rs_symmetric=True) for k in range(G)]
+    daos = [DeviceAO.from_arrays(a, dev, pack_ip1=c["packed"], pack_eri=c["packed"]) for a in aos]
+    if c["api"] == "roots":
+        assert G == 1
+        E, Cd, grads = ContinuationEvaluator(trd, A).energies_with_grads(daos[0], nroots, pairs)
+        E, Cd, grads = E[None], Cd[None], grads[None]
+    else:
+        E, Cd, grads = BatchedEvaluator(trd, A, G).multistate_energies_with_grads(DeviceAOBatch.stack(daos), nroots,
+                                                                                  pairs)
+    _assert_records(_records(), c["expect"], "roots call")
+    for k in sorted({0, G // 2, G - 1}):
+        o = Oracle(aos[k], one, two_p, S, nroots)
+        de = float(np.abs(E[k] - o.E).max())
+        assert de <= E_TOL, (k, de)
+        o.align(Cd[k])
+        for p, (r, s) in enumerate(pairs):
+            dg = float(np.abs(grads[k][p] - o.slot(r, s)).max())
+            assert dg <= G_TOL, (k, (r, s), dg)

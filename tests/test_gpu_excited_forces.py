@@ -51,14 +51,20 @@ class Oracle:
         self.E, self.C = self.E[:nroots], self.C[:nroots]
         self.X = orc.loewdin_trafo(self.b.S)
         self.dX = orc.derivative_ao_mo_trafo(self.b)
+        self._F = {}
 
     def align(self, C_dev):
         s = np.sign(np.sum(self.C * C_dev, axis=1))
         self.C = self.C * s[:, None]
 
     def F(self, c):
-        D, G = orc.predicted_rdms(c, self.one, self.two, self.n)
-        return orc.grad_elec_OAO(self.b, D, G, X=self.X, dX=self.dX)
+        """F(c), memoised per coefficient vector (its bytes): a coupling slot reuses F(c_k) and F(c_l)."""
+        key = np.ascontiguousarray(c, dtype=np.float64).tobytes()
+        if key not in self._F:
+            D, G = orc.predicted_rdms(c, self.one, self.two, self.n)
+            self._F[key] = orc.grad_elec_OAO(self.b, D, G, X=self.X, dX=self.dX)
+            self._F[key].setflags(write=False)
+        return self._F[key]
 
     def slot(self, k, l):
         if k == l:

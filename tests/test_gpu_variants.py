@@ -14,6 +14,14 @@ LARGE_T = ["tests/test_gpu_large_T.py::test_small_n_batched", "tests/test_gpu_la
 SUBSET = ["tests/test_gpu_sym8.py::test_packed_ip1_input", "tests/test_gpu_sym8.py::test_sym8_batched",
           "tests/test_gpu_bench_config.py::test_h2o_shape_t10_against_oracle",
           "tests/test_gpu_bench_config.py::test_k5_every_row_group_body"]
+# excited-state forces and couplings (root-pair slots) through the kernels a knob selects
+_ROOTS_LARGE_T = ["tests/test_gpu_excited_forces_batch.py::test_batch_roots_large_T_subspace_kernel"]
+ROOTS = {
+    "EVC_COLS_LDS": ["tests/test_gpu_excited_slots.py::test_batch_roots_eight_slots[P10]"],        # 30 slots in K8
+    "EVC_PT_DMA": ["tests/test_gpu_excited_forces_batch.py::test_batch_roots_pair_routes"],
+    "EVC_LOEWDIN_SPLIT": _ROOTS_LARGE_T,
+    "EVC_SUBSPACE_FEW": _ROOTS_LARGE_T,
+}
 
 
 @pytest.mark.parametrize("env", [
@@ -46,6 +54,7 @@ def test_variant_passes_parity_subset(env):
     if "EVC_ROWS_LDS_NT" in env or "EVC_ROWS_LDS" in env or "EVC_COLS_LDS" in env:   # (the kernels behind these knobs: batches of >= 12)
         subset = ["tests/test_gpu_bench_config.py::test_k5_every_row_group_body",
                   "tests/test_gpu_bench_config.py::test_k5_row_groups_wide_matrix", "tests/test_gpu_sym8.py::test_sym8_batched"]
+    subset = subset + [t for k, tests in ROOTS.items() if k in env for t in tests]
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + subset,
                        cwd=REPO, env=e, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
