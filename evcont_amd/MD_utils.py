@@ -12,7 +12,8 @@ import numpy as np
 from . import _lib
 from .ab_initio_gradients_loewdin import get_energy_with_grad
 from .ab_initio_eigenvector_continuation import (approximate_ground_state_OAO, _trdms,  # noqa: F401 (re-export)
-                                                 _trdms_auto, get_trdm_compression, integrals_have_symmetry)
+                                                 _resident_trdms, _trdms_auto, get_trdm_compression,
+                                                 integrals_have_symmetry)
 from .electron_integral_utils import get_basis, get_integrals  # noqa: F401 (re-export)
 from .evaluator import ContinuationEvaluator, DeviceAO
 from .hosted import HostedEvaluator
@@ -199,8 +200,7 @@ def get_state_scanner(mol, one_rdm, two_rdm, overlap, root, hermitian=True):
             if self._ev is None:
                 compress = resolve_compression("default", one_rdm, two_rdm, overlap,
                                                ao if is_array_mol(mol) else mol, hermitian=hermitian)
-                t = _trdms_auto(one_rdm, two_rdm, overlap, compress) if get_trdm_compression() == "auto" else \
-                    _trdms(one_rdm, two_rdm, overlap, compress)
+                t = _resident_trdms(one_rdm, two_rdm, overlap, compress)
                 self._ev = ContinuationEvaluator(t, int(np.asarray(ao.aoslices).shape[0]), warm_start=True,
                                                  want_two_rdm=False)
             ev = self._ev

@@ -12,32 +12,8 @@ from .electron_integral_utils import (  # re-exported, scripts import them from 
     get_integrals,
     compress_electron_exchange_symmetry,
 )
-from .evaluator import DeviceTRDMs, DeviceAO, ContinuationEvaluator, _dev
+from .evaluator import DeviceTRDMs, DeviceAO, ContinuationEvaluator, _dev, _eig_nonhermitian, _select
 from .integrals import ao_arrays, energy_nuc, is_array_mol
-
-
-def _eig_nonhermitian(H: np.ndarray, S: np.ndarray, layout: int):
-    """The reference's non-Hermitian branch (:50-51,67-68,76-81) on the subspace matrix assembled by the
-    device: pair layouts carry the two-body part in the lower triangle only, so the upper one is filled
-    from it first; then ``scipy.linalg.eig(H, S)`` (a T x T problem, solved on the host exactly as the
-    reference does) and the |Im| < 1e-5 filter."""
-    import scipy.linalg
-    H = np.array(H, dtype=np.float64)
-    if layout in (5, 2):
-        iu = np.triu_indices(H.shape[0])
-        H[iu] = H.T[iu]
-    vals, vecs = scipy.linalg.eig(H, np.asarray(S, dtype=np.float64))
-    keep = np.abs(vals.imag) < 1.0e-5
-    return vals[keep], vecs[:, keep]
-
-
-def _select(vals, vecs, nroots, ground_state):
-    if ground_state:
-        k = int(np.argmin(vals.real))
-        return float(vals[k].real), np.array(vecs[:, k].real)
-    assert vals.shape[0] >= nroots                   # reference :166
-    order = np.argsort(vals.real)[:nroots]
-    return np.array(vals[order].real), np.array(vecs[:, order].real.T)
 
 
 # How the resident copy of the training data is stored by the mol-level entry points (``*_OAO``,
@@ -174,12 +150,19 @@ def _trdms_auto(one_RDM, two_RDM, S, compress) -> DeviceTRDMs:
     return _trdms(one_RDM, two_RDM, S, compress)
 
 
+def _resident_trdms(one_RDM, two_RDM, S, compress, auto=None) -> DeviceTRDMs:
+    """The resident training data in the storage ``compress`` (None or "sym8", what ``resolve_compression`` returned
+    for this call), verified against the host arrays or uploaded again.  ``auto``: the storage was chosen by mode
+    "auto" (``_trdms_auto``); None: whether the current mode is "auto"."""
+    if auto is None:
+        auto = _COMPRESS == "auto"
+    return _trdms_auto(one_RDM, two_RDM, S, compress) if auto else _trdms(one_RDM, two_RDM, S, compress)
+
+
 def _evaluator(one_RDM, two_RDM, S, natm: int, compress=None, auto: bool = False) -> ContinuationEvaluator:
-    """``compress``: None or "sym8" (what ``resolve_compression`` returned for this call); ``auto``: it was chosen by
-    mode "auto" (``_trdms_auto``)."""
+    """``compress``, ``auto``: as for ``_resident_trdms``."""
     assert compress in (None, "sym8")
-    # (verified against the host arrays, or uploaded again)
-    t = _trdms_auto(one_RDM, two_RDM, S, compress) if auto else _trdms(one_RDM, two_RDM, S, compress)
+    t = _resident_trdms(one_RDM, two_RDM, S, compress, auto)
     key = ("evaluator", id(t), int(natm))
     ev = cache.get(key)
     if ev is None or ev.t is not t:

@@ -122,30 +122,39 @@ def get_multistate_energy_with_grad(mol, one_RDM, two_RDM, S, nroots=1, hermitia
     nroots = int(nroots)
     ao = ao_arrays(mol, need_grad=True)
     natm = int(np.asarray(ao.aoslices).shape[0])
-    if not hermitian:
-        ev = _evaluator(one_RDM, two_RDM, S, natm, compress=None)
-    else:
-        ev = _evaluator(one_RDM, two_RDM, S, natm,
-                        compress=resolve_compression("default", one_RDM, two_RDM, S,
-                                                     mol if not is_array_mol(mol) else ao, hermitian=True,
-                                                     want_rdms=return_density_matrices),
-                        auto=get_trdm_compression() == "auto")
-    pairs = [(k, k) for k in range(nroots)]
-    if return_couplings:
-        pairs += [(k, l) for k in range(nroots) for l in range(k + 1, nroots)]
+    ev = _evaluator(one_RDM, two_RDM, S, natm,
+                    compress=resolve_compression("default", one_RDM, two_RDM, S, mol if not is_array_mol(mol) else ao,
+                                                 hermitian=hermitian, want_rdms=return_density_matrices),
+                    auto=get_trdm_compression() == "auto")
+    pairs = _root_pairs(nroots, return_couplings)
     res = ev.energies_with_grads(DeviceAO.from_arrays(ao, ev.t.device), nroots, pairs,
                                  return_density_matrices=return_density_matrices, hermitian=hermitian)
     e, grads = res[0], res[2]
     out = (e, grads[:nroots].copy())
     if return_couplings:
-        h = np.zeros((nroots, nroots) + grads.shape[1:])
-        for p, (k, l) in enumerate(pairs):
-            h[k, l] = h[l, k] = grads[p]
-        h[np.arange(nroots), np.arange(nroots)] -= np.asarray(ao.gnuc, dtype=np.float64)
-        out += (h,)
+        out += (_fold_couplings(grads, pairs, nroots, np.asarray(ao.gnuc, dtype=np.float64)),)
     if return_density_matrices:
         out += (res[3][:nroots], res[4][:nroots])
     return out
+
+
+def _root_pairs(nroots: int, couplings: bool):
+    """The slots of a multistate call: (k, k) for every root, then with ``couplings`` every (k, l), k < l."""
+    pairs = [(k, k) for k in range(nroots)]
+    if couplings:
+        pairs += [(k, l) for k in range(nroots) for l in range(k + 1, nroots)]
+    return pairs
+
+
+def _fold_couplings(grads, pairs, nroots: int, gnuc):
+    """``h[..., k, l] = h[..., l, k]`` from the slots ``grads[..., p, :, :]`` of ``pairs`` (any leading geometry axes),
+    with the nuclear term ``gnuc (..., A, 3)`` taken off the diagonal: the electronic gradients."""
+    h = np.zeros(grads.shape[:-3] + (nroots, nroots) + grads.shape[-2:])
+    for p, (k, l) in enumerate(pairs):
+        h[..., k, l, :, :] = h[..., l, k, :, :] = grads[..., p, :, :]
+    for k in range(nroots):
+        h[..., k, k, :, :] -= gnuc
+    return h
 
 
 # Workspace bytes one call of get_multistate_energies_with_grads may hold (the list is split into chunks below this and
@@ -173,7 +182,7 @@ def get_multistate_energies_with_grads(mols, one_RDM, two_RDM, S, nroots=1, herm
     that a batch holds at most 4096 (geometry, root pair) slots and ``BATCH_WORKSPACE_BUDGET`` bytes of workspace."""
     import ctypes as C
     from . import _lib
-    from .ab_initio_eigenvector_continuation import _trdms, _trdms_auto
+    from .ab_initio_eigenvector_continuation import _resident_trdms
     from .evaluator import DeviceAOBatch
     mols = list(mols)
     if not mols:
@@ -183,16 +192,10 @@ def get_multistate_energies_with_grads(mols, one_RDM, two_RDM, S, nroots=1, herm
     natm = int(np.asarray(aos[0].aoslices).shape[0])
     if any(int(np.asarray(a.aoslices).shape[0]) != natm or a.S.shape != aos[0].S.shape for a in aos):
         raise ValueError("get_multistate_energies_with_grads: the geometries must be of one molecule")
-    if not hermitian:
-        t = _trdms(one_RDM, two_RDM, S, None)
-    else:
-        compress = resolve_compression("default", one_RDM, two_RDM, S, mols[0] if not is_array_mol(mols[0]) else aos[0],
-                                       hermitian=True, want_rdms=False)
-        t = _trdms_auto(one_RDM, two_RDM, S, compress) if get_trdm_compression() == "auto" else \
-            _trdms(one_RDM, two_RDM, S, compress)
-    pairs = [(k, k) for k in range(nroots)]
-    if return_couplings:
-        pairs += [(k, l) for k in range(nroots) for l in range(k + 1, nroots)]
+    t = _resident_trdms(one_RDM, two_RDM, S,
+                        resolve_compression("default", one_RDM, two_RDM, S,
+                                            mols[0] if not is_array_mol(mols[0]) else aos[0], hermitian=hermitian))
+    pairs = _root_pairs(nroots, return_couplings)
     npairs = len(pairs)
     lib = _lib.load()
     per_slot = lib.evc_workspace_bytes_roots_batch(C.byref(t.cstruct), natm, 1, 1)
@@ -212,11 +215,5 @@ def get_multistate_energies_with_grads(mols, one_RDM, two_RDM, S, nroots=1, herm
     E, grads = np.concatenate(E), np.concatenate(grads)
     out = (E, grads[:, :nroots].copy())
     if return_couplings:
-        h = np.zeros((len(mols), nroots, nroots) + grads.shape[2:])
-        for p, (k, l) in enumerate(pairs):
-            h[:, k, l] = h[:, l, k] = grads[:, p]
-        gnuc = np.stack([np.asarray(a.gnuc, dtype=np.float64) for a in aos])
-        for k in range(nroots):
-            h[:, k, k] -= gnuc
-        out += (h,)
+        out += (_fold_couplings(grads, pairs, nroots, np.stack([np.asarray(a.gnuc, dtype=np.float64) for a in aos])),)
     return out

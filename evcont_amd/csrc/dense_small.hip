@@ -2171,12 +2171,6 @@ int launch_pair_weights(const double *c, int T, int layout, double *w1, double *
     return pair_weights_launch(a, 1, st);
 }
 
-int launch_pair_weights_slots(const double *c, int T, int layout, const int32_t *pairs, int npairs, double *w1,
-                              double *w2, double *w1t, double *w2t, int64_t sw, int64_t w2_offset, int64_t w2_count,
-                              hipStream_t st) {
-    return launch_pair_weights_geo(c, 0, 0, T, layout, pairs, npairs, w1, w2, w1t, w2t, sw, w2_offset, w2_count, st);
-}
-
 // Slots s = p * geo_period + g (geo_period > 0; npairs counts the root pairs, the launch covers npairs * geo_period
 // slots): pair p of coefficient block g.  geo_period = 0: slot p = pair p of the one block c.
 int launch_pair_weights_geo(const double *c, int64_t sc, int geo_period, int T, int layout, const int32_t *pairs,

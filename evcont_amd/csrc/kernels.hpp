@@ -242,17 +242,14 @@ int launch_subspace_big(const SolveArgs &a, int count, hipStream_t st);
 // the diagonal; otherwise c_a c_b).
 int launch_pair_weights(const double *c, int T, int layout, double *w1, double *w2, int64_t w2_offset,
                         int64_t w2_count, hipStream_t st);
-// The same for `npairs` slots at once (evc_phase_gradient_roots): slot s gets the weights of the symmetric weighting
-// W = (c_k c_l^T + c_l c_k^T) / 2 of the rows k = pairs[2s], l = pairs[2s+1] of c (nvec, T) -- c_k c_k^T for k == l --,
-// w1 / w2 at + s*sw and, if w1t / w2t are given, the transposed group copies the batched K8 reads.
-int launch_pair_weights_slots(const double *c, int T, int layout, const int32_t *pairs, int npairs, double *w1,
-                              double *w2, double *w1t, double *w2t, int64_t sw, int64_t w2_offset, int64_t w2_count,
-                              hipStream_t st);
-constexpr int kPairWeightsSlots = 256;   // slots per launch (their (k, l) travel in the kernel arguments)
-// evc_phase_gradient_roots_batch: slot s takes its rows from coeffs + geo_of(s, geo_period) * sc ((count, T, T) blocks).
+// The same for the slots of the root pairs (evc_phase_gradient_roots*): slot s = p * geo_period + g (geo_period > 0;
+// geo_period = 0: slot s = pair p = s) gets the weights of the symmetric weighting W = (c_k c_l^T + c_l c_k^T) / 2
+// of the rows k = pairs[2p], l = pairs[2p+1] of the (nvec, T) block c + geo_of(s, geo_period) * sc -- c_k c_k^T for
+// k == l --, w1 / w2 at + s*sw and, if w1t / w2t are given, the transposed group copies the batched K8 reads.
 int launch_pair_weights_geo(const double *c, int64_t sc, int geo_period, int T, int layout, const int32_t *pairs,
                             int npairs, double *w1, double *w2, double *w1t, double *w2t, int64_t sw, int64_t w2_offset,
                             int64_t w2_count, hipStream_t st);
+constexpr int kPairWeightsSlots = 256;   // slots per launch (their (k, l) travel in the kernel arguments)
 struct PairWeightsArgs {
     const double *c;          // (nvec, T) rows  + geo_of(g, geo_period)*sc
     double *w1, *w2;          // + g*sw, g = slot0 + blockIdx.y

@@ -908,6 +908,44 @@ static Geo geo_single(const evc_geometry *g) {
     return o;
 }
 
+static int check_geometry_batch(const char *who, const evc_geometry_batch *gb, bool need_grad) {
+    EVC_REQUIRE(gb, "%s: null batch descriptor", who);
+    EVC_REQUIRE(gb->count >= 1 && gb->count <= 4096, "%s: batch count=%d out of range", who, gb->count);
+    EVC_REQUIRE(gb->S && gb->hcore && gb->eri && gb->enuc, "%s: batch geometry: S/hcore/eri/enuc must be given", who);
+    EVC_REQUIRE(aligned16(gb->eri) && (!gb->eri_ip1 || aligned16(gb->eri_ip1)),
+                "%s: batch geometry: eri / eri_ip1 must be 16-byte aligned", who);
+    if (need_grad)
+        EVC_REQUIRE(gb->natm >= 1 && gb->ipovlp && gb->dhcore && gb->eri_ip1 && gb->aoslices && gb->gnuc,
+                    "%s: batch geometry: ipovlp/dhcore/eri_ip1/gnuc/aoslices are required for the gradient", who);
+    return 0;
+}
+
+// count geometries of n orbitals, each at its own stride (geo_period 0: slot g reads geometry g)
+static Geo geo_batch(int n, const evc_geometry_batch *gb) {
+    const int64_t n2 = (int64_t)n * n, n4 = n2 * n2, A3 = (int64_t)gb->natm * 3;
+    Geo g;
+    memset(&g, 0, sizeof(g));
+    g.natm = gb->natm;
+    g.count = gb->count;
+    g.S = gb->S;
+    g.sS = n2;
+    g.hcore = gb->hcore;
+    g.sh = n2;
+    g.eri = gb->eri;
+    g.seri = n4;
+    g.ipovlp = gb->ipovlp;
+    g.sip = 3 * n2;
+    g.dhcore = gb->dhcore;
+    g.sdh = A3 * n2;
+    g.eri_ip1 = gb->eri_ip1;
+    g.sip1 = 3 * n4;   // (phase_gradient: the packed size with EVC_FLAG_IP1_S2KL)
+    g.gnuc = gb->gnuc;
+    g.sgn = A3;
+    g.aoslices = gb->aoslices;
+    g.enuc_dev = gb->enuc;
+    return g;
+}
+
 static Out out_single(const evc_outputs *o) {
     Out r;
     memset(&r, 0, sizeof(r));
@@ -1089,25 +1127,44 @@ extern "C" int evc_energy_with_grad(const evc_trdm_set *t, const evc_geometry *g
     return phase_gradient(t, gg, o, flags & ~EVC_FLAG_PARTIAL_RANK, w, st);
 }
 
-// ---- several roots of ONE geometry: evc_phase_gradient_roots ---------------------------------------------------
-// Slot p of the call is a batch "geometry" whose weights are those of the pair pairs[p] = (k, l); the geometry inputs
-// are shared (stride 0) and the per-geometry state phases A+B left in slot 0 (X, U, s, h1, K3) is copied into the
-// other slots, so that the batched gradient chain runs unchanged for count = npairs: K8 reads the t-RDM once per
-// kMaxBatchG slots.  Behind the npairs slot workspaces: the per-slot nuclear term (grad_nuc on the diagonal slots).
+// ---- several roots: evc_phase_gradient_roots (one geometry), evc_phase_gradient_roots_batch (several) -------------
+// Root-pair-major slots s = p * count + g: pair p = (k, l) of geometry g, whose row weights are those of the symmetric
+// weighting of rows k, l of geometry g's coefficient block.  Block p = 0 is the workspace the energy-only call left
+// (geometries 0 .. count-1); the state phases A+B left there (X, U, s, lflag, h1, K3) is copied into the blocks p >= 1,
+// so that the batched gradient chain runs unchanged for count * npairs slots: K8 reads the t-RDM once per kMaxBatchG
+// slots.  Behind the slots: the per-slot nuclear term (grad_nuc on the diagonal pairs, zero on the couplings).
+// gradient_roots does all of that for both entry points; they differ in their geometry alone:
+//   evc_phase_gradient_roots        count = 1, every stride 0 and geo_period = 0: to the chain every slot is a geometry
+//                                   of its own, so the IP1 contraction keeps its one-slot form;
+//                                   gnuc is optional (NULL: no nuclear term);
+//   evc_phase_gradient_roots_batch  geo_period = count: slot s reads the caller's inputs of geometry s % count
+//                                   (kernels.hpp geo_of); gnuc is required.
+// The nuclear term: with a coupling pair in the list the buffer is cleared and grad_nuc copied to each diagonal pair;
+// with the diagonal alone it is copied once and fanned out like the slot state.
 constexpr int kMaxRootPairs = 4096;
-static size_t roots_gnuc_bytes(int natm, int npairs) {
-    return align_up((size_t)npairs * (natm > 0 ? natm : 1) * 3 * sizeof(double), 256);
+// count * npairs slots of `slot_bytes` each, then the per-slot nuclear term
+static size_t roots_bytes(size_t slot_bytes, int natm, int nslots) {
+    return slot_bytes * (size_t)nslots + align_up((size_t)nslots * (natm > 0 ? natm : 1) * 3 * sizeof(double), 256);
 }
 
-extern "C" size_t evc_workspace_bytes_roots(const evc_trdm_set *t, int natm, int npairs) {
+static size_t workspace_bytes_roots(const char *who, const evc_trdm_set *t, int natm, int count, int npairs) {
     if (check_set(t)) return 0;
-    if (npairs < 1 || npairs > kMaxRootPairs) {
-        set_error("evc_workspace_bytes_roots: npairs=%d out of range 1..%d", npairs, kMaxRootPairs);
+    if (count < 1 || npairs < 1 || (int64_t)count * npairs > kMaxRootPairs) {
+        set_error("%s: count=%d, npairs=%d (need count >= 1, npairs >= 1, count * npairs <= %d)", who, count, npairs,
+                  kMaxRootPairs);
         return 0;
     }
     Ws w;
     carve(t, natm, nullptr, w);
-    return w.bytes * (size_t)npairs + roots_gnuc_bytes(natm, npairs);
+    return roots_bytes(w.bytes, natm, count * npairs);
+}
+
+extern "C" size_t evc_workspace_bytes_roots(const evc_trdm_set *t, int natm, int npairs) {
+    return workspace_bytes_roots("evc_workspace_bytes_roots", t, natm, 1, npairs);
+}
+
+extern "C" size_t evc_workspace_bytes_roots_batch(const evc_trdm_set *t, int natm, int count, int npairs) {
+    return workspace_bytes_roots("evc_workspace_bytes_roots_batch", t, natm, count, npairs);
 }
 
 // Block b of `rows` rows (row r at base + (b * rows + r) * pitch, `bytes` bytes each) := block 0, for b = 1 .. blocks-1:
@@ -1127,9 +1184,84 @@ static int fan_out_blocks(char *base, size_t bytes, size_t pitch, int rows, int 
     }
     return 0;
 }
-// dst[s * pitch] = src[0] for s = 1 .. count-1
-static int fan_out(char *base, size_t bytes, size_t pitch, int count, hipStream_t st) {
-    return fan_out_blocks(base, bytes, pitch, 1, count, st);
+
+// g: the caller's count = g.count geometries (checked, with t, by the caller); sc: the stride of their (T, T)
+// coefficient blocks (0: one block for every slot).
+static int gradient_roots(const char *who, const evc_trdm_set *t, Geo g, const double *coeffs, int64_t sc, int nvec,
+                          const int32_t *pairs, int npairs, const evc_outputs_roots *out, int flags, void *ws,
+                          size_t ws_bytes, void *stream) {
+    EVC_REQUIRE(coeffs && pairs, "%s: coeffs / pairs is NULL", who);
+    EVC_REQUIRE(out && out->grad, "%s: outputs.grad is required", who);
+    EVC_REQUIRE(!(flags & EVC_FLAG_PARTIAL_RANK), "%s: EVC_FLAG_PARTIAL_RANK is not supported", who);
+    EVC_REQUIRE(!(flags & ~EVC_FLAG_IP1_S2KL), "%s: flags=%d (only EVC_FLAG_IP1_S2KL is accepted)", who, flags);
+    EVC_REQUIRE(npairs >= 1 && npairs <= kMaxRootPairs, "%s: npairs=%d out of range 1..%d", who, npairs, kMaxRootPairs);
+    const int count = g.count;
+    EVC_REQUIRE((int64_t)count * npairs <= kMaxRootPairs, "%s: count * npairs = %d * %d exceeds %d slots", who, count,
+                npairs, kMaxRootPairs);
+    EVC_REQUIRE(nvec >= 1 && nvec <= t->ntrain, "%s: nvec=%d out of range 1..%d (T)", who, nvec, t->ntrain);
+    bool any_coupling = false;
+    for (int p = 0; p < npairs; ++p) {
+        const int k = pairs[2 * p], l = pairs[2 * p + 1];
+        EVC_REQUIRE(0 <= k && k <= l && l < nvec, "%s: pair %d = (%d, %d) outside 0 <= k <= l < nvec=%d", who, p, k, l,
+                    nvec);
+        any_coupling = any_coupling || k != l;
+    }
+    EVC_REQUIRE(ws && aligned16(ws), "%s: workspace NULL or misaligned", who);
+    const int nslots = count * npairs;
+    Ws w;
+    carve(t, g.natm, static_cast<char *>(ws), w);
+    const size_t need = roots_bytes(w.bytes, g.natm, nslots);
+    EVC_REQUIRE(ws_bytes >= need, "%s: workspace too small: %zu < %zu", who, ws_bytes, need);
+    replan(t, w, nslots);
+    hipStream_t st = as_stream(stream);
+    const int n = t->n;
+    const int64_t n2 = (int64_t)n * n, A3 = (int64_t)g.natm * 3;
+    int rc;
+    // (1) row weights of every slot: pair p of coefficient block g (+ the transposed group copies of the batched K8)
+    if ((rc = launch_pair_weights_geo(coeffs, sc, g.geo_period, t->ntrain, t->layout, pairs, npairs, w.w1, w.w2,
+                                      nslots > 1 ? w.w1t : nullptr, nslots > 1 ? w.w2t : nullptr, w.stride,
+                                      t->row_offset, t->rows2, st)))
+        return rc;
+    // (2) block 0 into the blocks p >= 1; U and s may still come from the side stream (phase A of an energy-only call)
+    if ((rc = side_join(w.base, st))) return rc;
+    char *b0 = static_cast<char *>(ws);
+    if (npairs > 1) {
+        // X, U, s, lflag, h1 (consecutive at the head of a slot) and K3: what phase A left there for Y2, the dense
+        // (pair, pair) intermediate of its first pair step where Y2 recomputes the half-transformed integrals
+        const bool pairs_route = use_pair_transform(n) || use_pair64(t->layout, n, (flags & EVC_FLAG_IP1_S2KL) != 0);
+        const size_t k3 = (pairs_route && use_fused_y2(is_sym8(t->layout), n)) ? (size_t)pair_ld(n) * pair_ld(n)
+                                                                                 : (size_t)n * n * n * n;
+        if ((rc = fan_out_blocks(b0, (size_t)((char *)(w.h1 + n2) - (char *)w.X), w.bytes, count, npairs, st)))
+            return rc;
+        if ((rc = fan_out_blocks((char *)w.K3, sizeof(double) * k3, w.bytes, count, npairs, st))) return rc;
+    }
+    // (3) nuclear term: the geometry's grad_nuc on the diagonal pairs, zero on the couplings
+    if (g.gnuc) {
+        char *gnuc = b0 + w.bytes * (size_t)nslots;
+        const size_t blk = sizeof(double) * A3 * count;   // one pair's (count, A, 3)
+        if (any_coupling) {
+            EVC_HIP(hipMemsetAsync(gnuc, 0, blk * npairs, st));
+            for (int p = 0; p < npairs; ++p)
+                if (pairs[2 * p] == pairs[2 * p + 1])
+                    EVC_HIP(hipMemcpyAsync(gnuc + blk * p, g.gnuc, blk, hipMemcpyDeviceToDevice, st));
+        } else {
+            EVC_HIP(hipMemcpyAsync(gnuc, g.gnuc, blk, hipMemcpyDeviceToDevice, st));
+            if ((rc = fan_out_blocks(gnuc, blk, blk, 1, npairs, st))) return rc;
+        }
+        g.gnuc = reinterpret_cast<const double *>(gnuc);
+    }
+    // (4) the gradient chain for count * npairs slots
+    g.count = nslots;
+    g.sgn = A3;
+    Out o;
+    memset(&o, 0, sizeof(o));
+    o.grad = out->grad;
+    o.sg = A3;
+    o.d_pred = out->d_pred;
+    o.sd = n2;
+    o.g_pred = out->g_pred;
+    o.sG = n2 * n2;
+    return phase_gradient(t, g, o, flags, w, st);
 }
 
 extern "C" int evc_phase_gradient_roots(const evc_trdm_set *t, const evc_geometry *g, const double *coeffs, int nvec,
@@ -1138,96 +1270,8 @@ extern "C" int evc_phase_gradient_roots(const evc_trdm_set *t, const evc_geometr
     clear_kernels(kStagesGradient);
     if (check_set(t)) return -1;
     if (check_geometry(g, true)) return -1;
-    EVC_REQUIRE(coeffs && pairs, "evc_phase_gradient_roots: coeffs / pairs is NULL");
-    EVC_REQUIRE(out && out->grad, "evc_phase_gradient_roots: outputs.grad is required");
-    EVC_REQUIRE(!(flags & EVC_FLAG_PARTIAL_RANK), "evc_phase_gradient_roots: EVC_FLAG_PARTIAL_RANK is not supported");
-    EVC_REQUIRE(!(flags & ~EVC_FLAG_IP1_S2KL), "evc_phase_gradient_roots: flags=%d (only EVC_FLAG_IP1_S2KL is accepted)",
-                flags);
-    EVC_REQUIRE(npairs >= 1 && npairs <= kMaxRootPairs, "evc_phase_gradient_roots: npairs=%d out of range 1..%d", npairs,
-                kMaxRootPairs);
-    EVC_REQUIRE(nvec >= 1 && nvec <= t->ntrain, "evc_phase_gradient_roots: nvec=%d out of range 1..%d (T)", nvec,
-                t->ntrain);
-    for (int p = 0; p < npairs; ++p) {
-        const int k = pairs[2 * p], l = pairs[2 * p + 1];
-        EVC_REQUIRE(0 <= k && k <= l && l < nvec, "evc_phase_gradient_roots: pair %d = (%d, %d) outside 0 <= k <= l < nvec=%d",
-                    p, k, l, nvec);
-    }
-    EVC_REQUIRE(ws && aligned16(ws), "evc_phase_gradient_roots: workspace NULL or misaligned");
-    Ws w;
-    carve(t, g->natm, static_cast<char *>(ws), w);
-    const size_t need = w.bytes * (size_t)npairs + roots_gnuc_bytes(g->natm, npairs);
-    EVC_REQUIRE(ws_bytes >= need, "evc_phase_gradient_roots: workspace too small: %zu < %zu", ws_bytes, need);
-    replan(t, w, npairs);
-    hipStream_t st = as_stream(stream);
-    const int64_t sw = w.stride, A3 = (int64_t)g->natm * 3;
-    int rc;
-    // (1) row weights of every slot (+ the transposed group copies the batched K8 reads)
-    if ((rc = launch_pair_weights_slots(coeffs, t->ntrain, t->layout, pairs, npairs, w.w1, w.w2,
-                                        npairs > 1 ? w.w1t : nullptr, npairs > 1 ? w.w2t : nullptr, sw, t->row_offset,
-                                        t->rows2, st)))
-        return rc;
-    // (2) slot 0's geometry state into the other slots; U and s may still come from the side stream (phase A of an
-    //     energy-only call)
-    if ((rc = side_join(w.base, st))) return rc;
-    char *b0 = static_cast<char *>(ws);
-    const size_t pitch = w.bytes;
-    if (npairs > 1) {
-        // X, U, s, lflag, h1 (consecutive at the head of a slot) and K3: what phase A left there for Y2, the dense
-        // (pair, pair) intermediate of its first pair step where Y2 recomputes the half-transformed integrals
-        const int n = t->n;
-        const bool pairs_route = use_pair_transform(n) || use_pair64(t->layout, n, (flags & EVC_FLAG_IP1_S2KL) != 0);
-        const size_t k3 = (pairs_route && use_fused_y2(is_sym8(t->layout), n)) ? (size_t)pair_ld(n) * pair_ld(n)
-                                                                                 : (size_t)n * n * n * n;
-        if ((rc = fan_out(b0, (size_t)((char *)(w.h1 + (size_t)n * n) - (char *)w.X), pitch, npairs, st))) return rc;
-        if ((rc = fan_out((char *)w.K3, sizeof(double) * k3, pitch, npairs, st))) return rc;
-    }
-    // (3) nuclear term on the diagonal slots only
-    double *gnuc = nullptr;
-    if (g->gnuc) {
-        gnuc = reinterpret_cast<double *>(b0 + w.bytes * (size_t)npairs);
-        bool all_diag = true;
-        for (int p = 0; p < npairs; ++p) all_diag = all_diag && pairs[2 * p] == pairs[2 * p + 1];
-        if (all_diag) {
-            EVC_HIP(hipMemcpyAsync(gnuc, g->gnuc, sizeof(double) * A3, hipMemcpyDeviceToDevice, st));
-            if ((rc = fan_out((char *)gnuc, sizeof(double) * A3, sizeof(double) * A3, npairs, st))) return rc;
-        } else {
-            EVC_HIP(hipMemsetAsync(gnuc, 0, sizeof(double) * A3 * npairs, st));
-            for (int p = 0; p < npairs; ++p)
-                if (pairs[2 * p] == pairs[2 * p + 1])
-                    EVC_HIP(hipMemcpyAsync(gnuc + p * A3, g->gnuc, sizeof(double) * A3, hipMemcpyDeviceToDevice, st));
-        }
-    }
-    // (4) the gradient chain for count = npairs slots of one geometry (every geometry stride 0)
-    Geo gg = geo_single(g);
-    gg.count = npairs;
-    gg.gnuc = gnuc;
-    gg.sgn = A3;
-    Out o;
-    memset(&o, 0, sizeof(o));
-    o.grad = out->grad;
-    o.sg = A3;
-    o.d_pred = out->d_pred;
-    o.sd = (int64_t)t->n * t->n;
-    o.g_pred = out->g_pred;
-    o.sG = o.sd * o.sd;
-    return phase_gradient(t, gg, o, flags, w, st);
-}
-
-// ---- several roots of SEVERAL geometries: evc_phase_gradient_roots_batch -------------------------------------------
-// Root-pair-major slots s = p * count + g (pair p of geometry g): block p = 0 is the workspace the batched energy-only
-// call left (geometries 0 .. count-1), the blocks p >= 1 are filled from it as evc_phase_gradient_roots fills its
-// slots from slot 0.  The gradient chain then runs for npairs * count slots with geo_period = count: slot s reads the
-// caller's inputs of geometry s % count (kernels.hpp geo_of).  Behind the slots: the per-slot nuclear term.
-extern "C" size_t evc_workspace_bytes_roots_batch(const evc_trdm_set *t, int natm, int count, int npairs) {
-    if (check_set(t)) return 0;
-    if (count < 1 || npairs < 1 || (int64_t)count * npairs > kMaxRootPairs) {
-        set_error("evc_workspace_bytes_roots_batch: count=%d, npairs=%d (need count >= 1, npairs >= 1, count * npairs <= %d)",
-                  count, npairs, kMaxRootPairs);
-        return 0;
-    }
-    Ws w;
-    carve(t, natm, nullptr, w);
-    return w.bytes * (size_t)count * npairs + roots_gnuc_bytes(natm, count * npairs);
+    return gradient_roots("evc_phase_gradient_roots", t, geo_single(g), coeffs, 0, nvec, pairs, npairs, out, flags, ws,
+                          ws_bytes, stream);
 }
 
 extern "C" int evc_phase_gradient_roots_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, const double *coeffs,
@@ -1236,138 +1280,25 @@ extern "C" int evc_phase_gradient_roots_batch(const evc_trdm_set *t, const evc_g
     const char *who = "evc_phase_gradient_roots_batch";
     clear_kernels(kStagesGradient);
     if (check_set(t)) return -1;
-    EVC_REQUIRE(gb, "%s: null batch descriptor", who);
-    EVC_REQUIRE(gb->count >= 1 && gb->count <= 4096, "%s: batch count=%d out of range", who, gb->count);
-    EVC_REQUIRE(gb->S && gb->hcore && gb->eri && gb->enuc, "%s: batch geometry: S/hcore/eri/enuc must be given", who);
-    EVC_REQUIRE(aligned16(gb->eri) && (!gb->eri_ip1 || aligned16(gb->eri_ip1)),
-                "%s: batch geometry: eri / eri_ip1 must be 16-byte aligned", who);
-    EVC_REQUIRE(gb->natm >= 1 && gb->ipovlp && gb->dhcore && gb->eri_ip1 && gb->aoslices && gb->gnuc,
-                "%s: batch geometry: ipovlp/dhcore/eri_ip1/gnuc/aoslices are required for the gradient", who);
-    EVC_REQUIRE(coeffs && pairs, "%s: coeffs / pairs is NULL", who);
-    EVC_REQUIRE(out && out->grad, "%s: outputs.grad is required", who);
-    EVC_REQUIRE(!(flags & EVC_FLAG_PARTIAL_RANK), "%s: EVC_FLAG_PARTIAL_RANK is not supported", who);
-    EVC_REQUIRE(!(flags & ~EVC_FLAG_IP1_S2KL), "%s: flags=%d (only EVC_FLAG_IP1_S2KL is accepted)", who, flags);
-    EVC_REQUIRE(npairs >= 1 && npairs <= kMaxRootPairs, "%s: npairs=%d out of range 1..%d", who, npairs, kMaxRootPairs);
-    const int count = gb->count;
-    EVC_REQUIRE((int64_t)count * npairs <= kMaxRootPairs, "%s: count * npairs = %d * %d exceeds %d slots", who, count,
-                npairs, kMaxRootPairs);
-    EVC_REQUIRE(nvec >= 1 && nvec <= t->ntrain, "%s: nvec=%d out of range 1..%d (T)", who, nvec, t->ntrain);
-    for (int p = 0; p < npairs; ++p) {
-        const int k = pairs[2 * p], l = pairs[2 * p + 1];
-        EVC_REQUIRE(0 <= k && k <= l && l < nvec, "%s: pair %d = (%d, %d) outside 0 <= k <= l < nvec=%d", who, p, k, l,
-                    nvec);
-    }
-    EVC_REQUIRE(ws && aligned16(ws), "%s: workspace NULL or misaligned", who);
-    const int nslots = count * npairs;
-    Ws w;
-    carve(t, gb->natm, static_cast<char *>(ws), w);
-    const size_t need = w.bytes * (size_t)nslots + roots_gnuc_bytes(gb->natm, nslots);
-    EVC_REQUIRE(ws_bytes >= need, "%s: workspace too small: %zu < %zu", who, ws_bytes, need);
-    replan(t, w, nslots);
-    hipStream_t st = as_stream(stream);
-    const int n = t->n;
-    const int64_t sw = w.stride, A3 = (int64_t)gb->natm * 3, T = t->ntrain;
-    int rc;
-    // (1) row weights of every slot: pair p of coefficient block g (+ the transposed group copies of the batched K8)
-    if ((rc = launch_pair_weights_geo(coeffs, T * T, count, (int)T, t->layout, pairs, npairs, w.w1, w.w2,
-                                      nslots > 1 ? w.w1t : nullptr, nslots > 1 ? w.w2t : nullptr, sw, t->row_offset,
-                                      t->rows2, st)))
-        return rc;
-    // (2) block 0 (the count geometries' state of phases A+B) into the blocks p >= 1; U and s may still come from the
-    //     side stream (phase A of an energy-only call)
-    if ((rc = side_join(w.base, st))) return rc;
-    char *b0 = static_cast<char *>(ws);
-    const size_t pitch = w.bytes;
-    if (npairs > 1) {
-        // the same regions as evc_phase_gradient_roots: X, U, s, lflag, h1 and K3
-        const bool pairs_route = use_pair_transform(n) || use_pair64(t->layout, n, (flags & EVC_FLAG_IP1_S2KL) != 0);
-        const size_t k3 = (pairs_route && use_fused_y2(is_sym8(t->layout), n)) ? (size_t)pair_ld(n) * pair_ld(n)
-                                                                                 : (size_t)n * n * n * n;
-        if ((rc = fan_out_blocks(b0, (size_t)((char *)(w.h1 + (size_t)n * n) - (char *)w.X), pitch, count, npairs, st)))
-            return rc;
-        if ((rc = fan_out_blocks((char *)w.K3, sizeof(double) * k3, pitch, count, npairs, st))) return rc;
-    }
-    // (3) nuclear term: the geometry's grad_nuc on the diagonal pairs, zero on the couplings
-    double *gnuc = reinterpret_cast<double *>(b0 + w.bytes * (size_t)nslots);
-    const size_t blk = sizeof(double) * A3 * count;   // one pair's (count, A, 3)
-    bool any_coupling = false;
-    for (int p = 0; p < npairs; ++p) any_coupling = any_coupling || pairs[2 * p] != pairs[2 * p + 1];
-    if (any_coupling) EVC_HIP(hipMemsetAsync(gnuc, 0, blk * npairs, st));
-    for (int p = 0; p < npairs; ++p)
-        if (pairs[2 * p] == pairs[2 * p + 1])
-            EVC_HIP(hipMemcpyAsync(reinterpret_cast<char *>(gnuc) + blk * p, gb->gnuc, blk, hipMemcpyDeviceToDevice, st));
-    // (4) the gradient chain for npairs * count slots; slot s reads geometry s % count
-    Geo g;
-    memset(&g, 0, sizeof(g));
-    const int64_t n2 = (int64_t)n * n, n4 = n2 * n2;
-    g.natm = gb->natm;
-    g.count = nslots;
-    g.geo_period = count;
-    g.S = gb->S;
-    g.sS = n2;
-    g.hcore = gb->hcore;
-    g.sh = n2;
-    g.eri = gb->eri;
-    g.seri = n4;
-    g.ipovlp = gb->ipovlp;
-    g.sip = 3 * n2;
-    g.dhcore = gb->dhcore;
-    g.sdh = A3 * n2;
-    g.eri_ip1 = gb->eri_ip1;
-    g.sip1 = 3 * n4;   // (phase_gradient: the packed size with EVC_FLAG_IP1_S2KL)
-    g.gnuc = gnuc;
-    g.sgn = A3;
-    g.aoslices = gb->aoslices;
-    g.enuc_dev = gb->enuc;
-    Out o;
-    memset(&o, 0, sizeof(o));
-    o.grad = out->grad;
-    o.sg = A3;
-    o.d_pred = out->d_pred;
-    o.sd = n2;
-    o.g_pred = out->g_pred;
-    o.sG = n4;
-    return phase_gradient(t, g, o, flags, w, st);
+    if (check_geometry_batch(who, gb, true)) return -1;
+    Geo g = geo_batch(t->n, gb);
+    g.geo_period = gb->count;
+    return gradient_roots(who, t, g, coeffs, (int64_t)t->ntrain * t->ntrain, nvec, pairs, npairs, out, flags, ws,
+                          ws_bytes, stream);
 }
 
 // Shared argument checking / descriptor set-up of the batch entry points.
 static int setup_batch(const char *who, const evc_trdm_set *t, const evc_geometry_batch *gb,
                        const evc_outputs_batch *ob, bool need_grad, void *ws, size_t ws_bytes, Ws &w, Geo &g, Out &o) {
     if (check_set(t)) return -1;
-    EVC_REQUIRE(gb, "%s: null batch descriptor", who);
-    EVC_REQUIRE(gb->count >= 1 && gb->count <= 4096, "%s: batch count=%d out of range", who, gb->count);
-    EVC_REQUIRE(gb->S && gb->hcore && gb->eri && gb->enuc, "%s: batch geometry: S/hcore/eri/enuc must be given", who);
-    EVC_REQUIRE(aligned16(gb->eri) && (!gb->eri_ip1 || aligned16(gb->eri_ip1)),
-                "%s: batch geometry: eri / eri_ip1 must be 16-byte aligned", who);
-    if (need_grad) {
-        EVC_REQUIRE(gb->natm >= 1 && gb->ipovlp && gb->dhcore && gb->eri_ip1 && gb->aoslices && gb->gnuc,
-                    "%s: batch geometry: ipovlp/dhcore/eri_ip1/gnuc/aoslices are required for the gradient", who);
-        EVC_REQUIRE(ob && ob->grad, "%s: batch outputs.grad is required", who);
-    }
+    if (check_geometry_batch(who, gb, need_grad)) return -1;
+    EVC_REQUIRE(!need_grad || (ob && ob->grad), "%s: batch outputs.grad is required", who);
     EVC_REQUIRE(ws && aligned16(ws), "%s: workspace NULL or misaligned", who);
     carve(t, gb->natm, static_cast<char *>(ws), w);
     EVC_REQUIRE(ws_bytes >= w.bytes * (size_t)gb->count, "%s: workspace too small: %zu < %zu", who, ws_bytes,
                 w.bytes * (size_t)gb->count);
-    const int64_t n = t->n, n2 = n * n, n4 = n2 * n2, T = t->ntrain, A = gb->natm;
-    memset(&g, 0, sizeof(g));
-    g.natm = gb->natm;
-    g.count = gb->count;
-    g.S = gb->S;
-    g.sS = n2;
-    g.hcore = gb->hcore;
-    g.sh = n2;
-    g.eri = gb->eri;
-    g.seri = n4;
-    g.ipovlp = gb->ipovlp;
-    g.sip = 3 * n2;
-    g.dhcore = gb->dhcore;
-    g.sdh = A * 3 * n2;
-    g.eri_ip1 = gb->eri_ip1;
-    g.sip1 = 3 * n4;
-    g.gnuc = gb->gnuc;
-    g.sgn = A * 3;
-    g.aoslices = gb->aoslices;
-    g.enuc_dev = gb->enuc;
+    const int64_t n2 = (int64_t)t->n * t->n, n4 = n2 * n2, T = t->ntrain, A = gb->natm;
+    g = geo_batch(t->n, gb);
     memset(&o, 0, sizeof(o));
     if (ob) {
         o.energy = ob->energy;

@@ -528,7 +528,129 @@ def _ip1_flag(trdms: "DeviceTRDMs", ao) -> int:
     return f
 
 
-class BatchedEvaluator:
+def _eig_nonhermitian(H: np.ndarray, S: np.ndarray, layout: int):
+    """The reference's non-Hermitian branch (:50-51,67-68,76-81) on the subspace matrix assembled by the
+    device: pair layouts carry the two-body part in the lower triangle only, so the upper one is filled
+    from it first; then ``scipy.linalg.eig(H, S)`` (a T x T problem, solved on the host exactly as the
+    reference does) and the |Im| < 1e-5 filter."""
+    import scipy.linalg
+    H = np.array(H, dtype=np.float64)
+    if layout in (5, 2):
+        iu = np.triu_indices(H.shape[0])
+        H[iu] = H.T[iu]
+    vals, vecs = scipy.linalg.eig(H, np.asarray(S, dtype=np.float64))
+    keep = np.abs(vals.imag) < 1.0e-5
+    return vals[keep], vecs[:, keep]
+
+
+def _select(vals, vecs, nroots, ground_state):
+    if ground_state:
+        k = int(np.argmin(vals.real))
+        return float(vals[k].real), np.array(vecs[:, k].real)
+    assert vals.shape[0] >= nroots                   # reference :166
+    order = np.argsort(vals.real)[:nroots]
+    return np.array(vals[order].real), np.array(vecs[:, order].real.T)
+
+
+def _check_nonhermitian(t: "DeviceTRDMs") -> None:
+    """hermitian=False solves the subspace matrix of the caller's layout, assembled from the complete t-RDM."""
+    if t.layout == _lib.LAYOUT_SYM8:
+        raise _lib.EvcontHipError("hermitian=False needs the training data in the layout the caller holds, not sym8")
+    if (t.row_offset, t.rows_local) != (0, t.rows_total):
+        raise _lib.EvcontHipError("hermitian=False needs the complete t-RDM on this device")
+
+
+class _EvaluatorBase:
+    """What ``ContinuationEvaluator`` (one geometry per call) and ``BatchedEvaluator`` (``count`` geometries per call)
+    share: the workspace, the stream every call is enqueued on, and the several-roots call.  A subclass names its
+    library calls by ``_suffix`` ("" / "_batch") and the leading shape of its per-geometry arrays by ``_lead``."""
+    _suffix = ""
+
+    @property
+    def _lead(self) -> tuple:
+        return ()
+
+    def _workspace_bytes(self, name: str, *args) -> int:
+        """``name + _suffix`` (an ``evc_workspace_bytes*`` query) for this evaluator's geometries and ``args``."""
+        nbytes = getattr(self.lib, name + self._suffix)(C.byref(self.t.cstruct), self.natm, *self._lead, *args)
+        if nbytes == 0:
+            raise _lib.EvcontHipError(f"{name}{self._suffix}: " + self.lib.evc_last_error().decode())
+        return nbytes
+
+    def _set_workspace(self, ws: torch.Tensor) -> None:
+        self.ws, self.ws_bytes = ws, int(ws.numel())
+        # (the library may attach a side stream to the workspace, include/evcont_hip.h evc_release_workspace)
+        self._ws_release = weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr())
+        self._ws_release.atexit = False
+
+    def _init_workspace(self) -> None:
+        # zero-filled once: the cached factorisation of S_train in it is recognised by content (a recycled allocator
+        # block must not look like a hit)
+        nbytes = self._workspace_bytes("evc_workspace_bytes")
+        self._set_workspace(torch.zeros(nbytes, dtype=torch.uint8, device=self.t.device))
+
+    def _grow_workspace(self, nbytes: int) -> None:
+        """Enlarge the workspace to ``nbytes`` (never shrinks).  The geometries' slots keep their place and contents
+        (the cached factorisation of S_train, the warm-start eigenvectors); the rest is zero-filled."""
+        if nbytes <= self.ws_bytes:
+            return
+        st = self._stream()
+        self._ws_release()          # waits for a side-stream launch into the old workspace, drops its events
+        ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.t.device)
+        with torch.cuda.stream(st):
+            ws[: self.ws_bytes].copy_(self.ws)
+        st.synchronize()
+        self._set_workspace(ws)
+
+    def _stream(self) -> "torch.cuda.Stream":
+        return self.stream if self.stream is not None else torch.cuda.current_stream(self.t.device)
+
+    def _sp(self) -> int:
+        return self._stream().cuda_stream
+
+    def synchronize(self) -> None:
+        self._stream().synchronize()
+
+    def _gradient_roots(self, ao, nroots: int, pairs, want_d: bool, want_g: bool, hermitian: bool):
+        """Energies of the lowest ``nroots`` roots, then one gradient slot per root pair of ``pairs`` (default: the
+        diagonal) in one pass of the gradient chain (``evc_phase_gradient_roots`` / ``_batch``).  Returns the host
+        energies and coefficient rows and the device ``grads``, ``D`` and ``Gamma`` of the slots, with the leading
+        shape ``(P,) + _lead``."""
+        T, n = self.t.T, self.t.n
+        nroots = int(nroots)
+        if not 1 <= nroots <= T:
+            raise ValueError(f"nroots={nroots} out of range 1..{T}")
+        if pairs is None:
+            pairs = [(k, k) for k in range(nroots)]
+        P = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        npairs = P.shape[0]
+        self._grow_workspace(self._workspace_bytes("evc_workspace_bytes_roots", npairs))
+        if hermitian:
+            self.enqueue(ao, nroots, energy_only=True)
+            coeffs = self.coeffs                      # rows 0 .. nroots-1 of every geometry as the solver wrote them
+        else:
+            e, c, coeffs = self._host_coeffs(ao, nroots)
+        d, lead = self.t.device, (npairs,) + self._lead
+        grads = torch.zeros(lead + (max(self.natm, 1), 3), dtype=F64, device=d)
+        D = torch.zeros(lead + (n, n), dtype=F64, device=d) if want_d else None
+        Gm = torch.zeros(lead + (n, n, n, n), dtype=F64, device=d) if want_g else None
+        p = lambda t: (t.data_ptr() if t is not None else None)
+        out = _lib.OutputsRoots(grad=p(grads), d_pred=p(D), g_pred=p(Gm))
+        g = ao.cstruct()
+        name = "evc_phase_gradient_roots" + self._suffix
+        rc = getattr(self.lib, name)(C.byref(self.t.cstruct), C.byref(g), coeffs.data_ptr(), nroots, P.ctypes.data,
+                                     npairs, C.byref(out), _ip1_flag(self.t, ao) & _lib.FLAG_IP1_S2KL,
+                                     self.ws.data_ptr(), self.ws_bytes, self._sp())
+        check(rc, name)
+        self.synchronize()        # (coeffs of the eig branch live until here)
+        if hermitian:
+            e = self.energy[..., :nroots].cpu().numpy().copy()
+            self._raise_if_nan(e[..., 0])
+            c = self.coeffs[..., :nroots, :].cpu().numpy().copy()
+        return e, c, grads, D, Gm
+
+
+class BatchedEvaluator(_EvaluatorBase):
     """``count`` independent geometries per call (``evc_energy_with_grad_batch``): every launch covers
     the whole batch and the t-RDM is streamed once per up to 32 geometries.  Results stay on the device in
     ``energy (G,T)``, ``coeffs (G,T,T)``, ``grad (G,A,3)``."""
@@ -544,16 +666,7 @@ class BatchedEvaluator:
         self.warm_start, self._primed = bool(warm_start), False
         self.lib = _lib.load()
         d, n, T = trdms.device, trdms.n, trdms.T
-        nbytes = self.lib.evc_workspace_bytes_batch(C.byref(trdms.cstruct), self.natm, self.count)
-        if nbytes == 0:
-            raise _lib.EvcontHipError("evc_workspace_bytes_batch: " + self.lib.evc_last_error().decode())
-        # zero-filled once: the cached factorisation of S_train in it is recognised by content (a recycled allocator
-        # block must not look like a hit)
-        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=d)
-        self.ws_bytes = nbytes
-        # (the library may attach a side stream to the workspace, include/evcont_hip.h evc_release_workspace)
-        self._ws_release = weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr())
-        self._ws_release.atexit = False
+        self._init_workspace()
         G = self.count
         # energies and gradients share one buffer: a caller that wants both on the host fetches them with ONE copy
         na = max(self.natm, 1)
@@ -572,11 +685,16 @@ class BatchedEvaluator:
         self.out = _lib.OutputsBatch(energy=p(self.energy), coeffs=p(self.coeffs), grad=p(self.grad),
                                      d_pred=p(self.d_pred), g_pred=p(self.g_pred), hmat=p(self.hmat))
 
-    def _sp(self) -> int:
-        return self.stream.cuda_stream if self.stream is not None else _stream_ptr(self.t.device)
+    _suffix = "_batch"
 
-    def synchronize(self) -> None:
-        (self.stream if self.stream is not None else torch.cuda.current_stream(self.t.device)).synchronize()
+    @property
+    def _lead(self) -> tuple:
+        return (self.count,)
+
+    @staticmethod
+    def _raise_if_nan(e):
+        if not np.all(np.isfinite(e)):
+            raise np.linalg.LinAlgError("generalised eigenproblem failed for at least one geometry of the batch")
 
     def phase_loewdin(self, aob: DeviceAOBatch, stream: Optional["torch.cuda.Stream"] = None) -> None:
         """Loewdin orthogonalisation of the batch alone (reads S and hcore only): the next ``enqueue`` of the SAME
@@ -611,8 +729,7 @@ class BatchedEvaluator:
         self.enqueue(aob)
         self.synchronize()
         e = self.energy[:, 0].cpu().numpy().copy()
-        if not np.all(np.isfinite(e)):
-            raise np.linalg.LinAlgError("generalised eigenproblem failed for at least one geometry of the batch")
+        self._raise_if_nan(e)
         return e, self.grad[:, : self.natm].cpu().numpy().copy()
 
     # -- phase API for the pair-sharded multi-GPU host (evcont_amd/distributed.py) -----------------
@@ -644,30 +761,11 @@ class BatchedEvaluator:
         self._primed = True
 
     # -- several roots of every geometry (evc_phase_gradient_roots_batch) -----------------------------------------
-    def _grow_workspace(self, nbytes: int) -> None:
-        """Enlarge the workspace to ``nbytes`` (never shrinks).  Geometries 0 .. count-1 keep their place and contents
-        (``ContinuationEvaluator._grow_workspace``); the rest is zero-filled."""
-        if nbytes <= self.ws_bytes:
-            return
-        st = self.stream if self.stream is not None else torch.cuda.current_stream(self.t.device)
-        self._ws_release()          # waits for a side-stream launch into the old workspace, drops its events
-        ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.t.device)
-        with torch.cuda.stream(st):
-            ws[: self.ws_bytes].copy_(self.ws)
-        st.synchronize()
-        self.ws, self.ws_bytes = ws, nbytes
-        self._ws_release = weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr())
-        self._ws_release.atexit = False
-
     def _host_coeffs(self, aob: DeviceAOBatch, nroots: int):
         """hermitian=False: H(R) of every geometry assembled on the device, the T x T pencils solved on the host as
-        ``ContinuationEvaluator._roots`` does; returns host E (G, nroots), C (G, nroots, T) and the device (G, T, T)
-        coefficient blocks the gradient call reads."""
-        from .ab_initio_eigenvector_continuation import _eig_nonhermitian, _select
-        if self.t.layout == _lib.LAYOUT_SYM8:
-            raise _lib.EvcontHipError("hermitian=False needs the training data in the layout the caller holds, not sym8")
-        if (self.t.row_offset, self.t.rows_local) != (0, self.t.rows_total):
-            raise _lib.EvcontHipError("hermitian=False needs the complete t-RDM on this device")
+        ``ContinuationEvaluator._host_coeffs`` does; returns host E (G, nroots), C (G, nroots, T) and the device
+        (G, T, T) coefficient blocks the gradient call reads."""
+        _check_nonhermitian(self.t)
         G, T, d = self.count, self.t.T, self.t.device
         if self.hmat is None:
             self.hmat = torch.zeros((G, T, T), dtype=F64, device=d)
@@ -681,8 +779,7 @@ class BatchedEvaluator:
         E = np.zeros((G, nroots))
         Cs = np.zeros((G, nroots, T))
         for g in range(G):
-            vals, vecs = _eig_nonhermitian(H[g], S, self.t.layout)
-            e, c = _select(vals, vecs, nroots, False)
+            e, c = _select(*_eig_nonhermitian(H[g], S, self.t.layout), nroots, False)
             E[g], Cs[g] = np.asarray(e, dtype=np.float64) + enuc[g], c
         blocks = np.zeros((G, T, T))
         blocks[:, :nroots] = Cs
@@ -698,44 +795,13 @@ class BatchedEvaluator:
         with ``return_density_matrices`` also ``D (G,P,N,N)`` and ``Gamma (G,P,N^4)``.  ``hermitian=False``: the host
         eig selection per geometry (not on sym8).  G * P <= 4096."""
         assert aob.count == self.count, "batch size is fixed at construction"
-        G, T, n = self.count, self.t.T, self.t.n
-        nroots = int(nroots)
-        if not 1 <= nroots <= T:
-            raise ValueError(f"nroots={nroots} out of range 1..{T}")
-        if pairs is None:
-            pairs = [(k, k) for k in range(nroots)]
-        P = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
-        npairs = P.shape[0]
-        nbytes = self.lib.evc_workspace_bytes_roots_batch(C.byref(self.t.cstruct), self.natm, G, npairs)
-        if nbytes == 0:
-            raise _lib.EvcontHipError("evc_workspace_bytes_roots_batch: " + self.lib.evc_last_error().decode())
-        self._grow_workspace(nbytes)
-        if hermitian:
-            self.enqueue(aob, nroots, energy_only=True)     # (checks the integrals' symmetry on the first call)
-            coeffs = self.coeffs
-        else:
-            E, Cs, coeffs = self._host_coeffs(aob, nroots)
-        d, want = self.t.device, bool(return_density_matrices)
-        grads = torch.zeros((npairs, G, max(self.natm, 1), 3), dtype=F64, device=d)
-        D = torch.zeros((npairs, G, n, n), dtype=F64, device=d) if want else None
-        Gm = torch.zeros((npairs, G, n ** 4), dtype=F64, device=d) if want else None
-        p = lambda t: (t.data_ptr() if t is not None else None)
-        out = _lib.OutputsRoots(grad=p(grads), d_pred=p(D), g_pred=p(Gm))
-        g = aob.cstruct()
-        rc = self.lib.evc_phase_gradient_roots_batch(C.byref(self.t.cstruct), C.byref(g), coeffs.data_ptr(), nroots,
-                                                     P.ctypes.data, npairs, C.byref(out),
-                                                     _ip1_flag(self.t, aob) & _lib.FLAG_IP1_S2KL, self.ws.data_ptr(),
-                                                     self.ws_bytes, self._sp())
-        check(rc, "evc_phase_gradient_roots_batch")
-        self.synchronize()        # (coeffs of the eig branch live until here)
-        if hermitian:
-            E = self.energy[:, :nroots].cpu().numpy().copy()
-            if not np.all(np.isfinite(E[:, 0])):
-                raise np.linalg.LinAlgError("generalised eigenproblem failed for at least one geometry of the batch")
-            Cs = self.coeffs[:, :nroots].cpu().numpy().copy()
+        want = bool(return_density_matrices)
+        # (the energy-only call checks the integrals' symmetry on the first call)
+        E, Cs, grads, D, Gm = self._gradient_roots(aob, nroots, pairs, want, want, hermitian)
         res = (E, Cs, grads[:, :, : self.natm].transpose(0, 1).cpu().numpy().copy())
         if want:
-            res += (D.transpose(0, 1).cpu().numpy().copy(), Gm.transpose(0, 1).cpu().numpy().copy())
+            res += (D.transpose(0, 1).cpu().numpy().copy(),
+                    Gm.transpose(0, 1).cpu().numpy().copy().reshape(self.count, Gm.shape[0], -1))
         return res
 
     def phase_gradient(self, aob: DeviceAOBatch, partial_rank: bool) -> None:
@@ -809,7 +875,7 @@ class PipelinedBatchedEvaluator:
         self._cs().synchronize()
 
 
-class ContinuationEvaluator:
+class ContinuationEvaluator(_EvaluatorBase):
     """Energy / energy+force of the continuation at one geometry per call
     (``get_energy_with_grad``, ``ab_initio_gradients_loewdin.py:308-379``)."""
 
@@ -829,13 +895,7 @@ class ContinuationEvaluator:
         self._primed = False
         self.lib = _lib.load()
         d, n, T = trdms.device, trdms.n, trdms.T
-        nbytes = self.lib.evc_workspace_bytes(C.byref(trdms.cstruct), self.natm)
-        if nbytes == 0:
-            raise _lib.EvcontHipError("evc_workspace_bytes: " + self.lib.evc_last_error().decode())
-        self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=d)   # (zero-filled: see BatchedEvaluator)
-        self.ws_bytes = nbytes
-        self._ws_release = weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr())
-        self._ws_release.atexit = False
+        self._init_workspace()
         self.energy = torch.zeros(T, dtype=F64, device=d)
         self.coeffs = torch.zeros((T, T), dtype=F64, device=d)
         self.grad = torch.zeros((max(self.natm, 1), 3), dtype=F64, device=d)
@@ -845,12 +905,6 @@ class ContinuationEvaluator:
         self.out = Outputs(energy=self.energy.data_ptr(), coeffs=self.coeffs.data_ptr(), grad=self.grad.data_ptr(),
                            d_pred=self.d_pred.data_ptr(),
                            g_pred=(self.g_pred.data_ptr() if want_two_rdm else None), hmat=self.hmat.data_ptr())
-
-    def _sp(self) -> int:
-        return self.stream.cuda_stream if self.stream is not None else _stream_ptr(self.t.device)
-
-    def synchronize(self) -> None:
-        (self.stream if self.stream is not None else torch.cuda.current_stream(self.t.device)).synchronize()
 
     # -- single-device fused path -------------------------------------------------------------
     def enqueue(self, ao: DeviceAO, nroots: int = 1, energy_only: bool = False) -> None:
@@ -929,23 +983,7 @@ class ContinuationEvaluator:
         branch; the T x T non-symmetric pencil goes to ``scipy.linalg.eig`` on the host, as in the reference (pair
         layouts: upper triangle filled from the lower one, ``|Im| < 1e-5`` filter, ``argmin``), and ITS 2-norm
         eigenvector -- real part, as the reference takes it -- defines the predicted RDMs and the gradient."""
-        import scipy.linalg
-        if self.t.layout == _lib.LAYOUT_SYM8:
-            raise _lib.EvcontHipError("hermitian=False needs the training data in the layout the caller holds, not sym8")
-        if (self.t.row_offset, self.t.rows_local) != (0, self.t.rows_total):
-            raise _lib.EvcontHipError("hermitian=False needs the complete t-RDM on this device")
-        rows = self.phase_hamiltonian(ao)
-        self.phase_solve(ao, rows, 1)
-        self.synchronize()
-        H = self.hmat.cpu().numpy().copy()
-        if self.t.layout in (5, 2):
-            iu = np.triu_indices(self.t.T)
-            H[iu] = H.T[iu]
-        vals, vecs = scipy.linalg.eig(H, self.t.S.cpu().numpy())
-        valid = np.abs(vals.imag) < 1.0e-5
-        k = int(np.argmin(vals[valid].real))
-        e = float(vals[valid][k].real)
-        vec = np.ascontiguousarray(vecs[:, valid][:, k].real, dtype=np.float64)
+        e, vec = _select(*self._host_eig(ao), 1, True)
         self.phase_set_coeffs(torch.from_numpy(vec).to(self.t.device))
         self.phase_gradient(ao, False)
         self.synchronize()
@@ -957,75 +995,29 @@ class ContinuationEvaluator:
             return e + ao.enuc, g, self.d_pred.cpu().numpy().copy(), self.g_pred.cpu().numpy().copy()
         return e + ao.enuc, g
 
+    def _host_eig(self, ao: DeviceAO):
+        """hermitian=False: H(R) assembled on the device as for the Hermitian branch, then the reference's ``eig``
+        branch on the host (``_eig_nonhermitian``)."""
+        _check_nonhermitian(self.t)
+        rows = self.phase_hamiltonian(ao)
+        self.phase_solve(ao, rows, 1)
+        self.synchronize()
+        return _eig_nonhermitian(self.hmat.cpu().numpy(), self.t.S.cpu().numpy(), self.t.layout)
+
     # -- several roots of one geometry (evc_phase_gradient_roots) ------------------------------------------
-    def _grow_workspace(self, nbytes: int) -> None:
-        """Enlarge the workspace to ``nbytes`` (never shrinks).  Slot 0 keeps its place and its contents (the cached
-        factorisation of S_train, the warm-start eigenvectors); the rest is zero-filled."""
-        if nbytes <= self.ws_bytes:
-            return
-        st = self.stream if self.stream is not None else torch.cuda.current_stream(self.t.device)
-        self._ws_release()          # waits for a side-stream launch into the old workspace, drops its events
-        ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.t.device)
-        with torch.cuda.stream(st):
-            ws[: self.ws_bytes].copy_(self.ws)
-        st.synchronize()
-        self.ws, self.ws_bytes = ws, nbytes
-        self._ws_release = weakref.finalize(self, self.lib.evc_release_workspace, self.ws.data_ptr())
-        self._ws_release.atexit = False
+    def _host_coeffs(self, ao: DeviceAO, nroots: int):
+        """hermitian=False: the reference's eig branch for every root (2-norm eigenvectors, real part, |Im| < 1e-5,
+        ascending); returns host E (nroots,), C (nroots, T) and the device copy of C the gradient call reads."""
+        e, c = _select(*self._host_eig(ao), nroots, False)
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        self._primed = False      # the workspace no longer holds a converged Hermitian solve
+        return np.asarray(e, dtype=np.float64) + ao.enuc, c, torch.from_numpy(c).to(self.t.device)
 
     def _roots(self, ao: DeviceAO, nroots: int, pairs, want_d: bool, want_g: bool, hermitian: bool):
         """Enqueue energies + the gradient slots of ``pairs``; returns host E, C and the device output tensors."""
-        T, n = self.t.T, self.t.n
-        nroots = int(nroots)
-        if not 1 <= nroots <= T:
-            raise ValueError(f"nroots={nroots} out of range 1..{T}")
-        if pairs is None:
-            pairs = [(k, k) for k in range(nroots)]
-        P = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
-        npairs = P.shape[0]
-        nbytes = self.lib.evc_workspace_bytes_roots(C.byref(self.t.cstruct), self.natm, npairs)
-        if nbytes == 0:
-            raise _lib.EvcontHipError("evc_workspace_bytes_roots: " + self.lib.evc_last_error().decode())
-        self._grow_workspace(nbytes)
         if hermitian:
-            _check_sym_first_call(self, ao)           # (with eri_ip1: the energy-only call below checks eri alone)
-            self.enqueue(ao, nroots, energy_only=True)
-            coeffs = self.coeffs                      # rows 0 .. nroots-1 as the solver wrote them
-        else:
-            # the reference's eig branch for every root: 2-norm eigenvectors, real part, |Im| < 1e-5, ascending
-            from .ab_initio_eigenvector_continuation import _eig_nonhermitian, _select
-            if self.t.layout == _lib.LAYOUT_SYM8:
-                raise _lib.EvcontHipError("hermitian=False needs the training data in the layout the caller holds, "
-                                          "not sym8")
-            if (self.t.row_offset, self.t.rows_local) != (0, self.t.rows_total):
-                raise _lib.EvcontHipError("hermitian=False needs the complete t-RDM on this device")
-            rows = self.phase_hamiltonian(ao)
-            self.phase_solve(ao, rows, 1)
-            self.synchronize()
-            vals, vecs = _eig_nonhermitian(self.hmat.cpu().numpy(), self.t.S.cpu().numpy(), self.t.layout)
-            e, c = _select(vals, vecs, nroots, False)
-            e = np.asarray(e, dtype=np.float64) + ao.enuc
-            c = np.ascontiguousarray(c, dtype=np.float64)
-            coeffs = torch.from_numpy(c).to(self.t.device)
-            self._primed = False      # the workspace no longer holds a converged Hermitian solve
-        d = self.t.device
-        grads = torch.zeros((npairs, max(self.natm, 1), 3), dtype=F64, device=d)
-        D = torch.zeros((npairs, n, n), dtype=F64, device=d) if want_d else None
-        G = torch.zeros((npairs, n, n, n, n), dtype=F64, device=d) if want_g else None
-        p = lambda t: (t.data_ptr() if t is not None else None)
-        out = _lib.OutputsRoots(grad=p(grads), d_pred=p(D), g_pred=p(G))
-        g = ao.cstruct()
-        rc = self.lib.evc_phase_gradient_roots(C.byref(self.t.cstruct), C.byref(g), coeffs.data_ptr(), nroots,
-                                               P.ctypes.data, npairs, C.byref(out),
-                                               _ip1_flag(self.t, ao) & _lib.FLAG_IP1_S2KL, self.ws.data_ptr(),
-                                               self.ws_bytes, self._sp())
-        check(rc, "evc_phase_gradient_roots")
-        self.synchronize()        # (coeffs of the eig branch live until here)
-        if hermitian:
-            e = self.energy[:nroots].cpu().numpy().copy()
-            self._raise_if_nan(e[0])
-            c = self.coeffs.reshape(-1)[: nroots * T].reshape(nroots, T).cpu().numpy().copy()
-        return e, c, grads, D, G
+            _check_sym_first_call(self, ao)           # (with eri_ip1: the energy-only call checks eri alone)
+        return self._gradient_roots(ao, nroots, pairs, want_d, want_g, hermitian)
 
     def energies_with_grads(self, ao: DeviceAO, nroots: int, pairs=None, return_density_matrices: bool = False,
                             hermitian: bool = True):
