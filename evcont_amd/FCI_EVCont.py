@@ -5,6 +5,8 @@ The FCI solve itself is host work outside the accelerated path; the integrals it
 ``evcont_amd.electron_integral_utils`` (four-index transform on the GPU).  ``cisolver`` is any object with
 PySCF's ``kernel(h1, h2, norb, nelec, nroots=)`` / ``trans_rdm12(bra, ket, norb, nelec)`` interface; the
 default is ``pyscf.fci.direct_spin0.FCI()`` when PySCF is importable and ``fci_small.SmallFCI`` otherwise.
+A solver that also has ``trans_rdm12_rows(bra, kets, norb, nelec) -> (ovlp, dm1, dm2)`` (``fci_device.DeviceFCI``: the
+sigma vector and the t-RDMs on the GPU, opt-in) is asked for the t-RDMs of a new state in that one call.
 """
 from __future__ import annotations
 
@@ -66,6 +68,11 @@ class FCI_EVCont_obj(TRDMContainer):
             self.ens.append(e_all[ind] + energy_nuc(mol))
             self.mol_index.append(mindex)
             T1 = len(self.fcivecs)
+            if hasattr(self.cisolver, "trans_rdm12_rows"):
+                # one bra against all stored states in one pass (fci_device.DeviceFCI)
+                ovlp, one, two = self.cisolver.trans_rdm12_rows(self.fcivecs[-1], self.fcivecs, n, mol.nelec)
+                self._append_state(ovlp, one, two)
+                continue
             ovlp = np.empty(T1)
             one = np.empty((T1, n, n))
             two = np.empty((T1, n, n, n, n))
@@ -79,3 +86,5 @@ class FCI_EVCont_obj(TRDMContainer):
         self._prune_arrays(keep_ids)
         self.fcivecs = [self.fcivecs[i] for i in keep_ids]
         self.ens = [self.ens[i] for i in keep_ids]
+        if hasattr(self.cisolver, "forget"):
+            self.cisolver.forget(self.fcivecs)     # device copies of the pruned vectors

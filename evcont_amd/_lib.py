@@ -122,6 +122,14 @@ SIGNATURES = {
     "evc_two_el_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_contract_nnA3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "evc_fci_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "evc_fci_excite": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "evc_fci_trdm_rows": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_void_p]),
+    "evc_fci_sigma": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_profile_begin": (C.c_int, [C.c_int]),
     "evc_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int)]),
@@ -133,6 +141,9 @@ SIGNATURES = {
 # stages of evc_profile_stage (include/evcont_hip.h EVC_PROF_*)
 PROF_STAGES = {"k5_rows": 0, "k8_cols": 1, "pair_transform": 2, "ip1": 3, "y2": 4, "unpack": 5, "loewdin": 6,
                "subspace": 7}
+# stages of the full-CI entry points (EVC_PROF_FCI_*): named by evc_profile_kernel, not timed by the bench hook
+FCI_PROF_STAGES = {"fci_excite": 8, "fci_trdm": 9, "fci_sigma": 10}
+FCI_DET_MAJOR, FCI_DET_MAJOR_T, FCI_ORB_MAJOR = 0, 1, 2
 
 _lib: Optional[C.CDLL] = None
 

@@ -1,0 +1,514 @@
+// Full-CI training states on the device (fci_small.py: SmallFCI._excite_all, .trans_rdm12, .contract):
+//   excite      D[pq](Ia,Ib) = sa c(Ja,Ib) + sb c(Ia,Jb)      signed gather through the string tables
+//   t-RDM       M = D~_bra . D_ket^T  (N^2 x dim x N^2)       split-K FP64 MFMA, partial tiles summed in a fixed order
+//   sigma       G = h2 . D            (N^2 x N^2 x dim)       FP64 MFMA over determinant tiles, then the signed gather of
+//               sigma = sum_pq E_pq (G[pq]/2 + h'_pq c)       G back through the tables
+// D is materialised in HBM in chunks (the caller's workspace), so that the MFMA kernels issue nothing but operand
+// loads and MFMAs and the gather work runs in launches of its own (FP64 MFMA blocks its SIMD's vector issue).
+//
+// String tables (fci_tables.py): tab[I * npad + pq] = +-(J + 1) with <I| a_p^+ a_q |J> = +-1, 0 where E_pq annihilates
+// every string into I; npad = N^2 rounded up to 16, the pad columns are 0.  One table per spin.
+//
+// Both matrix kernels contract operands stored [k][m] (m contiguous), so every MFMA fragment load is 16 consecutive
+// doubles: the t-RDM reads D determinant-major ([k][pq]), sigma reads h2^T [rs][pq] and D orbital-major ([rs][k]).
+#include "common.hpp"
+#include "kernels.hpp"
+
+namespace evc {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
+
+constexpr int kFciMaxOrb = 16;
+constexpr int kFciMinRows = 256;     // determinants per split-K block, at least
+constexpr int kFciMaxBlocks = 256;   // split-K blocks (= partial tiles per ket), at most
+
+static int fci_npad(int norb) { return (norb * norb + 15) / 16 * 16; }
+// The split of the determinants into blocks depends on the determinant count alone -- not on the workspace, not on the
+// number of kets -- so a row call and its single-pair calls sum the same partials in the same order.
+static int64_t fci_rows_per_block(int64_t dim) {
+    const int64_t r = align_up((size_t)ceil_div(dim, kFciMaxBlocks), 64);
+    return r < kFciMinRows ? kFciMinRows : r;
+}
+// sigma: row tiles per wave for nt = npad / 16 tiles
+static int fci_rt(int nt) { return (int)ceil_div(nt, ceil_div(nt, 4)); }
+
+// ---- excite ----------------------------------------------------------------------
+__device__ __forceinline__ double fci_excite_one(const int32_t *__restrict__ tab_a, const int32_t *__restrict__ tab_b,
+                                                 const double *__restrict__ c, int64_t nb, int npad, int64_t ia,
+                                                 int64_t ib, int pq) {
+    const int32_t ta = tab_a[ia * npad + pq], tb = tab_b[ib * npad + pq];
+    double v = 0.0;
+    if (ta != 0) {
+        const double x = c[(int64_t)(abs(ta) - 1) * nb + ib];
+        v = ta > 0 ? x : -x;
+    }
+    if (tb != 0) {
+        const double x = c[ia * nb + (abs(tb) - 1)];
+        v += tb > 0 ? x : -x;
+    }
+    return v;
+}
+
+// LAYOUT 0: D[kk * npad + pq]; 1: D[kk * npad + qp] (the bra side of the t-RDM product); rows kk with k0 + kk >= dim
+// and the pad columns are written as zeros.
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void fci_excite_det_kernel(const int32_t *__restrict__ tab_a,
+                                                             const int32_t *__restrict__ tab_b,
+                                                             const double *__restrict__ c, int norb, int64_t nb,
+                                                             int64_t dim, int64_t k0, int64_t nk, int npad,
+                                                             double *__restrict__ D) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= nk * npad) return;
+    const int64_t kk = idx / npad, k = k0 + kk;
+    const int pq = (int)(idx - kk * npad);
+    double v = 0.0;
+    if (k < dim) v = fci_excite_one(tab_a, tab_b, c, nb, npad, k / nb, k % nb, pq);
+    int col = pq;
+    if (LAYOUT == 1 && pq < norb * norb) col = (pq % norb) * norb + pq / norb;
+    D[kk * npad + col] = v;
+}
+
+// D[pq * ld + kk], pq < npad, kk < nk (nk <= ld)
+__global__ __launch_bounds__(256) void fci_excite_orb_kernel(const int32_t *__restrict__ tab_a,
+                                                             const int32_t *__restrict__ tab_b,
+                                                             const double *__restrict__ c, int64_t nb, int64_t dim,
+                                                             int64_t k0, int64_t nk, int npad, double *__restrict__ D,
+                                                             int64_t ld) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= nk * npad) return;
+    const int pq = (int)(idx / nk);
+    const int64_t kk = idx - (int64_t)pq * nk, k = k0 + kk;
+    double v = 0.0;
+    if (k < dim) v = fci_excite_one(tab_a, tab_b, c, nb, npad, k / nb, k % nb, pq);
+    D[(int64_t)pq * ld + kk] = v;
+}
+
+static int launch_excite(int layout, int norb, int64_t nb, int64_t dim, const int32_t *tab_a, const int32_t *tab_b,
+                         const double *c, int64_t k0, int64_t nk, double *D, int64_t ld, hipStream_t st) {
+    const int npad = fci_npad(norb);
+    const unsigned grid = (unsigned)ceil_div(nk * npad, 256);
+    if (layout == EVC_FCI_ORB_MAJOR) {
+        fci_excite_orb_kernel<<<grid, 256, 0, st>>>(tab_a, tab_b, c, nb, dim, k0, nk, npad, D, ld);
+        note_kernel(EVC_PROF_FCI_EXCITE, "fci_excite_orb_kernel");
+    } else if (layout == EVC_FCI_DET_MAJOR_T) {
+        fci_excite_det_kernel<1><<<grid, 256, 0, st>>>(tab_a, tab_b, c, norb, nb, dim, k0, nk, npad, D);
+        note_kernel(EVC_PROF_FCI_EXCITE, "fci_excite_det_kernel<1>");
+    } else {
+        fci_excite_det_kernel<0><<<grid, 256, 0, st>>>(tab_a, tab_b, c, norb, nb, dim, k0, nk, npad, D);
+        note_kernel(EVC_PROF_FCI_EXCITE, "fci_excite_det_kernel<0>");
+    }
+    EVC_LAUNCH_CHECK("fci_excite");
+    return 0;
+}
+
+// ---- t-RDM product ---------------------------------------------------------------
+// One workgroup per block of `rows` determinants: NBW x NBW waves, each with RT x RT tiles of the (npad, npad) product
+// A^T B over the block's rows, A = D~_bra rows, B = D_ket rows (RT * RT * 8 accumulator registers a lane: 72 at twelve
+// orbitals, where 3 x 3 waves hold 3 x 3 tiles each).  The waves of the first wave row also carry g1[rs] = sum_k bra[k] B[k][rs] on the B fragments they hold anyway (RT FP64 FMAs per RT*RT MFMAs), wave 0 the overlap.
+// Partials: Pm[blk][npad][npad], Pg[blk][npad], Po[blk].
+template <int RT, int NBW>
+__global__ __launch_bounds__(64 * NBW * NBW) void fci_trdm_kernel(
+    const double *__restrict__ A, const double *__restrict__ B, const double *__restrict__ bra,
+    const double *__restrict__ ket, int npad, int nq, int64_t rows, int64_t blk0, int64_t dim, int a_resident,
+    double *__restrict__ Pm, double *__restrict__ Pg, double *__restrict__ Po) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int nt = npad / 16;
+    // beyond RT * NBW tiles per edge the product is made in nq x nq quadrants, one per blockIdx.y
+    const int wr = (int)(blockIdx.y / nq) * NBW + wave / NBW, wc = (int)(blockIdx.y % nq) * NBW + wave % NBW;
+    const bool first = blockIdx.y == 0 && wave == 0;
+    const int64_t blk = blk0 + blockIdx.x;
+    A += (a_resident ? blk : (int64_t)blockIdx.x) * rows * npad;
+    B += (int64_t)blockIdx.x * rows * npad;
+    const int64_t kg0 = blk * rows;
+    bool rok[RT], cok[RT];
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+        rok[t] = wr * RT + t < nt;
+        cok[t] = wc * RT + t < nt;
+    }
+    d4 acc[RT][RT];
+    double g1[RT];
+    double ov = 0.0;
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+        g1[r] = 0.0;
+#pragma unroll
+        for (int c = 0; c < RT; ++c) acc[r][c] = (d4){0.0, 0.0, 0.0, 0.0};
+    }
+    const double *__restrict__ ap = A + (int64_t)l4 * npad + wr * RT * 16 + l15;
+    const double *__restrict__ bp = B + (int64_t)l4 * npad + wc * RT * 16 + l15;
+    const int64_t ksteps = rows / 4;
+    for (int64_t ks = 0; ks < ksteps; ++ks) {
+        double af[RT], bf[RT];
+#pragma unroll
+        for (int t = 0; t < RT; ++t) {
+            af[t] = rok[t] ? ap[ks * 4 * npad + t * 16] : 0.0;
+            bf[t] = cok[t] ? bp[ks * 4 * npad + t * 16] : 0.0;
+        }
+        if (wr == 0) {
+            const int64_t kg = kg0 + ks * 4 + l4;
+            const double cb = kg < dim ? bra[kg] : 0.0;
+#pragma unroll
+            for (int t = 0; t < RT; ++t) g1[t] = fma(cb, bf[t], g1[t]);
+            if (first) ov = fma(cb, kg < dim ? ket[kg] : 0.0, ov);
+        }
+#pragma unroll
+        for (int r = 0; r < RT; ++r)
+#pragma unroll
+            for (int c = 0; c < RT; ++c) acc[r][c] = mfma_f64(af[r], bf[c], acc[r][c]);
+    }
+    double *__restrict__ pm = Pm + blk * npad * npad;
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+        for (int c = 0; c < RT; ++c)
+            if (rok[r] && cok[c]) {
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    pm[(int64_t)((wr * RT + r) * 16 + l4 + 4 * v) * npad + (wc * RT + c) * 16 + l15] = acc[r][c][v];
+            }
+    if (wr == 0) {
+#pragma unroll
+        for (int t = 0; t < RT; ++t) {
+            double v = g1[t];
+            v += __shfl_xor(v, 16);
+            v += __shfl_xor(v, 32);
+            if (cok[t] && l4 == 0) Pg[blk * npad + (wc * RT + t) * 16 + l15] = v;
+        }
+        if (first) {
+            double v = ov;
+            v += __shfl_xor(v, 16);
+            v += __shfl_xor(v, 32);
+            if (lane == 0) Po[blk] = v;
+        }
+    }
+}
+
+// g1[pq] = sum over the blocks in order; dm1[q][p] = g1[p][q]; thread n2: the overlap
+__global__ __launch_bounds__(256) void fci_trdm_reduce1_kernel(const double *__restrict__ Pg,
+                                                               const double *__restrict__ Po, int norb, int npad,
+                                                               int64_t nblk, double *__restrict__ g1,
+                                                               double *__restrict__ dm1, double *__restrict__ ovlp) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int n2 = norb * norb;
+    if (t > n2) return;
+    double s = 0.0;
+    if (t == n2) {
+        for (int64_t b = 0; b < nblk; ++b) s += Po[b];
+        *ovlp = s;
+        return;
+    }
+    for (int64_t b = 0; b < nblk; ++b) s += Pg[b * npad + t];
+    g1[t] = s;
+    dm1[(t % norb) * norb + t / norb] = s;
+}
+
+// dm2[p,q,r,s] = sum_blocks M[pq,rs] - delta_qr g1[p,s]
+__global__ __launch_bounds__(256) void fci_trdm_reduce2_kernel(const double *__restrict__ Pm,
+                                                               const double *__restrict__ g1, int norb, int npad,
+                                                               int64_t nblk, double *__restrict__ dm2) {
+    const int n2 = norb * norb;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n2 * n2) return;
+    const int pq = idx / n2, rs = idx - pq * n2;
+    const double *__restrict__ src = Pm + (int64_t)pq * npad + rs;
+    double m = 0.0;
+    for (int64_t b = 0; b < nblk; ++b) m += src[b * npad * npad];
+    const int p = pq / norb, q = pq % norb, r = rs / norb, s = rs % norb;
+    dm2[idx] = q == r ? m - g1[p * norb + s] : m;
+}
+
+struct TrdmLaunch {
+    const double *A, *B, *bra, *ket;
+    int npad, nq;
+    int64_t rows, blk0, nblocks, dim;
+    int a_resident;
+    double *Pm, *Pg, *Po;
+};
+template <int RT, int NBW>
+static void launch_trdm_t(const TrdmLaunch &a, hipStream_t st) {
+    fci_trdm_kernel<RT, NBW><<<dim3((unsigned)a.nblocks, a.nq * a.nq), 64 * NBW * NBW, 0, st>>>(
+        a.A, a.B, a.bra, a.ket, a.npad, a.nq, a.rows, a.blk0, a.dim, a.a_resident, a.Pm, a.Pg, a.Po);
+}
+// tiles per wave edge, waves per workgroup edge, quadrants per edge for nt tiles per edge
+static void fci_trdm_config(int nt, int &rt, int &nbw, int &nq) {
+    nq = 1;
+    if (nt <= 4) rt = nt, nbw = 1;
+    else if (nt <= 6) rt = 3, nbw = 2;
+    else if (nt <= 8) rt = 4, nbw = 2;
+    else if (nt == 9) rt = 3, nbw = 3;
+    else if (nt <= 12) rt = 3, nbw = 2, nq = 2;
+    else rt = 4, nbw = 2, nq = 2;
+}
+static void launch_trdm(int rt, int nbw, const TrdmLaunch &a, hipStream_t st) {
+    switch (rt * 10 + nbw) {
+        case 11: launch_trdm_t<1, 1>(a, st); break;
+        case 21: launch_trdm_t<2, 1>(a, st); break;
+        case 31: launch_trdm_t<3, 1>(a, st); break;
+        case 41: launch_trdm_t<4, 1>(a, st); break;
+        case 32: launch_trdm_t<3, 2>(a, st); break;
+        case 42: launch_trdm_t<4, 2>(a, st); break;
+        default: launch_trdm_t<3, 3>(a, st); break;
+    }
+}
+
+// ---- sigma -----------------------------------------------------------------------
+// hp[pq] = h1[pq] - 1/2 sum_r (pr|rq); h2T[rs * npad + pq] = h2[pq][rs], zero padded
+__global__ __launch_bounds__(256) void fci_sigma_prep_kernel(const double *__restrict__ h1,
+                                                             const double *__restrict__ h2, int norb, int npad,
+                                                             double *__restrict__ hp, double *__restrict__ h2T) {
+    const int n2 = norb * norb;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= npad * npad) return;
+    const int rs = idx / npad, pq = idx - rs * npad;
+    h2T[idx] = (rs < n2 && pq < n2) ? h2[(int64_t)pq * n2 + rs] : 0.0;
+    if (rs == 0) {
+        double v = 0.0;
+        if (pq < n2) {
+            const int p = pq / norb, q = pq % norb;
+            double s = 0.0;
+            for (int r = 0; r < norb; ++r) s += h2[(((int64_t)p * norb + r) * norb + r) * norb + q];
+            v = h1[pq] - 0.5 * s;
+        }
+        hp[pq] = v;
+    }
+}
+
+// G[pq][k0 + k] = sum_rs h2T[rs][pq] D[rs][k]: a wave owns RT row tiles x 4 determinant tiles; consecutive waves share
+// the determinant tiles (their D fragments meet in the cache).
+template <int RT>
+__global__ __launch_bounds__(256) void fci_sigma_gemm_kernel(const double *__restrict__ h2T,
+                                                             const double *__restrict__ D, int64_t ldd, int npad,
+                                                             int nbw, int64_t njb, double *__restrict__ G, int64_t ldg) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int nt = npad / 16;
+    const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
+    const int rb = (int)(gw % nbw);
+    const int64_t jb = gw / nbw;
+    if (jb >= njb) return;
+    bool rok[RT];
+#pragma unroll
+    for (int t = 0; t < RT; ++t) rok[t] = rb * RT + t < nt;
+    d4 acc[RT][4];
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = (d4){0.0, 0.0, 0.0, 0.0};
+    const double *__restrict__ ap = h2T + (int64_t)l4 * npad + rb * RT * 16 + l15;
+    const double *__restrict__ bp = D + (int64_t)l4 * ldd + jb * 64 + l15;
+    for (int ks = 0; ks < npad / 4; ++ks) {
+        double af[RT], bf[4];
+#pragma unroll
+        for (int t = 0; t < RT; ++t) af[t] = rok[t] ? ap[(int64_t)ks * 4 * npad + t * 16] : 0.0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) bf[t] = bp[(int64_t)ks * 4 * ldd + t * 16];
+#pragma unroll
+        for (int r = 0; r < RT; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[r][c] = mfma_f64(af[r], bf[c], acc[r][c]);
+    }
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+        if (rok[r]) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    G[(int64_t)((rb * RT + r) * 16 + l4 + 4 * v) * ldg + jb * 64 + c * 16 + l15] = acc[r][c][v];
+        }
+}
+
+template <int RT>
+static void launch_sigma_gemm_t(const double *h2T, const double *D, int64_t ldd, int npad, int nbw, int64_t njb,
+                                double *G, int64_t ldg, hipStream_t st) {
+    fci_sigma_gemm_kernel<RT><<<(unsigned)ceil_div(njb * nbw, 4), 256, 0, st>>>(h2T, D, ldd, npad, nbw, njb, G, ldg);
+}
+
+// sigma(I) = sum_pq [ sa X_pq(Ja,Ib) + sb X_pq(Ia,Jb) ],  X_pq = G[pq]/2 + h'_pq c; one thread per determinant, pq in
+// order
+__global__ __launch_bounds__(256) void fci_sigma_gather_kernel(const int32_t *__restrict__ tab_a,
+                                                               const int32_t *__restrict__ tab_b,
+                                                               const double *__restrict__ c,
+                                                               const double *__restrict__ G, int64_t ldg,
+                                                               const double *__restrict__ hp, int norb, int npad,
+                                                               int64_t nb, int64_t dim, double *__restrict__ sigma) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= dim) return;
+    const int64_t ia = k / nb, ib = k % nb;
+    const int n2 = norb * norb;
+    double s = 0.0;
+    for (int pq = 0; pq < n2; ++pq) {
+        const int32_t ta = tab_a[ia * npad + pq], tb = tab_b[ib * npad + pq];
+        const double h = hp[pq];
+        if (ta != 0) {
+            const int64_t j = (int64_t)(abs(ta) - 1) * nb + ib;
+            const double x = 0.5 * G[(int64_t)pq * ldg + j] + h * c[j];
+            s += ta > 0 ? x : -x;
+        }
+        if (tb != 0) {
+            const int64_t j = ia * nb + (abs(tb) - 1);
+            const double x = 0.5 * G[(int64_t)pq * ldg + j] + h * c[j];
+            s += tb > 0 ? x : -x;
+        }
+    }
+    sigma[k] = s;
+}
+
+// ---- workspace layouts ------------------------------------------------------------
+struct FciShape {
+    int norb, npad, nt, rt, nbw;
+    int64_t na, nb, dim, rows, nblk, ldg;
+    size_t trdm_fixed, trdm_block, sigma_fixed, sigma_col;   // bytes
+};
+static int fci_shape(const char *who, int norb, int64_t na, int64_t nb, FciShape &s) {
+    EVC_REQUIRE(norb >= 1 && norb <= kFciMaxOrb, "%s: norb=%d, supported 1 ... %d", who, norb, kFciMaxOrb);
+    EVC_REQUIRE(na >= 1 && nb >= 1 && na <= 12870 && nb <= 12870, "%s: na=%lld nb=%lld strings (1 ... 12870 each)", who,
+                (long long)na, (long long)nb);
+    s.norb = norb;
+    s.npad = fci_npad(norb);
+    s.nt = s.npad / 16;
+    s.rt = fci_rt(s.nt);
+    s.nbw = (int)ceil_div(s.nt, s.rt);
+    s.na = na;
+    s.nb = nb;
+    s.dim = na * nb;
+    s.rows = fci_rows_per_block(s.dim);
+    s.nblk = ceil_div(s.dim, s.rows);
+    s.ldg = (int64_t)align_up((size_t)s.dim, 64);
+    // t-RDM: Pm, Pg, Po, g1 | D~_bra blocks | D_ket blocks
+    s.trdm_fixed = align_up(((size_t)s.nblk * ((size_t)s.npad * s.npad + s.npad + 1) + s.npad) * 8, 256);
+    s.trdm_block = (size_t)s.rows * s.npad * 8;
+    // sigma: h2T, hp | G (npad, ldg) | D chunk (npad, columns)
+    s.sigma_fixed = align_up(((size_t)s.npad * s.npad + s.npad) * 8, 256) + (size_t)s.npad * s.ldg * 8;
+    s.sigma_col = (size_t)s.npad * 8;
+    return 0;
+}
+
+}  // namespace evc
+
+using namespace evc;
+
+extern "C" size_t evc_fci_workspace_bytes(int norb, int64_t na, int64_t nb, int minimal) {
+    FciShape s;
+    if (fci_shape("evc_fci_workspace_bytes", norb, na, nb, s)) return 0;
+    const size_t t = s.trdm_fixed + s.trdm_block * (size_t)(minimal ? 2 : 2 * s.nblk);
+    const size_t g = s.sigma_fixed + s.sigma_col * (size_t)(minimal ? 64 : s.ldg);
+    return t > g ? t : g;
+}
+
+extern "C" int evc_fci_excite(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
+                              const double *c, int64_t k0, int64_t nk, int layout, double *D, int64_t ld,
+                              void *stream) {
+    FciShape s;
+    if (int rc = fci_shape("evc_fci_excite", norb, na, nb, s)) return rc;
+    EVC_REQUIRE(tab_a && tab_b && c && D, "evc_fci_excite: null pointer");
+    EVC_REQUIRE(layout == EVC_FCI_DET_MAJOR || layout == EVC_FCI_DET_MAJOR_T || layout == EVC_FCI_ORB_MAJOR,
+                "evc_fci_excite: layout=%d", layout);
+    EVC_REQUIRE(k0 >= 0 && nk >= 1 && nk * s.npad < ((int64_t)1 << 38), "evc_fci_excite: k0=%lld nk=%lld", (long long)k0,
+                (long long)nk);
+    EVC_REQUIRE(layout == EVC_FCI_ORB_MAJOR ? ld >= nk : ld == s.npad, "evc_fci_excite: ld=%lld (layout %d, nk=%lld)",
+                (long long)ld, layout, (long long)nk);
+    return launch_excite(layout, norb, nb, s.dim, tab_a, tab_b, c, k0, nk, D, ld, as_stream(stream));
+}
+
+extern "C" int evc_fci_trdm_rows(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
+                                 const double *bra, const double *const *kets, int nkets, double *ovlp, double *dm1,
+                                 double *dm2, void *ws, size_t ws_bytes, void *stream) {
+    FciShape s;
+    if (int rc = fci_shape("evc_fci_trdm_rows", norb, na, nb, s)) return rc;
+    EVC_REQUIRE(tab_a && tab_b && bra && kets && ovlp && dm1 && dm2 && ws, "evc_fci_trdm_rows: null pointer");
+    EVC_REQUIRE(nkets >= 1 && nkets <= 4096, "evc_fci_trdm_rows: nkets=%d (1 ... 4096)", nkets);
+    for (int i = 0; i < nkets; ++i) EVC_REQUIRE(kets[i], "evc_fci_trdm_rows: kets[%d] is null", i);
+    EVC_REQUIRE(aligned16(ws), "evc_fci_trdm_rows: workspace not 16-byte aligned");
+    const size_t need = s.trdm_fixed + 2 * s.trdm_block;
+    EVC_REQUIRE(ws_bytes >= need, "evc_fci_trdm_rows: workspace of %zu bytes, at least %zu needed for %lld determinants",
+                ws_bytes, need, (long long)s.dim);
+    hipStream_t st = as_stream(stream);
+    clear_fci_kernels(EVC_PROF_FCI_TRDM);
+    const int64_t nfit = (int64_t)((ws_bytes - s.trdm_fixed) / s.trdm_block);
+    const bool resident = nfit >= s.nblk + 1;   // D~_bra whole: formed once for all the kets
+    const int64_t cb = resident ? (nfit - s.nblk < s.nblk ? nfit - s.nblk : s.nblk) : nfit / 2;
+    double *Pm = static_cast<double *>(ws);
+    double *Pg = Pm + s.nblk * s.npad * s.npad;
+    double *Po = Pg + s.nblk * s.npad;
+    double *g1 = Po + s.nblk;
+    double *Dbra = reinterpret_cast<double *>(static_cast<char *>(ws) + s.trdm_fixed);
+    double *Dket = Dbra + (resident ? s.nblk : cb) * s.rows * s.npad;
+    const int n2 = norb * norb;
+    int trt, tnbw, nq;
+    fci_trdm_config(s.nt, trt, tnbw, nq);
+    if (resident)
+        if (int rc = launch_excite(EVC_FCI_DET_MAJOR_T, norb, nb, s.dim, tab_a, tab_b, bra, 0, s.nblk * s.rows, Dbra,
+                                   s.npad, st))
+            return rc;
+    for (int i = 0; i < nkets; ++i) {
+        for (int64_t b0 = 0; b0 < s.nblk; b0 += cb) {
+            const int64_t nbk = s.nblk - b0 < cb ? s.nblk - b0 : cb;
+            if (!resident)
+                if (int rc = launch_excite(EVC_FCI_DET_MAJOR_T, norb, nb, s.dim, tab_a, tab_b, bra, b0 * s.rows,
+                                           nbk * s.rows, Dbra, s.npad, st))
+                    return rc;
+            if (int rc = launch_excite(EVC_FCI_DET_MAJOR, norb, nb, s.dim, tab_a, tab_b, kets[i], b0 * s.rows,
+                                       nbk * s.rows, Dket, s.npad, st))
+                return rc;
+            const TrdmLaunch a = {Dbra, Dket, bra, kets[i], s.npad, nq, s.rows, b0, nbk, s.dim, resident ? 1 : 0, Pm, Pg, Po};
+            launch_trdm(trt, tnbw, a, st);
+            EVC_LAUNCH_CHECK("fci_trdm_kernel");
+        }
+        fci_trdm_reduce1_kernel<<<(unsigned)ceil_div(n2 + 1, 256), 256, 0, st>>>(
+            Pg, Po, norb, s.npad, s.nblk, g1, dm1 + (int64_t)i * n2, ovlp + i);
+        EVC_LAUNCH_CHECK("fci_trdm_reduce1_kernel");
+        fci_trdm_reduce2_kernel<<<(unsigned)ceil_div((int64_t)n2 * n2, 256), 256, 0, st>>>(
+            Pm, g1, norb, s.npad, s.nblk, dm2 + (int64_t)i * n2 * n2);
+        EVC_LAUNCH_CHECK("fci_trdm_reduce2_kernel");
+    }
+    note_kernel(EVC_PROF_FCI_TRDM, "fci_trdm_kernel<%d,%d> quadrants=%d blocks=%lld bra_resident=%d", trt, tnbw, nq * nq,
+                (long long)s.nblk, resident ? 1 : 0);
+    return 0;
+}
+
+extern "C" int evc_fci_sigma(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
+                             const double *h1, const double *h2, const double *c, double *sigma, void *ws,
+                             size_t ws_bytes, void *stream) {
+    FciShape s;
+    if (int rc = fci_shape("evc_fci_sigma", norb, na, nb, s)) return rc;
+    EVC_REQUIRE(tab_a && tab_b && h1 && h2 && c && sigma && ws, "evc_fci_sigma: null pointer");
+    EVC_REQUIRE(c != sigma, "evc_fci_sigma: sigma must not alias c");
+    EVC_REQUIRE(aligned16(ws), "evc_fci_sigma: workspace not 16-byte aligned");
+    const size_t need = s.sigma_fixed + 64 * s.sigma_col;
+    EVC_REQUIRE(ws_bytes >= need, "evc_fci_sigma: workspace of %zu bytes, at least %zu needed for %lld determinants",
+                ws_bytes, need, (long long)s.dim);
+    hipStream_t st = as_stream(stream);
+    clear_fci_kernels(EVC_PROF_FCI_SIGMA);
+    int64_t cols = (int64_t)((ws_bytes - s.sigma_fixed) / s.sigma_col) / 64 * 64;
+    if (cols > s.ldg) cols = s.ldg;
+    double *h2T = static_cast<double *>(ws);
+    double *hp = h2T + (int64_t)s.npad * s.npad;
+    double *G = reinterpret_cast<double *>(static_cast<char *>(ws) + align_up(((size_t)s.npad * s.npad + s.npad) * 8, 256));
+    double *D = G + (int64_t)s.npad * s.ldg;
+    fci_sigma_prep_kernel<<<(unsigned)ceil_div(s.npad * s.npad, 256), 256, 0, st>>>(h1, h2, norb, s.npad, hp, h2T);
+    EVC_LAUNCH_CHECK("fci_sigma_prep_kernel");
+    for (int64_t k0 = 0; k0 < s.ldg; k0 += cols) {
+        const int64_t nk = s.ldg - k0 < cols ? s.ldg - k0 : cols;   // a multiple of 64
+        if (int rc = launch_excite(EVC_FCI_ORB_MAJOR, norb, nb, s.dim, tab_a, tab_b, c, k0, nk, D, cols, st)) return rc;
+        switch (s.rt) {
+            case 1: launch_sigma_gemm_t<1>(h2T, D, cols, s.npad, s.nbw, nk / 64, G + k0, s.ldg, st); break;
+            case 2: launch_sigma_gemm_t<2>(h2T, D, cols, s.npad, s.nbw, nk / 64, G + k0, s.ldg, st); break;
+            case 3: launch_sigma_gemm_t<3>(h2T, D, cols, s.npad, s.nbw, nk / 64, G + k0, s.ldg, st); break;
+            default: launch_sigma_gemm_t<4>(h2T, D, cols, s.npad, s.nbw, nk / 64, G + k0, s.ldg, st); break;
+        }
+        EVC_LAUNCH_CHECK("fci_sigma_gemm_kernel");
+    }
+    fci_sigma_gather_kernel<<<(unsigned)ceil_div(s.dim, 256), 256, 0, st>>>(tab_a, tab_b, c, G, s.ldg, hp, norb, s.npad,
+                                                                            nb, s.dim, sigma);
+    EVC_LAUNCH_CHECK("fci_sigma_gather_kernel");
+    note_kernel(EVC_PROF_FCI_SIGMA, "fci_sigma_gemm_kernel<%d> chunk=%lld + fci_sigma_gather_kernel", s.rt,
+                (long long)cols);
+    return 0;
+}

@@ -29,7 +29,7 @@ void set_error(const char *fmt, ...) {
 // recorded on the launch stream right before/after the kernel, so the figure is the kernel's own
 // duration inside the real per-geometry DAG.  Process-wide, off by default.
 // Stages: EVC_PROF_* of include/evcont_hip.h.
-constexpr int kProfStages = 8;
+constexpr int kProfStages = 11;
 static char g_kernel_ran[kProfStages][96];
 void note_kernel(int stage, const char *fmt, ...) {
     if (stage < 0 || stage >= kProfStages) return;
@@ -44,6 +44,8 @@ constexpr unsigned kStagesHamiltonian =
     (1u << EVC_PROF_LOEWDIN) | (1u << EVC_PROF_PAIR_TRANSFORM) | (1u << EVC_PROF_ROWS) | (1u << EVC_PROF_UNPACK);
 constexpr unsigned kStagesGradient = (1u << EVC_PROF_COLS) | (1u << EVC_PROF_UNPACK) | (1u << EVC_PROF_Y2) |
                                      (1u << EVC_PROF_PAIR_TRANSFORM) | (1u << EVC_PROF_IP1);
+static void clear_kernels(unsigned mask);
+void clear_fci_kernels(int stage) { clear_kernels((1u << EVC_PROF_FCI_EXCITE) | (1u << stage)); }
 static void clear_kernels(unsigned mask) {
     for (int s = 0; s < kProfStages; ++s)
         if (mask >> s & 1u) g_kernel_ran[s][0] = '\0';

@@ -1,0 +1,221 @@
+"""``DeviceFCI``: the small determinant full-CI solver of ``fci_small.SmallFCI`` with its two heavy operations on the
+GPU (``csrc/fci.hip``): the sigma vector ``H c`` and the transition RDMs.  Same calls, same conventions:
+
+    e, ci = solver.kernel(h1, h2, norb, nelec, nroots=k)
+    dm1, dm2 = solver.trans_rdm12(cibra, ciket, norb, nelec)       # dm1[p,q] = <q^+ p>, dm2[p,q,r,s] = <p^+ r^+ s q>
+
+plus ``trans_rdm12_rows(bra, kets, norb, nelec)``: one bra against all kets in one pass, which is what
+``FCI_EVCont_obj.append_to_rdms`` needs for a new training state.  Opt in with
+``FCI_EVCont_obj(cisolver=DeviceFCI(), cibasis="OAO")``.
+
+Limits: ``norb <= 16``, real CI vectors, any ``(n_alpha, n_beta)``.  The eigensolver iteration of ``kernel`` stays on the
+host (``scipy.sparse.linalg.eigsh``); every matrix-vector product it asks for is a device sigma vector.  There is no host
+fallback: without the library or a device every call raises ``EvcontHipError``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from scipy.sparse.linalg import LinearOperator, eigsh
+
+from . import _lib
+from ._lib import EvcontHipError, check
+from .fci_tables import MAX_ORB, packed_table
+
+F64 = torch.float64
+
+
+def _nelec(nelec) -> Tuple[int, int]:
+    if isinstance(nelec, (int, np.integer)):
+        return (int(nelec) + 1) // 2, int(nelec) // 2
+    return int(nelec[0]), int(nelec[1])
+
+
+class DeviceFCI:
+    """``workspace_bytes=None`` grants what keeps every intermediate resident (``evc_fci_workspace_bytes``: two
+    ``dim x npad`` excitation arrays and the split-K partials; 2.1 GB at (12, (6, 6))); a smaller grant makes the
+    library work in chunks of determinants, with the same results bit for bit."""
+
+    def __init__(self, device=None, tol: float = 1e-13, workspace_bytes: Optional[int] = None, dense_limit: int = 1500):
+        self.tol = tol
+        self.dense_limit = dense_limit
+        self.workspace_bytes = workspace_bytes
+        self.converged = True
+        self._device_arg = device
+        self._device = None
+        self._tables = {}
+        self._ws = None
+        self._vecs = {}        # id(host array) -> (host array, device tensor): CI vectors already uploaded
+
+    # ---- plumbing ----------------------------------------------------------------
+    def _dev(self) -> torch.device:
+        if self._device is None:
+            _lib.load()
+            if not torch.cuda.is_available():
+                raise EvcontHipError("DeviceFCI needs a HIP device (evcont_amd has no CPU fallback; "
+                                     "fci_small.SmallFCI is the host solver)")
+            self._device = torch.device(self._device_arg if self._device_arg is not None else "cuda:0")
+        return self._device
+
+    def _check_shape(self, norb: int, nelec: Tuple[int, int]) -> None:
+        if not 1 <= norb <= MAX_ORB:
+            raise EvcontHipError(f"DeviceFCI: norb={norb}, supported 1 ... {MAX_ORB}")
+        if not (0 <= nelec[0] <= norb and 0 <= nelec[1] <= norb):
+            raise EvcontHipError(f"DeviceFCI: nelec={nelec} for {norb} orbitals")
+
+    def _setup(self, norb: int, nelec: Tuple[int, int]):
+        """Tables on the device and a workspace the library accepts; every limit is checked before any launch."""
+        self._check_shape(norb, nelec)
+        lib = _lib.load()
+        key = (norb, nelec)
+        if key not in self._tables:
+            ta = packed_table(norb, nelec[0])
+            tb = ta if nelec[1] == nelec[0] else packed_table(norb, nelec[1])
+            na, nb = ta.shape[0], tb.shape[0]
+            least = lib.evc_fci_workspace_bytes(norb, na, nb, 1)
+            full = lib.evc_fci_workspace_bytes(norb, na, nb, 0)
+            if least == 0 or full == 0:
+                check(-1, "evc_fci_workspace_bytes")
+            grant = full if self.workspace_bytes is None else int(self.workspace_bytes)
+            if grant < least:
+                raise EvcontHipError(f"DeviceFCI: workspace_bytes={grant}, but {na * nb} determinants of {norb} orbitals "
+                                     f"need at least {least} bytes ({full} to keep everything resident)")
+            dev = self._dev()
+            dta = torch.from_numpy(ta).to(dev)
+            dtb = dta if tb is ta else torch.from_numpy(tb).to(dev)
+            self._tables[key] = (dta, dtb, na, nb, min(grant, full))
+        dta, dtb, na, nb, grant = self._tables[key]
+        if self._ws is None or self._ws.numel() < grant:
+            self._ws = None
+            self._ws = torch.empty(grant, dtype=torch.uint8, device=self._dev())
+        return lib, dta, dtb, na, nb, grant
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self._dev()).cuda_stream
+
+    def _upload(self, v, na: int, nb: int, cache: bool) -> torch.Tensor:
+        if torch.is_tensor(v):
+            t = v.to(self._dev(), F64).contiguous()
+        else:
+            if np.iscomplexobj(v):
+                raise EvcontHipError("DeviceFCI: complex CI vectors are not supported")
+            hit = self._vecs.get(id(v))
+            if hit is not None and hit[0] is v:
+                return hit[1]
+            t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(self._dev())
+            if cache:
+                self._vecs[id(v)] = (v, t)
+        if t.numel() != na * nb:
+            raise EvcontHipError(f"DeviceFCI: CI vector of {t.numel()} elements, expected {na} x {nb}")
+        return t
+
+    def forget(self, keep: Sequence = ()) -> None:
+        """Drop the device copies of CI vectors, except those of the host arrays in ``keep`` (after pruning a
+        container: ``solver.forget(cont.fcivecs)``)."""
+        ids = {id(v) for v in keep}
+        self._vecs = {k: hv for k, hv in self._vecs.items() if k in ids}
+
+    # ---- the SmallFCI interface --------------------------------------------------
+    def contract(self, h1, h2, c, norb, nelec):
+        """sigma = H c, shape ``(na, nb)`` (``SmallFCI.contract``)."""
+        nelec = _nelec(nelec)
+        lib, dta, dtb, na, nb, grant = self._setup(norb, nelec)
+        dev = self._dev()
+        dh1 = torch.from_numpy(np.ascontiguousarray(h1, dtype=np.float64).reshape(norb, norb)).to(dev)
+        dh2 = torch.from_numpy(np.ascontiguousarray(h2, dtype=np.float64).reshape(norb ** 4)).to(dev)
+        return self._sigma(lib, dta, dtb, na, nb, grant, norb, dh1, dh2,
+                           self._upload(c, na, nb, cache=False)).cpu().numpy().reshape(na, nb)
+
+    def _sigma(self, lib, dta, dtb, na, nb, grant, norb, dh1, dh2, dc) -> torch.Tensor:
+        out = torch.empty(na * nb, dtype=F64, device=dc.device)
+        check(lib.evc_fci_sigma(norb, na, nb, dta.data_ptr(), dtb.data_ptr(), dh1.data_ptr(), dh2.data_ptr(),
+                                dc.data_ptr(), out.data_ptr(), self._ws.data_ptr(), grant, self._stream()),
+              "evc_fci_sigma")
+        return out
+
+    def kernel(self, h1, h2, norb, nelec, nroots: int = 1, **_):
+        """Lowest ``nroots`` eigenpairs; scalars/array for ``nroots == 1``, lists otherwise; sign convention of
+        ``SmallFCI.kernel`` (largest-magnitude coefficient positive).  Up to ``dense_limit`` determinants H is built
+        column by column from device sigma vectors and diagonalised densely, beyond that Lanczos (eigsh) runs over
+        them -- the same split as ``SmallFCI``."""
+        nelec = _nelec(nelec)
+        lib, dta, dtb, na, nb, grant = self._setup(norb, nelec)
+        dev = self._dev()
+        dim = na * nb
+        dh1 = torch.from_numpy(np.ascontiguousarray(h1, dtype=np.float64).reshape(norb, norb)).to(dev)
+        dh2 = torch.from_numpy(np.ascontiguousarray(h2, dtype=np.float64).reshape(norb ** 4)).to(dev)
+
+        def mv(v):
+            dc = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64).reshape(-1)).to(dev)
+            return self._sigma(lib, dta, dtb, na, nb, grant, norb, dh1, dh2, dc).cpu().numpy()
+
+        if dim <= self.dense_limit:
+            H = torch.empty((dim, dim), dtype=F64, device=dev)
+            eye = torch.zeros(dim, dtype=F64, device=dev)
+            for k in range(dim):
+                eye[k] = 1.0
+                H[k] = self._sigma(lib, dta, dtb, na, nb, grant, norb, dh1, dh2, eye)     # column k of H
+                eye[k] = 0.0
+            H = H.cpu().numpy()
+            w, v = np.linalg.eigh(0.5 * (H + H.T))
+        else:
+            op = LinearOperator((dim, dim), matvec=mv, dtype=np.float64)
+            rng = np.random.default_rng(0)
+            w, v = eigsh(op, k=max(nroots, 1), which="SA", tol=self.tol, v0=rng.standard_normal(dim),
+                         ncv=max(20, 2 * nroots + 10))
+            order = np.argsort(w)
+            w, v = w[order], v[:, order]
+        vecs = []
+        for k in range(nroots):
+            x = v[:, k].copy()
+            x *= np.sign(x[np.argmax(np.abs(x))])
+            vecs.append(x.reshape(na, nb))
+        if nroots == 1:
+            return float(w[0]), vecs[0]
+        return [float(x) for x in w[:nroots]], vecs
+
+    def trans_rdm12_rows(self, bra, kets, norb, nelec):
+        """One bra against all ``kets`` in one pass: ``(ovlp (K,), dm1 (K,N,N), dm2 (K,N,N,N,N))``.  The host arrays are
+        uploaded once and remembered by identity, so the next training state does not upload the old vectors again."""
+        nelec = _nelec(nelec)
+        kets = list(kets)
+        if not kets:
+            raise EvcontHipError("DeviceFCI.trans_rdm12_rows: no kets")
+        lib, dta, dtb, na, nb, grant = self._setup(norb, nelec)
+        dev = self._dev()
+        dbra = self._upload(bra, na, nb, cache=True)
+        dkets = [self._upload(k, na, nb, cache=True) for k in kets]
+        K = len(dkets)
+        ovlp = torch.empty(K, dtype=F64, device=dev)
+        dm1 = torch.empty((K, norb, norb), dtype=F64, device=dev)
+        dm2 = torch.empty((K, norb, norb, norb, norb), dtype=F64, device=dev)
+        ptrs = (C.c_void_p * K)(*[t.data_ptr() for t in dkets])
+        check(lib.evc_fci_trdm_rows(norb, na, nb, dta.data_ptr(), dtb.data_ptr(), dbra.data_ptr(), ptrs, K,
+                                    ovlp.data_ptr(), dm1.data_ptr(), dm2.data_ptr(), self._ws.data_ptr(), grant,
+                                    self._stream()), "evc_fci_trdm_rows")
+        return ovlp.cpu().numpy(), dm1.cpu().numpy(), dm2.cpu().numpy()
+
+    def trans_rdm12(self, cibra, ciket, norb, nelec):
+        nelec = _nelec(nelec)
+        lib, dta, dtb, na, nb, grant = self._setup(norb, nelec)
+        dev = self._dev()
+        dbra = self._upload(cibra, na, nb, cache=False)
+        dket = dbra if ciket is cibra else self._upload(ciket, na, nb, cache=False)
+        ovlp = torch.empty(1, dtype=F64, device=dev)
+        dm1 = torch.empty((norb, norb), dtype=F64, device=dev)
+        dm2 = torch.empty((norb, norb, norb, norb), dtype=F64, device=dev)
+        ptrs = (C.c_void_p * 1)(dket.data_ptr())
+        check(lib.evc_fci_trdm_rows(norb, na, nb, dta.data_ptr(), dtb.data_ptr(), dbra.data_ptr(), ptrs, 1,
+                                    ovlp.data_ptr(), dm1.data_ptr(), dm2.data_ptr(), self._ws.data_ptr(), grant,
+                                    self._stream()), "evc_fci_trdm_rows")
+        return dm1.cpu().numpy(), dm2.cpu().numpy()
+
+    def make_rdm12(self, ci, norb, nelec):
+        return self.trans_rdm12(ci, ci, norb, nelec)
+
+    def energy(self, h1, h2, ci, norb, nelec) -> float:
+        dm1, dm2 = self.make_rdm12(ci, norb, nelec)
+        return float(np.sum(np.asarray(h1) * dm1.T) + 0.5 * np.sum(np.asarray(h2).reshape(dm2.shape) * dm2))

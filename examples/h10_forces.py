@@ -39,7 +39,18 @@ p.add_argument("--batch", type=int, default=50)
 p.add_argument("--fixture", action="store_true",
                help="take the five training states from tests/golden/h10_fci_t5.npz (STO-3G, other spacings) instead "
                     "of solving five 63504-determinant FCI problems first (~2 min)")
+p.add_argument("--solver", choices=("host", "device"), default="host",
+               help="FCI solver of the training states and the exact energies: fci_small.SmallFCI (default) or "
+                    "fci_device.DeviceFCI (sigma vectors and transition RDMs on the GPU: seconds instead of minutes)")
 a = p.parse_args()
+
+
+def make_solver():
+    if a.solver == "device":
+        from evcont_amd.fci_device import DeviceFCI
+        return DeviceFCI()
+    return SmallFCI()
+
 
 n_data_points, seed, natm = a.points, 1, 10
 rng = np.random.default_rng(seed)
@@ -52,7 +63,7 @@ def get_mol(positions, need_grad=True):
     return s_gaussian_mol(np.asarray(positions), exponents=ex, coefficients=co, need_grad=need_grad)
 
 
-continuation_object = FCI_EVCont_obj(cisolver=SmallFCI(), cibasis="OAO")
+continuation_object = FCI_EVCont_obj(cisolver=make_solver(), cibasis="OAO")
 if a.fixture:
     with np.load(os.path.join(REPO, "tests", "golden", "h10_fci_t5.npz")) as z:
         continuation_object.overlap, continuation_object.one_rdm = z["overlap"], z["one_rdm"]
@@ -99,7 +110,7 @@ for k, (E, g) in enumerate(first):
     assert abs(E - en[k]) < 1e-9 and np.abs(g - gr[k]).max() < 1e-8, (k, E, en[k])
 
 exact = np.full(n_data_points, np.nan)
-solver = SmallFCI()
+solver = make_solver()
 for i in range(min(a.exact, n_data_points)):
     m = get_mol(geoms[i], need_grad=False)
     h1, h2 = get_integrals(m, get_basis(m))

@@ -8,7 +8,9 @@ FCI training states from ``evcont_amd.fci_small`` held in ``FCI_EVCont_obj``, an
 should be run on this hardware.
 
     python examples/h6_pes.py            # needs a HIP device; writes predicted_surface_*.txt, exact_surface.txt
+    python examples/h6_pes.py --solver device     # the FCI training states on the GPU too (fci_device.DeviceFCI)
 """
+import argparse
 import os
 import sys
 
@@ -34,7 +36,15 @@ def get_mol(dist, need_grad=False):
 
 
 def main():
-    solver = SmallFCI()
+    p = argparse.ArgumentParser()
+    p.add_argument("--solver", choices=("host", "device"), default="host",
+                   help="FCI solver of the training states: fci_small.SmallFCI (default) or fci_device.DeviceFCI")
+    a = p.parse_args()
+    if a.solver == "device":
+        from evcont_amd.fci_device import DeviceFCI
+        solver = DeviceFCI()
+    else:
+        solver = SmallFCI()
     continuation_object = FCI_EVCont_obj(cisolver=solver, cibasis="OAO")
     test_dists = np.linspace(0.8, 3.0)
     test_mols = [get_mol(d) for d in test_dists]

@@ -39,7 +39,9 @@ extern "C" {
                              9: evc_release_workspace (a workspace may own a side stream);
                              10: evc_phase_gradient_roots, evc_workspace_bytes_roots, evc_outputs_roots;
                                  later additions under 10 (no existing signature or behaviour changed):
-                                 evc_phase_gradient_roots_batch, evc_workspace_bytes_roots_batch */
+                                 evc_phase_gradient_roots_batch, evc_workspace_bytes_roots_batch;
+                                 evc_fci_excite, evc_fci_trdm_rows, evc_fci_sigma, evc_fci_workspace_bytes and the
+                                 stages EVC_PROF_FCI_* */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -413,6 +415,42 @@ int evc_contract_nnA3(const double *T, const double *M, int transposed, int n, i
                       void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Full-CI training states (fci_small.py: SmallFCI._excite_all, .trans_rdm12, .contract) for real CI vectors c[na][nb]
+ * over alpha / beta occupation strings ordered by their integer value, norb <= 16, any (n_alpha, n_beta).
+ *   tab_a (na, npad), tab_b (nb, npad)  DEVICE int32 string tables, npad = norb^2 rounded up to 16:
+ *       tab[I * npad + p * norb + q] = +-(J + 1) where <I| a_p^+ a_q |J> = +-1, 0 where there is no such J and in the
+ *       pad columns (evcont_amd/fci_tables.py builds them).
+ * The determinants are split into blocks of R = max(256, ceil(dim / 256) rounded up to 64) rows; every sum over the
+ * determinants is formed per block and the blocks are added in order, whatever the workspace and the number of kets:
+ * results are reproducible bit for bit, and a row call equals its single-pair calls.
+ *
+ * evc_fci_workspace_bytes(norb, na, nb, minimal): bytes with which evc_fci_trdm_rows and evc_fci_sigma keep every
+ *       intermediate of a CI vector resident (minimal = 0: one pass, the bra side of a row call formed once), or the
+ *       least they accept (minimal != 0: the excitations D = E_pq c are then formed and consumed in chunks; the
+ *       sigma intermediate G, norb^2 * dim doubles, is always whole).  0 on an argument error.
+ * evc_fci_excite: rows k0 .. k0 + nk - 1 of D[pq](k) = (E_pq c)(k) (zero for k >= dim and in the pad columns) as
+ *       EVC_FCI_DET_MAJOR    D[(k - k0) * ld + pq]           ld = npad
+ *       EVC_FCI_DET_MAJOR_T  D[(k - k0) * ld + q * norb + p] ld = npad   (the bra side <E_qp bra|)
+ *       EVC_FCI_ORB_MAJOR    D[pq * ld + (k - k0)]           ld >= nk, all npad rows are written
+ * evc_fci_trdm_rows: one bra against nkets kets (`kets`: HOST array of nkets DEVICE pointers), conventions of
+ *       SmallFCI.trans_rdm12: ovlp[i] = <bra|ket_i>, dm1[i][p][q] = <bra| q^+ p |ket_i>,
+ *       dm2[i][p][q][r][s] = <bra| p^+ r^+ s q |ket_i>;  dm1 (nkets, norb^2), dm2 (nkets, norb^4), dense.
+ * evc_fci_sigma: sigma = H c, H = sum h'_pq E_pq + 1/2 sum (pq|rs) E_pq E_rs, h'_pq = h1_pq - 1/2 sum_r (pr|rq);
+ *       h1 (norb, norb), h2 (norb, norb, norb, norb) chemists' order, no symmetry assumed; sigma must not alias c.
+ * --------------------------------------------------------------------------------- */
+#define EVC_FCI_DET_MAJOR 0
+#define EVC_FCI_DET_MAJOR_T 1
+#define EVC_FCI_ORB_MAJOR 2
+size_t evc_fci_workspace_bytes(int norb, int64_t na, int64_t nb, int minimal);
+int evc_fci_excite(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b, const double *c,
+                   int64_t k0, int64_t nk, int layout, double *D, int64_t ld, void *stream);
+int evc_fci_trdm_rows(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b, const double *bra,
+                      const double *const *kets, int nkets, double *ovlp, double *dm1, double *dm2, void *ws,
+                      size_t ws_bytes, void *stream);
+int evc_fci_sigma(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b, const double *h1,
+                  const double *h2, const double *c, double *sigma, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Measurement hook (bench.py): while enabled, the fused pipeline records hipEvents on the launch
  * stream immediately before and after the launches of the stages below, for up to max_samples
  * evaluations.  evc_profile_end synchronises those events, returns the summed durations in
@@ -428,6 +466,9 @@ int evc_contract_nnA3(const double *T, const double *M, int transposed, int n, i
 #define EVC_PROF_UNPACK 5         /* unpack/symmetrise the predicted 2-RDM */
 #define EVC_PROF_LOEWDIN 6        /* Loewdin orthogonalisation */
 #define EVC_PROF_SUBSPACE 7       /* subspace generalised eigenproblem */
+#define EVC_PROF_FCI_EXCITE 8     /* evc_fci_*: D = E_pq c (last launch: the layout it wrote) */
+#define EVC_PROF_FCI_TRDM 9       /* evc_fci_trdm_rows: split-K product, with its tiling */
+#define EVC_PROF_FCI_SIGMA 10     /* evc_fci_sigma: G = h2 . D and the gather */
 int evc_profile_begin(int max_samples);
 int evc_profile_end(double *rows_ms, int *rows_n, double *cols_ms, int *cols_n);
 int evc_profile_stage(int stage, double *ms, int *launches);
