@@ -84,7 +84,8 @@ struct Geo {
     int64_t sS, sh, seri, sip, sdh, sip1, sgn;
     double enuc;             // used when enuc_dev == NULL
     const double *enuc_dev;  // [count]
-    int eri_s4;              // eri is the dense (pair, pair) matrix (EVC_FLAG_ERI_S4); set from the call's flags
+    int batch;               // built by geo_batch: enuc and gnuc are device arrays, both required (check_geometry)
+    int eri_s4;              // eri is the dense (pair, pair) matrix (EVC_FLAG_ERI_S4); set from the call's flags (setup)
     int geo_period;          // gradient chain: slot g reads geometry geo_of(g, geo_period) (kernels.hpp; 0: g)
 };
 struct Out {
@@ -133,10 +134,6 @@ static bool use_pair_transform(int n) { return n <= kPairTransformMaxN; }
 static bool use_pair64(int layout, int n, bool packed_input) {
     return layout == EVC_LAYOUT_SYM8 && n > kPairTransformMaxN && n <= 64 && packed_input;
 }
-
-// Geometries per pass of the multi-kernel stages of a batched call (integral rotation, gradient tail): one pass over
-// the whole batch (chunks of 16, which keep the intermediates closer to the Infinity Cache, measured within noise).
-static int stage_chunk(int count) { return count; }
 
 // Many spans: sum the partials in a multi-workgroup launch instead of inside the eigensolver kernel.
 static bool reduce_in_own_launch(const Ws &w) { return w.rp2.nspans > 64; }
@@ -389,6 +386,26 @@ static void replan(const evc_trdm_set *t, Ws &w, int count) {
     plan_rows(w.rp1, batched);
 }
 
+// The Loewdin step of the geometries g into the workspace slots w (part 0: everything in one launch).
+static LoewdinArgs loewdin_args(int n, const Geo &g, const Ws &w) {
+    LoewdinArgs la{};
+    la.S = g.S;
+    la.h = g.hcore;
+    la.X = w.X;
+    la.U = w.U;
+    la.s = w.s;
+    la.h1 = w.h1;
+    la.sS = g.sS;
+    la.sh = g.sh;
+    la.sws = w.stride;
+    la.n = n;
+    la.warm = w.warm ? 1 : 0;
+    la.scratch = w.B1;   // (free until the integral rotation; n > 64 only)
+    la.sscratch = w.stride;
+    la.flag = w.lflag;   // (read by the two halves of a split step only)
+    return la;
+}
+
 // rows_out != NULL: the scaled two-body rows go to rows_out[g*srows_out + r] (r local) instead of the workspace.
 static int phase_hamiltonian(const evc_trdm_set *t, const Geo &g_in, Ws &w, bool reduce_rows, hipStream_t st,
                              double *rows_out = nullptr, int64_t srows_out = 0) {
@@ -403,22 +420,7 @@ static int phase_hamiltonian(const evc_trdm_set *t, const Geo &g_in, Ws &w, bool
     }
     const int64_t sw = w.stride;
     int rc;
-    replan(t, w, cnt);
-    LoewdinArgs la{};
-    la.S = g.S;
-    la.h = g.hcore;
-    la.X = w.X;
-    la.U = w.U;
-    la.s = w.s;
-    la.h1 = w.h1;
-    la.sS = g.sS;
-    la.sh = g.sh;
-    la.sws = sw;
-    la.n = n;
-    la.warm = w.warm ? 1 : 0;
-    la.scratch = w.B1;   // (free until the integral rotation; n > 64 only)
-    la.sscratch = sw;
-    la.flag = w.lflag;
+    LoewdinArgs la = loewdin_args(n, g, w);
     if (!w.loewdin_done) {
         if (w.split == 1) {
             // the eigendecomposition of S (U, s: read by launch_grad_final alone) on the side stream, forked here: the
@@ -455,9 +457,10 @@ static int phase_hamiltonian(const evc_trdm_set *t, const Geo &g_in, Ws &w, bool
         // two fused pair steps; the second one emits K3 and writes h2 straight into the form the
         // streaming kernel consumes (packed with diag x 1/2, or full)
         // in chunks of geometries, so that the intermediate of a chunk (6.5 MB per geometry) is still in the
-        // 256 MB Infinity Cache when the second step reads it
+        // 256 MB Infinity Cache when the second step reads it -- one chunk, the whole batch, here and in the gradient
+        // tail: chunks of 16 keep the intermediates closer to that cache and measured within noise
         v2 = is_packed(t->layout) ? w.vec2 : w.B2;
-        const int chunk = stage_chunk(cnt);
+        const int chunk = cnt;
         for (int c0 = 0; c0 < cnt; c0 += chunk) {
             const int cc = cnt - c0 < chunk ? cnt - c0 : chunk;
             const int64_t o = (int64_t)c0 * sw;
@@ -700,8 +703,9 @@ static int gradient_from_rdms(int n, const Geo &g, const double *D, int64_t sD, 
     if (packed) {
         if (pairs_route) {
             // unpack+symmetrise -> Y2 -> B1 (symmetrised, OAO) -> B2 -> B1 (AO) -> ip1 contraction, in chunks of
-            // geometries so that each kernel finds its predecessor's output in the Infinity Cache
-            const int chunk = stage_chunk(cnt);
+            // geometries so that each kernel finds its predecessor's output in the Infinity Cache (one chunk: see
+            // phase_hamiltonian)
+            const int chunk = cnt;
             for (int c0 = 0; c0 < cnt; c0 += chunk) {
                 const int cc = cnt - c0 < chunk ? cnt - c0 : chunk;
                 const int64_t o = (int64_t)c0 * sw;
@@ -880,22 +884,13 @@ static int phase_gradient(const evc_trdm_set *t, const Geo &g_in, const Out &out
                               w, st);
 }
 
-static int check_geometry(const evc_geometry *g, bool need_grad) {
-    EVC_REQUIRE(g != nullptr, "geometry is NULL");
-    EVC_REQUIRE(g->S && g->hcore && g->eri, "geometry: S/hcore/eri must be given");
-    // (the pair kernels fetch the rows of the two large arrays through 16-byte windows)
-    EVC_REQUIRE(aligned16(g->eri) && (!g->eri_ip1 || aligned16(g->eri_ip1)), "geometry: eri / eri_ip1 must be 16-byte aligned");
-    if (need_grad) {
-        EVC_REQUIRE(g->natm >= 1, "geometry: natm=%d", g->natm);
-        EVC_REQUIRE(g->ipovlp && g->dhcore && g->eri_ip1 && g->aoslices,
-                    "geometry: ipovlp/dhcore/eri_ip1/aoslices are required for the gradient");
-    }
-    return 0;
-}
-
+// The two constructors of Geo.  One geometry: count = 1, every stride 0, enuc by value, geo_period 0 (to the chain the
+// slot is a geometry of its own).  They and those of Out are called before any check: a NULL descriptor gives
+// count = 0, which check_geometry reports (a NULL set: check_set).
 static Geo geo_single(const evc_geometry *g) {
     Geo o;
     memset(&o, 0, sizeof(o));
+    if (!g) return o;
     o.natm = g->natm;
     o.count = 1;
     o.S = g->S;
@@ -910,25 +905,15 @@ static Geo geo_single(const evc_geometry *g) {
     return o;
 }
 
-static int check_geometry_batch(const char *who, const evc_geometry_batch *gb, bool need_grad) {
-    EVC_REQUIRE(gb, "%s: null batch descriptor", who);
-    EVC_REQUIRE(gb->count >= 1 && gb->count <= 4096, "%s: batch count=%d out of range", who, gb->count);
-    EVC_REQUIRE(gb->S && gb->hcore && gb->eri && gb->enuc, "%s: batch geometry: S/hcore/eri/enuc must be given", who);
-    EVC_REQUIRE(aligned16(gb->eri) && (!gb->eri_ip1 || aligned16(gb->eri_ip1)),
-                "%s: batch geometry: eri / eri_ip1 must be 16-byte aligned", who);
-    if (need_grad)
-        EVC_REQUIRE(gb->natm >= 1 && gb->ipovlp && gb->dhcore && gb->eri_ip1 && gb->aoslices && gb->gnuc,
-                    "%s: batch geometry: ipovlp/dhcore/eri_ip1/gnuc/aoslices are required for the gradient", who);
-    return 0;
-}
-
-// count geometries of n orbitals, each at its own stride (geo_period 0: slot g reads geometry g)
-static Geo geo_batch(int n, const evc_geometry_batch *gb) {
-    const int64_t n2 = (int64_t)n * n, n4 = n2 * n2, A3 = (int64_t)gb->natm * 3;
+// count geometries of t->n orbitals, each at its own stride (geo_period 0: slot g reads geometry g), enuc on the device
+static Geo geo_batch(const evc_trdm_set *t, const evc_geometry_batch *gb) {
     Geo g;
     memset(&g, 0, sizeof(g));
+    if (!t || !gb) return g;
+    const int64_t n2 = (int64_t)t->n * t->n, n4 = n2 * n2, A3 = (int64_t)gb->natm * 3;
     g.natm = gb->natm;
     g.count = gb->count;
+    g.batch = 1;
     g.S = gb->S;
     g.sS = n2;
     g.hcore = gb->hcore;
@@ -948,6 +933,24 @@ static Geo geo_batch(int n, const evc_geometry_batch *gb) {
     return g;
 }
 
+// A batch needs enuc and gnuc as device arrays; one geometry takes enuc by value and gnuc is optional (NULL: no
+// nuclear term).
+static int check_geometry(const char *who, const Geo &g, bool need_grad) {
+    EVC_REQUIRE(g.count >= 1 && g.count <= 4096,
+                "%s: geometry is NULL / null batch descriptor, or count=%d out of range 1..4096", who, g.count);
+    EVC_REQUIRE(g.S && g.hcore && g.eri && (!g.batch || g.enuc_dev), "%s: geometry: S/hcore/eri%s must be given", who,
+                g.batch ? "/enuc" : "");
+    // (the pair kernels fetch the rows of the two large arrays through 16-byte windows)
+    EVC_REQUIRE(aligned16(g.eri) && (!g.eri_ip1 || aligned16(g.eri_ip1)),
+                "%s: geometry: eri / eri_ip1 must be 16-byte aligned", who);
+    if (need_grad)
+        EVC_REQUIRE(g.natm >= 1 && g.ipovlp && g.dhcore && g.eri_ip1 && g.aoslices && (!g.batch || g.gnuc),
+                    "%s: geometry: natm=%d, ipovlp/dhcore/eri_ip1/aoslices%s are required for the gradient", who, g.natm,
+                    g.batch ? "/gnuc" : "");
+    return 0;
+}
+
+// The two constructors of Out: one geometry (strides 0), count geometries each at its own stride.
 static Out out_single(const evc_outputs *o) {
     Out r;
     memset(&r, 0, sizeof(r));
@@ -960,6 +963,109 @@ static Out out_single(const evc_outputs *o) {
         r.hmat = o->hmat;
     }
     return r;
+}
+
+static Out out_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, const evc_outputs_batch *ob) {
+    Out r;
+    memset(&r, 0, sizeof(r));
+    if (t && gb && ob) {
+        const int64_t n2 = (int64_t)t->n * t->n, T = t->ntrain;
+        r.energy = ob->energy;
+        r.se = T;
+        r.coeffs = ob->coeffs;
+        r.sc = T * T;
+        r.grad = ob->grad;
+        r.sg = (int64_t)gb->natm * 3;
+        r.d_pred = ob->d_pred;
+        r.sd = n2;
+        r.g_pred = ob->g_pred;
+        r.sG = n2 * n2;
+        r.hmat = ob->hmat;
+        r.sH = T * T;
+    }
+    return r;
+}
+
+// The set-up every entry point that works in a caller's workspace of `slots` geometry slots goes through (t checked by
+// the caller, check_set): the workspace checks, its carving, the span plan of the call, and the call's flags that configure the
+// two views -- each decoded here and nowhere else.
+static int setup(const char *who, const evc_trdm_set *t, Geo &g, int flags, void *ws, size_t ws_bytes, int slots,
+                 Ws &w) {
+    EVC_REQUIRE(ws && aligned16(ws), "%s: workspace NULL or misaligned", who);
+    carve(t, g.natm, static_cast<char *>(ws), w);
+    EVC_REQUIRE(ws_bytes >= w.bytes * (size_t)slots, "%s: workspace too small: %zu < %zu", who, ws_bytes,
+                w.bytes * (size_t)slots);
+    replan(t, w, slots);
+    w.warm = (flags & EVC_FLAG_WARM_START) != 0;
+    w.loewdin_done = (flags & EVC_FLAG_LOEWDIN_DONE) != 0;
+    g.eri_s4 = (flags & EVC_FLAG_ERI_S4) ? 1 : 0;
+    return 0;
+}
+
+// ---- one body per operation: the full call and the phases A, B, C --------------------------------------------------
+// Each takes the two views and serves the single-geometry entry point and its _batch twin alike.  Where the two differ
+// on purpose it says so (Geo::batch): a batch is handed its rows, energies and coefficients in the caller's arrays, one
+// geometry may leave them in the workspace.
+
+// what the subspace solve needs of its caller (full call and phase B)
+static int check_solve(const char *who, const evc_trdm_set *t, const Geo &g, const Out &o, int nroots) {
+    EVC_REQUIRE(!g.batch || (o.energy && o.coeffs), "%s: batch outputs.energy/coeffs are required", who);
+    EVC_REQUIRE(nroots >= 1 && nroots <= t->ntrain, "%s: nroots=%d out of range 1..%d", who, nroots, t->ntrain);
+    return 0;
+}
+
+static int full_call(const char *who, const evc_trdm_set *t, Geo g, const Out &o, int nroots, int flags, void *ws,
+                     size_t ws_bytes, void *stream) {
+    const bool energy_only = (flags & EVC_FLAG_ENERGY_ONLY) != 0;
+    if (check_set(t) || check_geometry(who, g, !energy_only)) return -1;
+    EVC_REQUIRE(energy_only || o.grad, "%s: outputs.grad is required unless EVC_FLAG_ENERGY_ONLY", who);
+    Ws w;
+    if (setup(who, t, g, flags, ws, ws_bytes, g.count, w) || check_solve(who, t, g, o, nroots)) return -1;
+    EVC_REQUIRE(t->rows2 == t->rows2_total && t->row_offset == 0,
+                "%s needs the complete t-RDM on this device (use the phase calls when sharded)", who);
+    const int s2kl = flags & EVC_FLAG_IP1_S2KL;
+    EVC_REQUIRE(energy_only || t->n <= kPairTransformMaxN || !g.eri_s4 == !s2kl,
+                "%s: N > 32: EVC_FLAG_ERI_S4 and EVC_FLAG_IP1_S2KL go together (both packed inputs, or neither)", who);
+    hipStream_t st = as_stream(stream);
+    w.split = loewdin_split_mode(t->n, t->ntrain, g.count, w.loewdin_done, energy_only, w.warm, st);
+    int rc;
+    if ((rc = phase_hamiltonian(t, g, w, false, st))) return rc;
+    if ((rc = phase_solve(t, g, nullptr, 0, o, nroots, w, st))) return rc;
+    if (energy_only) return 0;
+    // (of the two bits the gradient phase reads, EVC_FLAG_PARTIAL_RANK belongs to the phase calls alone)
+    return phase_gradient(t, g, o, s2kl, w, st);
+}
+
+// Phase A.  rows_out NULL (one geometry): the rows stay in the workspace, w tells the caller where.
+static int hamiltonian_call(const char *who, const evc_trdm_set *t, Geo g, int flags, double *rows_out,
+                            int64_t ld_rows_out, void *ws, size_t ws_bytes, void *stream, Ws &w) {
+    if (check_set(t) || check_geometry(who, g, false) || setup(who, t, g, flags, ws, ws_bytes, g.count, w)) return -1;
+    EVC_REQUIRE(!g.batch || t->rows2 == 0 || (rows_out && ld_rows_out >= t->rows2),
+                "%s: rows_out NULL or ld_rows_out=%lld < rows2=%lld", who, (long long)ld_rows_out, (long long)t->rows2);
+    return phase_hamiltonian(t, g, w, true, as_stream(stream), rows_out, ld_rows_out);
+}
+
+// Phase B.  h2rows_all NULL (one geometry): the rows phase A left in the workspace.
+static int solve_call(const char *who, const evc_trdm_set *t, Geo g, const double *h2rows_all, int64_t ld_rows_all,
+                      const Out &o, int nroots, int flags, void *ws, size_t ws_bytes, void *stream) {
+    Ws w;
+    if (check_set(t) || check_geometry(who, g, false) || setup(who, t, g, flags, ws, ws_bytes, g.count, w) ||
+        check_solve(who, t, g, o, nroots))
+        return -1;
+    EVC_REQUIRE(!g.batch || (h2rows_all && ld_rows_all >= t->rows2_total),
+                "%s: h2rows_all NULL or ld_rows_all=%lld < rows2_total=%lld", who, (long long)ld_rows_all,
+                (long long)t->rows2_total);
+    return phase_solve(t, g, h2rows_all ? h2rows_all : w.h2rows, ld_rows_all, o, nroots, w, as_stream(stream));
+}
+
+// Phase C.
+static int gradient_call(const char *who, const evc_trdm_set *t, Geo g, const Out &o, int flags, void *ws,
+                         size_t ws_bytes, void *stream) {
+    if (check_set(t) || check_geometry(who, g, true)) return -1;
+    EVC_REQUIRE(o.grad, "%s: outputs.grad is required", who);
+    Ws w;
+    if (setup(who, t, g, flags, ws, ws_bytes, g.count, w)) return -1;
+    return phase_gradient(t, g, o, flags & (EVC_FLAG_IP1_S2KL | EVC_FLAG_PARTIAL_RANK), w, as_stream(stream));
 }
 
 }  // namespace evc
@@ -1052,81 +1158,100 @@ extern "C" size_t evc_workspace_bytes_batch(const evc_trdm_set *t, int natm, int
     return w.bytes * (size_t)count;
 }
 
-#define EVC_SETUP(need_grad)                                                                      \
-    if (check_set(t)) return -1;                                                                  \
-    if (check_geometry(g, need_grad)) return -1;                                                  \
-    EVC_REQUIRE(ws && aligned16(ws), "workspace NULL or misaligned");                             \
-    Ws w;                                                                                         \
-    carve(t, g->natm, static_cast<char *>(ws), w);                                                \
-    EVC_REQUIRE(ws_bytes >= w.bytes, "workspace too small: %zu < %zu", ws_bytes, w.bytes);        \
-    replan(t, w, 1);                                                                              \
-    hipStream_t st = as_stream(stream);                                                           \
-    const Geo geo = geo_single(g)
+// ---- the single-geometry entry points and their _batch twins: clear the stage records, build the two views, call ----
+// EVC_FLAG_LOEWDIN_DONE belongs to the batch calls; callers pass one flag word to both forms, one geometry ignores it.
+constexpr int kSingleFlags = ~EVC_FLAG_LOEWDIN_DONE;
+
+extern "C" int evc_energy_with_grad(const evc_trdm_set *t, const evc_geometry *g, const evc_outputs *out,
+                                    int nroots, int flags, void *ws, size_t ws_bytes, void *stream) {
+    clear_kernels(kStagesAll);
+    EVC_REQUIRE(out != nullptr, "evc_energy_with_grad: outputs is NULL");
+    return full_call("evc_energy_with_grad", t, geo_single(g), out_single(out), nroots, flags & kSingleFlags, ws,
+                     ws_bytes, stream);
+}
+
+extern "C" int evc_energy_with_grad_batch(const evc_trdm_set *t, const evc_geometry_batch *gb,
+                                          const evc_outputs_batch *ob, int nroots, int flags, void *ws,
+                                          size_t ws_bytes, void *stream) {
+    clear_kernels(kStagesAll);
+    return full_call("evc_energy_with_grad_batch", t, geo_batch(t, gb), out_batch(t, gb, ob), nroots, flags, ws,
+                     ws_bytes, stream);
+}
 
 extern "C" int evc_phase_hamiltonian(const evc_trdm_set *t, const evc_geometry *g, int flags, void *ws, size_t ws_bytes,
                                      double **h2rows_local, double **h1rows, void *stream) {
-    EVC_SETUP(false);
     clear_kernels(kStagesHamiltonian);
-    w.warm = (flags & EVC_FLAG_WARM_START) != 0;
-    Geo gg = geo;
-    gg.eri_s4 = (flags & EVC_FLAG_ERI_S4) ? 1 : 0;
-    int rc = phase_hamiltonian(t, gg, w, true, st);
-    if (rc) return rc;
+    Ws w;
+    if (int rc = hamiltonian_call("evc_phase_hamiltonian", t, geo_single(g), flags & kSingleFlags, nullptr, 0, ws,
+                                  ws_bytes, stream, w))
+        return rc;
     if (h2rows_local) *h2rows_local = w.h2rows + t->row_offset;
     if (h1rows) *h1rows = w.h1part;
     return 0;
 }
 
+extern "C" int evc_phase_hamiltonian_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, int flags,
+                                           double *rows_out, int64_t ld_rows_out, void *ws, size_t ws_bytes,
+                                           void *stream) {
+    clear_kernels(kStagesHamiltonian);
+    Ws w;
+    return hamiltonian_call("evc_phase_hamiltonian_batch", t, geo_batch(t, gb), flags, rows_out, ld_rows_out, ws,
+                            ws_bytes, stream, w);
+}
+
 extern "C" int evc_phase_solve(const evc_trdm_set *t, const evc_geometry *g, const double *h2rows_all,
                                const evc_outputs *out, int nroots, int flags, void *ws, size_t ws_bytes, void *stream) {
-    EVC_SETUP(false);
-    EVC_REQUIRE(nroots >= 1 && nroots <= t->ntrain, "nroots=%d out of range 1..%d", nroots, t->ntrain);
     clear_kernels(1u << EVC_PROF_SUBSPACE);
-    w.warm = (flags & EVC_FLAG_WARM_START) != 0;
-    return phase_solve(t, geo, h2rows_all ? h2rows_all : w.h2rows, 0, out_single(out), nroots, w, st);
+    return solve_call("evc_phase_solve", t, geo_single(g), h2rows_all, 0, out_single(out), nroots, flags, ws, ws_bytes,
+                      stream);
+}
+
+extern "C" int evc_phase_solve_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, const double *h2rows_all,
+                                     int64_t ld_rows_all, const evc_outputs_batch *ob, int nroots, int flags,
+                                     void *ws, size_t ws_bytes, void *stream) {
+    clear_kernels(1u << EVC_PROF_SUBSPACE);
+    return solve_call("evc_phase_solve_batch", t, geo_batch(t, gb), h2rows_all, ld_rows_all, out_batch(t, gb, ob),
+                      nroots, flags, ws, ws_bytes, stream);
+}
+
+extern "C" int evc_phase_gradient(const evc_trdm_set *t, const evc_geometry *g, const evc_outputs *out,
+                                  int flags, void *ws, size_t ws_bytes, void *stream) {
+    clear_kernels(kStagesGradient);
+    return gradient_call("evc_phase_gradient", t, geo_single(g), out_single(out), flags, ws, ws_bytes, stream);
+}
+
+extern "C" int evc_phase_gradient_batch(const evc_trdm_set *t, const evc_geometry_batch *gb,
+                                        const evc_outputs_batch *ob, int flags, void *ws, size_t ws_bytes,
+                                        void *stream) {
+    clear_kernels(kStagesGradient);
+    return gradient_call("evc_phase_gradient_batch", t, geo_batch(t, gb), out_batch(t, gb, ob), flags, ws, ws_bytes,
+                         stream);
 }
 
 extern "C" int evc_phase_set_coeffs(const evc_trdm_set *t, const double *coeffs, int natm, void *ws, size_t ws_bytes,
                                     void *stream) {
     if (check_set(t)) return -1;
     EVC_REQUIRE(coeffs, "evc_phase_set_coeffs: coeffs is NULL");
-    EVC_REQUIRE(ws && aligned16(ws), "workspace NULL or misaligned");
+    Geo g = geo_single(nullptr);   // (no geometry: the workspace of one slot for natm atoms)
+    g.natm = natm;
     Ws w;
-    carve(t, natm, static_cast<char *>(ws), w);
-    EVC_REQUIRE(ws_bytes >= w.bytes, "workspace too small: %zu < %zu", ws_bytes, w.bytes);
+    if (setup("evc_phase_set_coeffs", t, g, 0, ws, ws_bytes, 1, w)) return -1;
     return launch_pair_weights(coeffs, t->ntrain, t->layout, w.w1, w.w2, t->row_offset, t->rows2, as_stream(stream));
 }
 
-extern "C" int evc_phase_gradient(const evc_trdm_set *t, const evc_geometry *g, const evc_outputs *out,
-                                  int flags, void *ws, size_t ws_bytes, void *stream) {
-    EVC_SETUP(true);
-    EVC_REQUIRE(out && out->grad, "outputs.grad is required");
-    clear_kernels(kStagesGradient);
-    return phase_gradient(t, geo, out_single(out), flags, w, st);
-}
-
-extern "C" int evc_energy_with_grad(const evc_trdm_set *t, const evc_geometry *g, const evc_outputs *out,
-                                    int nroots, int flags, void *ws, size_t ws_bytes, void *stream) {
-    const bool energy_only = (flags & EVC_FLAG_ENERGY_ONLY) != 0;
-    clear_kernels(kStagesAll);
-    EVC_SETUP(!energy_only);
-    EVC_REQUIRE(out != nullptr, "outputs is NULL");
-    EVC_REQUIRE(nroots >= 1 && nroots <= t->ntrain, "nroots=%d out of range 1..%d", nroots, t->ntrain);
-    EVC_REQUIRE(t->rows2 == t->rows2_total && t->row_offset == 0,
-                "evc_energy_with_grad needs the complete t-RDM on this device (use the phase calls when sharded)");
-    EVC_REQUIRE(energy_only || out->grad, "outputs.grad is required unless EVC_FLAG_ENERGY_ONLY");
-    const Out o = out_single(out);
-    int rc;
-    EVC_REQUIRE(energy_only || t->n <= kPairTransformMaxN || !(flags & EVC_FLAG_ERI_S4) == !(flags & EVC_FLAG_IP1_S2KL),
-                "N > 32: EVC_FLAG_ERI_S4 and EVC_FLAG_IP1_S2KL go together (both packed inputs, or neither)");
-    w.warm = (flags & EVC_FLAG_WARM_START) != 0;
-    w.split = loewdin_split_mode(t->n, t->ntrain, 1, false, energy_only, w.warm, st);
-    Geo gg = geo;
-    gg.eri_s4 = (flags & EVC_FLAG_ERI_S4) ? 1 : 0;
-    if ((rc = phase_hamiltonian(t, gg, w, false, st))) return rc;
-    if ((rc = phase_solve(t, gg, nullptr, 0, o, nroots, w, st))) return rc;
-    if (energy_only) return 0;
-    return phase_gradient(t, gg, o, flags & ~EVC_FLAG_PARTIAL_RANK, w, st);
+extern "C" int evc_phase_loewdin_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, int flags, void *ws,
+                                       size_t ws_bytes, void *stream) {
+    const char *who = "evc_phase_loewdin_batch";
+    clear_kernels(1u << EVC_PROF_LOEWDIN);
+    Geo g = geo_batch(t, gb);
+    if (check_set(t)) return -1;
+    EVC_REQUIRE(g.count >= 1 && g.count <= 4096 && g.S && g.hcore, "%s: batch descriptor / S / hcore missing", who);
+    Ws w;
+    if (setup(who, t, g, flags, ws, ws_bytes, g.count, w)) return -1;
+    hipStream_t st = as_stream(stream);
+    // (rewrites U and s: after an energy-only call their eigensolver launch may still be running on the side stream)
+    if (int rc = side_join(w.base, st)) return rc;
+    return launch_loewdin(loewdin_args(t->n, g, w), g.count, st);
 }
 
 // ---- several roots: evc_phase_gradient_roots (one geometry), evc_phase_gradient_roots_batch (several) -------------
@@ -1187,11 +1312,12 @@ static int fan_out_blocks(char *base, size_t bytes, size_t pitch, int rows, int 
     return 0;
 }
 
-// g: the caller's count = g.count geometries (checked, with t, by the caller); sc: the stride of their (T, T)
-// coefficient blocks (0: one block for every slot).
-static int gradient_roots(const char *who, const evc_trdm_set *t, Geo g, const double *coeffs, int64_t sc, int nvec,
+// g: the caller's count = g.count geometries; a batch brings one (T, T) coefficient block per geometry, one geometry
+// one block for every slot (stride 0).
+static int gradient_roots(const char *who, const evc_trdm_set *t, Geo g, const double *coeffs, int nvec,
                           const int32_t *pairs, int npairs, const evc_outputs_roots *out, int flags, void *ws,
                           size_t ws_bytes, void *stream) {
+    if (check_set(t) || check_geometry(who, g, true)) return -1;
     EVC_REQUIRE(coeffs && pairs, "%s: coeffs / pairs is NULL", who);
     EVC_REQUIRE(out && out->grad, "%s: outputs.grad is required", who);
     EVC_REQUIRE(!(flags & EVC_FLAG_PARTIAL_RANK), "%s: EVC_FLAG_PARTIAL_RANK is not supported", who);
@@ -1208,18 +1334,17 @@ static int gradient_roots(const char *who, const evc_trdm_set *t, Geo g, const d
                     nvec);
         any_coupling = any_coupling || k != l;
     }
-    EVC_REQUIRE(ws && aligned16(ws), "%s: workspace NULL or misaligned", who);
     const int nslots = count * npairs;
     Ws w;
-    carve(t, g.natm, static_cast<char *>(ws), w);
+    if (setup(who, t, g, 0, ws, ws_bytes, nslots, w)) return -1;   // (flags: none of those that configure the views)
     const size_t need = roots_bytes(w.bytes, g.natm, nslots);
     EVC_REQUIRE(ws_bytes >= need, "%s: workspace too small: %zu < %zu", who, ws_bytes, need);
-    replan(t, w, nslots);
     hipStream_t st = as_stream(stream);
     const int n = t->n;
     const int64_t n2 = (int64_t)n * n, A3 = (int64_t)g.natm * 3;
     int rc;
     // (1) row weights of every slot: pair p of coefficient block g (+ the transposed group copies of the batched K8)
+    const int64_t sc = g.batch ? (int64_t)t->ntrain * t->ntrain : 0;
     if ((rc = launch_pair_weights_geo(coeffs, sc, g.geo_period, t->ntrain, t->layout, pairs, npairs, w.w1, w.w2,
                                       nslots > 1 ? w.w1t : nullptr, nslots > 1 ? w.w2t : nullptr, w.stride,
                                       t->row_offset, t->rows2, st)))
@@ -1270,158 +1395,18 @@ extern "C" int evc_phase_gradient_roots(const evc_trdm_set *t, const evc_geometr
                                         const int32_t *pairs, int npairs, const evc_outputs_roots *out, int flags,
                                         void *ws, size_t ws_bytes, void *stream) {
     clear_kernels(kStagesGradient);
-    if (check_set(t)) return -1;
-    if (check_geometry(g, true)) return -1;
-    return gradient_roots("evc_phase_gradient_roots", t, geo_single(g), coeffs, 0, nvec, pairs, npairs, out, flags, ws,
+    return gradient_roots("evc_phase_gradient_roots", t, geo_single(g), coeffs, nvec, pairs, npairs, out, flags, ws,
                           ws_bytes, stream);
 }
 
 extern "C" int evc_phase_gradient_roots_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, const double *coeffs,
                                               int nvec, const int32_t *pairs, int npairs, const evc_outputs_roots *out,
                                               int flags, void *ws, size_t ws_bytes, void *stream) {
-    const char *who = "evc_phase_gradient_roots_batch";
     clear_kernels(kStagesGradient);
-    if (check_set(t)) return -1;
-    if (check_geometry_batch(who, gb, true)) return -1;
-    Geo g = geo_batch(t->n, gb);
-    g.geo_period = gb->count;
-    return gradient_roots(who, t, g, coeffs, (int64_t)t->ntrain * t->ntrain, nvec, pairs, npairs, out, flags, ws,
-                          ws_bytes, stream);
-}
-
-// Shared argument checking / descriptor set-up of the batch entry points.
-static int setup_batch(const char *who, const evc_trdm_set *t, const evc_geometry_batch *gb,
-                       const evc_outputs_batch *ob, bool need_grad, void *ws, size_t ws_bytes, Ws &w, Geo &g, Out &o) {
-    if (check_set(t)) return -1;
-    if (check_geometry_batch(who, gb, need_grad)) return -1;
-    EVC_REQUIRE(!need_grad || (ob && ob->grad), "%s: batch outputs.grad is required", who);
-    EVC_REQUIRE(ws && aligned16(ws), "%s: workspace NULL or misaligned", who);
-    carve(t, gb->natm, static_cast<char *>(ws), w);
-    EVC_REQUIRE(ws_bytes >= w.bytes * (size_t)gb->count, "%s: workspace too small: %zu < %zu", who, ws_bytes,
-                w.bytes * (size_t)gb->count);
-    const int64_t n2 = (int64_t)t->n * t->n, n4 = n2 * n2, T = t->ntrain, A = gb->natm;
-    g = geo_batch(t->n, gb);
-    memset(&o, 0, sizeof(o));
-    if (ob) {
-        o.energy = ob->energy;
-        o.se = T;
-        o.coeffs = ob->coeffs;
-        o.sc = T * T;
-        o.grad = ob->grad;
-        o.sg = A * 3;
-        o.d_pred = ob->d_pred;
-        o.sd = n2;
-        o.g_pred = ob->g_pred;
-        o.sG = n4;
-        o.hmat = ob->hmat;
-        o.sH = T * T;
-    }
-    return 0;
-}
-
-extern "C" int evc_energy_with_grad_batch(const evc_trdm_set *t, const evc_geometry_batch *gb,
-                                          const evc_outputs_batch *ob, int nroots, int flags, void *ws,
-                                          size_t ws_bytes, void *stream) {
-    const bool energy_only = (flags & EVC_FLAG_ENERGY_ONLY) != 0;
-    clear_kernels(kStagesAll);
-    Ws w;
-    Geo g;
-    Out o;
-    if (setup_batch("evc_energy_with_grad_batch", t, gb, ob, !energy_only, ws, ws_bytes, w, g, o)) return -1;
-    EVC_REQUIRE(ob && ob->energy && ob->coeffs, "batch outputs.energy/coeffs are required");
-    EVC_REQUIRE(nroots >= 1 && nroots <= t->ntrain, "nroots=%d out of range 1..%d", nroots, t->ntrain);
-    EVC_REQUIRE(t->rows2 == t->rows2_total && t->row_offset == 0,
-                "evc_energy_with_grad_batch needs the complete t-RDM on this device (use the phase calls when sharded)");
-    hipStream_t st = as_stream(stream);
-    int rc;
-    w.warm = (flags & EVC_FLAG_WARM_START) != 0;
-    EVC_REQUIRE(energy_only || t->n <= kPairTransformMaxN || !(flags & EVC_FLAG_ERI_S4) == !(flags & EVC_FLAG_IP1_S2KL),
-                "N > 32: EVC_FLAG_ERI_S4 and EVC_FLAG_IP1_S2KL go together (both packed inputs, or neither)");
-    w.loewdin_done = (flags & EVC_FLAG_LOEWDIN_DONE) != 0;
-    w.split = loewdin_split_mode(t->n, t->ntrain, g.count, w.loewdin_done, energy_only, w.warm, st);
-    g.eri_s4 = (flags & EVC_FLAG_ERI_S4) ? 1 : 0;
-    if ((rc = phase_hamiltonian(t, g, w, false, st))) return rc;
-    if ((rc = phase_solve(t, g, nullptr, 0, o, nroots, w, st))) return rc;
-    if (energy_only) return 0;
-    return phase_gradient(t, g, o, flags & EVC_FLAG_IP1_S2KL, w, st);
-}
-
-extern "C" int evc_phase_loewdin_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, int flags, void *ws,
-                                       size_t ws_bytes, void *stream) {
-    clear_kernels(1u << EVC_PROF_LOEWDIN);
-    if (check_set(t)) return -1;
-    EVC_REQUIRE(gb && gb->count >= 1 && gb->count <= 4096 && gb->S && gb->hcore,
-                "evc_phase_loewdin_batch: batch descriptor / S / hcore missing");
-    EVC_REQUIRE(ws && aligned16(ws), "evc_phase_loewdin_batch: workspace NULL or misaligned");
-    Ws w;
-    carve(t, gb->natm, static_cast<char *>(ws), w);
-    EVC_REQUIRE(ws_bytes >= w.bytes * (size_t)gb->count, "evc_phase_loewdin_batch: workspace too small: %zu < %zu",
-                ws_bytes, w.bytes * (size_t)gb->count);
-    const int64_t n2 = (int64_t)t->n * t->n;
-    LoewdinArgs la{};
-    la.S = gb->S;
-    la.h = gb->hcore;
-    la.X = w.X;
-    la.U = w.U;
-    la.s = w.s;
-    la.h1 = w.h1;
-    la.sS = n2;
-    la.sh = n2;
-    la.sws = w.stride;
-    la.n = t->n;
-    la.warm = (flags & EVC_FLAG_WARM_START) ? 1 : 0;
-    la.scratch = w.B1;
-    la.sscratch = w.stride;
-    // (rewrites U and s: after an energy-only call their eigensolver launch may still be running on the side stream)
-    if (int rc = side_join(w.base, as_stream(stream))) return rc;
-    return launch_loewdin(la, gb->count, as_stream(stream));
-}
-
-extern "C" int evc_phase_hamiltonian_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, int flags,
-                                           double *rows_out, int64_t ld_rows_out, void *ws, size_t ws_bytes,
-                                           void *stream) {
-    clear_kernels(kStagesHamiltonian);
-    Ws w;
-    Geo g;
-    Out o;
-    if (setup_batch("evc_phase_hamiltonian_batch", t, gb, nullptr, false, ws, ws_bytes, w, g, o)) return -1;
-    EVC_REQUIRE(t->rows2 == 0 || (rows_out && ld_rows_out >= t->rows2),
-                "evc_phase_hamiltonian_batch: rows_out NULL or ld_rows_out=%lld < rows2=%lld", (long long)ld_rows_out,
-                (long long)t->rows2);
-    w.warm = (flags & EVC_FLAG_WARM_START) != 0;
-    w.loewdin_done = (flags & EVC_FLAG_LOEWDIN_DONE) != 0;
-    g.eri_s4 = (flags & EVC_FLAG_ERI_S4) ? 1 : 0;
-    return phase_hamiltonian(t, g, w, true, as_stream(stream), rows_out, ld_rows_out);
-}
-
-extern "C" int evc_phase_solve_batch(const evc_trdm_set *t, const evc_geometry_batch *gb, const double *h2rows_all,
-                                     int64_t ld_rows_all, const evc_outputs_batch *ob, int nroots, int flags,
-                                     void *ws, size_t ws_bytes, void *stream) {
-    clear_kernels(1u << EVC_PROF_SUBSPACE);
-    Ws w;
-    Geo g;
-    Out o;
-    if (setup_batch("evc_phase_solve_batch", t, gb, ob, false, ws, ws_bytes, w, g, o)) return -1;
-    EVC_REQUIRE(ob && ob->energy && ob->coeffs, "batch outputs.energy/coeffs are required");
-    EVC_REQUIRE(nroots >= 1 && nroots <= t->ntrain, "nroots=%d out of range 1..%d", nroots, t->ntrain);
-    EVC_REQUIRE(h2rows_all && ld_rows_all >= t->rows2_total,
-                "evc_phase_solve_batch: h2rows_all NULL or ld_rows_all=%lld < rows2_total=%lld",
-                (long long)ld_rows_all, (long long)t->rows2_total);
-    replan(t, w, g.count);
-    w.warm = (flags & EVC_FLAG_WARM_START) != 0;
-    return phase_solve(t, g, h2rows_all, ld_rows_all, o, nroots, w, as_stream(stream));
-}
-
-extern "C" int evc_phase_gradient_batch(const evc_trdm_set *t, const evc_geometry_batch *gb,
-                                        const evc_outputs_batch *ob, int flags, void *ws, size_t ws_bytes,
-                                        void *stream) {
-    clear_kernels(kStagesGradient);
-    Ws w;
-    Geo g;
-    Out o;
-    if (setup_batch("evc_phase_gradient_batch", t, gb, ob, true, ws, ws_bytes, w, g, o)) return -1;
-    replan(t, w, g.count);
-    return phase_gradient(t, g, o, flags, w, as_stream(stream));
+    Geo g = geo_batch(t, gb);
+    g.geo_period = g.count;
+    return gradient_roots("evc_phase_gradient_roots_batch", t, g, coeffs, nvec, pairs, npairs, out, flags, ws, ws_bytes,
+                          stream);
 }
 
 extern "C" size_t evc_subspace_solve_ws_bytes(int T, int count) {
@@ -1594,26 +1579,16 @@ extern "C" size_t evc_grad_elec_ws_bytes(int n, int natm) {
 extern "C" int evc_grad_elec_oao(int n, const evc_geometry *g, const double *trafo, const double *one_rdm,
                                  const double *two_rdm, double *grad, void *ws, size_t ws_bytes, void *stream) {
     EVC_REQUIRE(n >= 1 && n <= kMaxOrbitals, "evc_grad_elec_oao: n=%d out of range 1..%d", n, kMaxOrbitals);
-    if (check_geometry(g, true)) return -1;
-    EVC_REQUIRE(one_rdm && two_rdm && grad && ws && aligned16(ws), "evc_grad_elec_oao: null/misaligned pointer");
+    Geo geo = geo_single(g);
+    if (check_geometry("evc_grad_elec_oao", geo, true)) return -1;
+    EVC_REQUIRE(one_rdm && two_rdm && grad, "evc_grad_elec_oao: null pointer");
     evc_trdm_set t;
     fake_set(t, n);
     Ws w;
-    carve(&t, g->natm, static_cast<char *>(ws), w);
-    EVC_REQUIRE(ws_bytes >= w.bytes, "evc_grad_elec_oao: workspace too small: %zu < %zu", ws_bytes, w.bytes);
+    if (setup("evc_grad_elec_oao", &t, geo, 0, ws, ws_bytes, 1, w)) return -1;
     hipStream_t st = as_stream(stream);
-    const Geo geo = geo_single(g);
     int rc;
-    LoewdinArgs la{};
-    la.S = g->S;
-    la.h = g->hcore;
-    la.X = w.X;
-    la.U = w.U;
-    la.s = w.s;
-    la.h1 = w.h1;
-    la.n = n;
-    la.scratch = w.B1;
-    if ((rc = launch_loewdin(la, 1, st))) return rc;
+    if ((rc = launch_loewdin(loewdin_args(n, geo, w), 1, st))) return rc;
     if (trafo) {
         // caller-supplied ao_mo_trafo (gradients_loewdin.py:271-272); its derivative is still the
         // Loewdin response of g->S, exactly as the reference computes it when none is passed (:274-277)

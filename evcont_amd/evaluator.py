@@ -562,9 +562,11 @@ def _check_nonhermitian(t: "DeviceTRDMs") -> None:
 
 class _EvaluatorBase:
     """What ``ContinuationEvaluator`` (one geometry per call) and ``BatchedEvaluator`` (``count`` geometries per call)
-    share: the workspace, the stream every call is enqueued on, and the several-roots call.  A subclass names its
-    library calls by ``_suffix`` ("" / "_batch") and the leading shape of its per-geometry arrays by ``_lead``."""
+    share: the workspace, the stream every call is enqueued on, and every library call that exists for one geometry
+    and for a batch.  A subclass names its library calls by ``_suffix`` ("" / "_batch"), the leading shape of its
+    per-geometry arrays by ``_lead`` and the form it hands rows of the subspace matrix over in by ``_rows_args``."""
     _suffix = ""
+    _nan_message = ""
 
     @property
     def _lead(self) -> tuple:
@@ -611,6 +613,68 @@ class _EvaluatorBase:
     def synchronize(self) -> None:
         self._stream().synchronize()
 
+    def _init_state(self, trdms: DeviceTRDMs, natm: int, stream, warm_start: bool) -> None:
+        self.t, self.natm, self.stream, self.warm_start = trdms, int(natm), stream, bool(warm_start)
+        self._primed = False         # the workspace holds the eigenvectors of a converged Hermitian solve (warm start)
+        self._loewdin_done = False   # phase_loewdin has run: the next phase A / full call skips the Loewdin step
+        self.lib = _lib.load()
+        self._init_workspace()
+
+    def _call(self, name: str, *args, sp: Optional[int] = None) -> None:
+        """``name + _suffix(training set, *args, workspace, its size, stream)``; raises on a non-zero return code."""
+        name += self._suffix
+        check(getattr(self.lib, name)(C.byref(self.t.cstruct), *args, self.ws.data_ptr(), self.ws_bytes,
+                                      self._sp() if sp is None else sp), name)
+
+    def _flags(self, flags: int = 0, loewdin: bool = False) -> int:
+        """Flag word of a call that solves something: ``flags`` plus the warm start when the workspace is primed, and
+        for the calls that run the Loewdin step (``loewdin``) the note that ``phase_loewdin`` has done it already."""
+        if self.warm_start and self._primed:
+            flags |= _lib.FLAG_WARM_START
+        if loewdin and self._loewdin_done:
+            flags |= _lib.FLAG_LOEWDIN_DONE
+            self._loewdin_done = False
+        return flags
+
+    def _raise_if_nan(self, e) -> None:
+        if not np.all(np.isfinite(e)):
+            raise np.linalg.LinAlgError(self._nan_message)
+
+    def _check_ao(self, ao) -> None:
+        pass
+
+    def enqueue(self, ao, nroots: int = 1, energy_only: bool = False) -> None:
+        """Enqueue one evaluation (``evc_energy_with_grad`` / ``_batch``) on this evaluator's stream; no
+        synchronisation."""
+        self._check_ao(ao)
+        _check_sym_first_call(self, ao, energy_only)
+        g = ao.cstruct()
+        flags = self._flags((_lib.FLAG_ENERGY_ONLY if energy_only else 0) | _ip1_flag(self.t, ao), loewdin=True)
+        self._call("evc_energy_with_grad", C.byref(g), C.byref(self.out), int(nroots), flags)
+        self._primed = True
+
+    # -- phase API for the pair-sharded multi-GPU host (evcont_amd/distributed.py); phase_hamiltonian: the subclasses --
+    def phase_solve(self, ao, rows_all: torch.Tensor, nroots: int = 1) -> None:
+        g = ao.cstruct()
+        self._call("evc_phase_solve", C.byref(g), *self._rows_args(rows_all, self.t.rows_total), C.byref(self.out),
+                   int(nroots), self._flags())
+        self._primed = True
+
+    def phase_gradient(self, ao, partial_rank: bool) -> None:
+        g = ao.cstruct()
+        self._call("evc_phase_gradient", C.byref(g), C.byref(self.out),
+                   (_lib.FLAG_PARTIAL_RANK if partial_rank else 0) | _ip1_flag(self.t, ao))
+
+    def _host_eigs(self, ao, rows: torch.Tensor) -> list:
+        """hermitian=False: phase B on the ``rows`` of phase A assembles H(R) of every geometry on the device as for
+        the Hermitian branch; then the reference's ``eig`` branch on the host (``_eig_nonhermitian``), one
+        (values, vectors) pair per geometry.  (The caller has run ``_check_nonhermitian`` before phase A.)"""
+        self.phase_solve(ao, rows, 1)
+        self.synchronize()
+        self._primed = False      # the workspace no longer holds a converged Hermitian solve
+        S, T = self.t.S.cpu().numpy(), self.t.T
+        return [_eig_nonhermitian(H, S, self.t.layout) for H in self.hmat.cpu().numpy().reshape(-1, T, T)]
+
     def _gradient_roots(self, ao, nroots: int, pairs, want_d: bool, want_g: bool, hermitian: bool):
         """Energies of the lowest ``nroots`` roots, then one gradient slot per root pair of ``pairs`` (default: the
         diagonal) in one pass of the gradient chain (``evc_phase_gradient_roots`` / ``_batch``).  Returns the host
@@ -637,11 +701,8 @@ class _EvaluatorBase:
         p = lambda t: (t.data_ptr() if t is not None else None)
         out = _lib.OutputsRoots(grad=p(grads), d_pred=p(D), g_pred=p(Gm))
         g = ao.cstruct()
-        name = "evc_phase_gradient_roots" + self._suffix
-        rc = getattr(self.lib, name)(C.byref(self.t.cstruct), C.byref(g), coeffs.data_ptr(), nroots, P.ctypes.data,
-                                     npairs, C.byref(out), _ip1_flag(self.t, ao) & _lib.FLAG_IP1_S2KL,
-                                     self.ws.data_ptr(), self.ws_bytes, self._sp())
-        check(rc, name)
+        self._call("evc_phase_gradient_roots", C.byref(g), coeffs.data_ptr(), nroots, P.ctypes.data, npairs,
+                   C.byref(out), _ip1_flag(self.t, ao) & _lib.FLAG_IP1_S2KL)
         self.synchronize()        # (coeffs of the eig branch live until here)
         if hermitian:
             e = self.energy[..., :nroots].cpu().numpy().copy()
@@ -662,11 +723,9 @@ class BatchedEvaluator(_EvaluatorBase):
         from the second call on the eigensolvers start from the previous call's eigenvectors (EVC_FLAG_WARM_START).
         ``energy_grad``: caller's buffer of ``count * T + count * max(natm, 1) * 3`` doubles for the energies and the
         gradients -- e.g. PINNED HOST memory, which the device writes directly (no download copy, hosted.py)."""
-        self.t, self.natm, self.count, self.stream = trdms, int(natm), int(count), stream
-        self.warm_start, self._primed = bool(warm_start), False
-        self.lib = _lib.load()
+        self.count = int(count)
+        self._init_state(trdms, natm, stream, warm_start)
         d, n, T = trdms.device, trdms.n, trdms.T
-        self._init_workspace()
         G = self.count
         # energies and gradients share one buffer: a caller that wants both on the host fetches them with ONE copy
         na = max(self.natm, 1)
@@ -686,43 +745,29 @@ class BatchedEvaluator(_EvaluatorBase):
                                      d_pred=p(self.d_pred), g_pred=p(self.g_pred), hmat=p(self.hmat))
 
     _suffix = "_batch"
+    _nan_message = "generalised eigenproblem failed for at least one geometry of the batch"
 
     @property
     def _lead(self) -> tuple:
         return (self.count,)
 
-    @staticmethod
-    def _raise_if_nan(e):
-        if not np.all(np.isfinite(e)):
-            raise np.linalg.LinAlgError("generalised eigenproblem failed for at least one geometry of the batch")
+    def _check_ao(self, aob: DeviceAOBatch) -> None:
+        assert aob.count == self.count, "batch size is fixed at construction"
+
+    def _rows_args(self, rows: torch.Tensor, need: int) -> tuple:
+        """(pointer, row stride) of a (G, >= need) matrix of subspace-matrix rows."""
+        assert rows.dtype == F64 and rows.dim() == 2 and rows.shape[0] == self.count
+        assert rows.stride(1) == 1 and rows.shape[1] >= need
+        return rows.data_ptr(), int(rows.stride(0))
 
     def phase_loewdin(self, aob: DeviceAOBatch, stream: Optional["torch.cuda.Stream"] = None) -> None:
         """Loewdin orthogonalisation of the batch alone (reads S and hcore only): the next ``enqueue`` of the SAME
         geometries skips it (``EVC_FLAG_LOEWDIN_DONE``).  ``stream``: enqueue it there instead of on this
         evaluator's stream (the caller orders the streams)."""
-        assert aob.count == self.count
+        self._check_ao(aob)
         g = aob.cstruct()
-        flags = _lib.FLAG_WARM_START if (self.warm_start and self._primed) else 0
-        sp = stream.cuda_stream if stream is not None else self._sp()
-        rc = self.lib.evc_phase_loewdin_batch(C.byref(self.t.cstruct), C.byref(g), flags, self.ws.data_ptr(),
-                                              self.ws_bytes, sp)
-        check(rc, "evc_phase_loewdin_batch")
+        self._call("evc_phase_loewdin", C.byref(g), self._flags(), sp=stream.cuda_stream if stream is not None else None)
         self._loewdin_done = True
-
-    def enqueue(self, aob: DeviceAOBatch, nroots: int = 1, energy_only: bool = False) -> None:
-        assert aob.count == self.count, "batch size is fixed at construction"
-        _check_sym_first_call(self, aob, energy_only)
-        g = aob.cstruct()
-        flags = (_lib.FLAG_ENERGY_ONLY if energy_only else 0) | _ip1_flag(self.t, aob)
-        if getattr(self, "_loewdin_done", False):
-            flags |= _lib.FLAG_LOEWDIN_DONE
-            self._loewdin_done = False
-        if self.warm_start and self._primed:
-            flags |= _lib.FLAG_WARM_START
-        rc = self.lib.evc_energy_with_grad_batch(C.byref(self.t.cstruct), C.byref(g), C.byref(self.out), int(nroots),
-                                                 flags, self.ws.data_ptr(), self.ws_bytes, self._sp())
-        check(rc, "evc_energy_with_grad_batch")
-        self._primed = True
 
     def energies_with_grads(self, aob: DeviceAOBatch):
         """(E[G], grad[G,A,3]) as numpy arrays."""
@@ -732,37 +777,17 @@ class BatchedEvaluator(_EvaluatorBase):
         self._raise_if_nan(e)
         return e, self.grad[:, : self.natm].cpu().numpy().copy()
 
-    # -- phase API for the pair-sharded multi-GPU host (evcont_amd/distributed.py) -----------------
     def phase_hamiltonian(self, aob: DeviceAOBatch, rows_out: torch.Tensor) -> None:
         """Scaled two-body rows of this rank's pairs -> ``rows_out[g, :rows_local]`` (row stride = rows_out.stride(0))."""
-        assert rows_out.dtype == F64 and rows_out.dim() == 2 and rows_out.shape[0] == self.count
-        assert rows_out.stride(1) == 1 and rows_out.shape[1] >= self.t.rows_local
+        rows = self._rows_args(rows_out, self.t.rows_local)
         _check_sym_first_call(self, aob)
         g = aob.cstruct()
-        flags = _ip1_flag(self.t, aob) & _lib.FLAG_ERI_S4
-        if getattr(self, "_loewdin_done", False):
-            flags |= _lib.FLAG_LOEWDIN_DONE
-            self._loewdin_done = False
-        if self.warm_start and self._primed:
-            flags |= _lib.FLAG_WARM_START
-        rc = self.lib.evc_phase_hamiltonian_batch(C.byref(self.t.cstruct), C.byref(g), flags, rows_out.data_ptr(),
-                                                  int(rows_out.stride(0)), self.ws.data_ptr(), self.ws_bytes, self._sp())
-        check(rc, "evc_phase_hamiltonian_batch")
-
-    def phase_solve(self, aob: DeviceAOBatch, rows_all: torch.Tensor, nroots: int = 1) -> None:
-        assert rows_all.dtype == F64 and rows_all.dim() == 2 and rows_all.shape[0] == self.count
-        assert rows_all.stride(1) == 1 and rows_all.shape[1] >= self.t.rows_total
-        g = aob.cstruct()
-        flags = _lib.FLAG_WARM_START if (self.warm_start and self._primed) else 0
-        rc = self.lib.evc_phase_solve_batch(C.byref(self.t.cstruct), C.byref(g), rows_all.data_ptr(),
-                                            int(rows_all.stride(0)), C.byref(self.out), int(nroots), flags,
-                                            self.ws.data_ptr(), self.ws_bytes, self._sp())
-        check(rc, "evc_phase_solve_batch")
-        self._primed = True
+        self._call("evc_phase_hamiltonian", C.byref(g),
+                   self._flags(_ip1_flag(self.t, aob) & _lib.FLAG_ERI_S4, loewdin=True), *rows)
 
     # -- several roots of every geometry (evc_phase_gradient_roots_batch) -----------------------------------------
     def _host_coeffs(self, aob: DeviceAOBatch, nroots: int):
-        """hermitian=False: H(R) of every geometry assembled on the device, the T x T pencils solved on the host as
+        """hermitian=False: the T x T pencil of every geometry solved on the host as
         ``ContinuationEvaluator._host_coeffs`` does; returns host E (G, nroots), C (G, nroots, T) and the device
         (G, T, T) coefficient blocks the gradient call reads."""
         _check_nonhermitian(self.t)
@@ -772,18 +797,14 @@ class BatchedEvaluator(_EvaluatorBase):
             self.out.hmat = self.hmat.data_ptr()
         rows = torch.zeros((G, max(self.t.rows_total, 1)), dtype=F64, device=d)
         self.phase_hamiltonian(aob, rows)
-        self.phase_solve(aob, rows, 1)
-        self.synchronize()
-        H, S = self.hmat.cpu().numpy(), self.t.S.cpu().numpy()
         enuc = aob.enuc.cpu().numpy()
         E = np.zeros((G, nroots))
         Cs = np.zeros((G, nroots, T))
-        for g in range(G):
-            e, c = _select(*_eig_nonhermitian(H[g], S, self.t.layout), nroots, False)
+        for g, eig in enumerate(self._host_eigs(aob, rows)):
+            e, c = _select(*eig, nroots, False)
             E[g], Cs[g] = np.asarray(e, dtype=np.float64) + enuc[g], c
         blocks = np.zeros((G, T, T))
         blocks[:, :nroots] = Cs
-        self._primed = False      # the workspace no longer holds a converged Hermitian solve
         return E, Cs, torch.from_numpy(blocks).to(d)
 
     def multistate_energies_with_grads(self, aob: DeviceAOBatch, nroots: int, pairs=None,
@@ -803,13 +824,6 @@ class BatchedEvaluator(_EvaluatorBase):
             res += (D.transpose(0, 1).cpu().numpy().copy(),
                     Gm.transpose(0, 1).cpu().numpy().copy().reshape(self.count, Gm.shape[0], -1))
         return res
-
-    def phase_gradient(self, aob: DeviceAOBatch, partial_rank: bool) -> None:
-        g = aob.cstruct()
-        rc = self.lib.evc_phase_gradient_batch(C.byref(self.t.cstruct), C.byref(g), C.byref(self.out),
-                                               (_lib.FLAG_PARTIAL_RANK if partial_rank else 0) | _ip1_flag(self.t, aob),
-                                               self.ws.data_ptr(), self.ws_bytes, self._sp())
-        check(rc, "evc_phase_gradient_batch")
 
 
 class PipelinedBatchedEvaluator:
@@ -888,14 +902,8 @@ class ContinuationEvaluator(_EvaluatorBase):
         ``warm_start``: consecutive calls are steps of one trajectory (``EVC_FLAG_WARM_START``): from the
         second call on, the two Jacobi eigensolvers start from the eigenvectors the previous call left in the
         workspace.  Same results to solver tolerance (~1e-14), not bit for bit."""
-        self.t = trdms
-        self.natm = int(natm)
-        self.stream = stream
-        self.warm_start = bool(warm_start)
-        self._primed = False
-        self.lib = _lib.load()
+        self._init_state(trdms, natm, stream, warm_start)
         d, n, T = trdms.device, trdms.n, trdms.T
-        self._init_workspace()
         self.energy = torch.zeros(T, dtype=F64, device=d)
         self.coeffs = torch.zeros((T, T), dtype=F64, device=d)
         self.grad = torch.zeros((max(self.natm, 1), 3), dtype=F64, device=d)
@@ -906,19 +914,14 @@ class ContinuationEvaluator(_EvaluatorBase):
                            d_pred=self.d_pred.data_ptr(),
                            g_pred=(self.g_pred.data_ptr() if want_two_rdm else None), hmat=self.hmat.data_ptr())
 
-    # -- single-device fused path -------------------------------------------------------------
-    def enqueue(self, ao: DeviceAO, nroots: int = 1, energy_only: bool = False) -> None:
-        """Enqueue one evaluation on torch's current stream; no synchronisation."""
-        _check_sym_first_call(self, ao, energy_only)
-        g = ao.cstruct()
-        flags = (_lib.FLAG_ENERGY_ONLY if energy_only else 0) | _ip1_flag(self.t, ao)
-        if self.warm_start and self._primed:
-            flags |= _lib.FLAG_WARM_START
-        rc = self.lib.evc_energy_with_grad(C.byref(self.t.cstruct), C.byref(g), C.byref(self.out), int(nroots), flags,
-                                           self.ws.data_ptr(), self.ws_bytes, self._sp())
-        check(rc, "evc_energy_with_grad")
-        self._primed = True
+    # scipy.linalg.eigh raises LinAlgError when S is not positive definite (evcont.py:75)
+    _nan_message = "generalised eigenproblem failed: overlap matrix not positive definite or non-finite input"
 
+    def _rows_args(self, rows: torch.Tensor, need: int) -> tuple:
+        assert rows.dtype == F64 and rows.numel() == need and rows.is_contiguous()
+        return (rows.data_ptr(),)
+
+    # -- single-device fused path -------------------------------------------------------------
     def energy_with_grad(self, ao: DeviceAO, return_density_matrices: bool = False):
         self.enqueue(ao, 1, False)
         self.synchronize()
@@ -939,43 +942,23 @@ class ContinuationEvaluator(_EvaluatorBase):
         self._raise_if_nan(e[0])
         return e, self.coeffs.reshape(-1)[: nroots * self.t.T].reshape(nroots, self.t.T).cpu().numpy().copy()
 
-    @staticmethod
-    def _raise_if_nan(e):
-        if not np.isfinite(e):
-            # scipy.linalg.eigh raises LinAlgError when S is not positive definite (evcont.py:75)
-            raise np.linalg.LinAlgError("generalised eigenproblem failed: overlap matrix not positive definite "
-                                        "or non-finite input")
-
     # -- phase API for the pair-sharded multi-GPU host (evcont_amd/distributed.py) -----------------
     def phase_hamiltonian(self, ao: DeviceAO) -> torch.Tensor:
         """Returns a view of this rank's scaled two-body rows (length rows_local) in the workspace."""
         _check_sym_first_call(self, ao)
         g = ao.cstruct()
         p_rows, p_h1 = C.c_void_p(), C.c_void_p()
-        flags = _ip1_flag(self.t, ao) & _lib.FLAG_ERI_S4
-        if self.warm_start and self._primed:
-            flags |= _lib.FLAG_WARM_START
+        flags = self._flags(_ip1_flag(self.t, ao) & _lib.FLAG_ERI_S4, loewdin=True)
         rc = self.lib.evc_phase_hamiltonian(C.byref(self.t.cstruct), C.byref(g), flags, self.ws.data_ptr(),
                                             self.ws_bytes, C.byref(p_rows), C.byref(p_h1), self._sp())
         check(rc, "evc_phase_hamiltonian")
         off = p_rows.value - self.ws.data_ptr()
         return self.ws[off: off + 8 * self.t.rows_local].view(F64)
 
-    def phase_solve(self, ao: DeviceAO, rows_all: torch.Tensor, nroots: int = 1) -> None:
-        g = ao.cstruct()
-        assert rows_all.dtype == F64 and rows_all.numel() == self.t.rows_total and rows_all.is_contiguous()
-        flags = _lib.FLAG_WARM_START if (self.warm_start and self._primed) else 0
-        rc = self.lib.evc_phase_solve(C.byref(self.t.cstruct), C.byref(g), rows_all.data_ptr(), C.byref(self.out),
-                                      int(nroots), flags, self.ws.data_ptr(), self.ws_bytes, self._sp())
-        check(rc, "evc_phase_solve")
-        self._primed = True
-
     def phase_set_coeffs(self, coeffs: torch.Tensor) -> None:
         """Row weights of the predicted RDMs from a caller-supplied coefficient vector (``evc_phase_set_coeffs``)."""
         assert coeffs.dtype == F64 and coeffs.numel() == self.t.T and coeffs.is_contiguous()
-        rc = self.lib.evc_phase_set_coeffs(C.byref(self.t.cstruct), coeffs.data_ptr(), self.natm, self.ws.data_ptr(),
-                                           self.ws_bytes, self._sp())
-        check(rc, "evc_phase_set_coeffs")
+        self._call("evc_phase_set_coeffs", coeffs.data_ptr(), self.natm)
 
     def energy_with_grad_nonhermitian(self, ao: DeviceAO, return_density_matrices: bool = False):
         """``get_energy_with_grad(..., hermitian=False)`` (``ab_initio_gradients_loewdin.py:341-379`` with the ``eig``
@@ -987,7 +970,6 @@ class ContinuationEvaluator(_EvaluatorBase):
         self.phase_set_coeffs(torch.from_numpy(vec).to(self.t.device))
         self.phase_gradient(ao, False)
         self.synchronize()
-        self._primed = False      # the workspace no longer holds a converged Hermitian solve
         g = self.grad[: self.natm].cpu().numpy().copy()
         if return_density_matrices:
             if self.g_pred is None:
@@ -999,10 +981,7 @@ class ContinuationEvaluator(_EvaluatorBase):
         """hermitian=False: H(R) assembled on the device as for the Hermitian branch, then the reference's ``eig``
         branch on the host (``_eig_nonhermitian``)."""
         _check_nonhermitian(self.t)
-        rows = self.phase_hamiltonian(ao)
-        self.phase_solve(ao, rows, 1)
-        self.synchronize()
-        return _eig_nonhermitian(self.hmat.cpu().numpy(), self.t.S.cpu().numpy(), self.t.layout)
+        return self._host_eigs(ao, self.phase_hamiltonian(ao))[0]
 
     # -- several roots of one geometry (evc_phase_gradient_roots) ------------------------------------------
     def _host_coeffs(self, ao: DeviceAO, nroots: int):
@@ -1010,7 +989,6 @@ class ContinuationEvaluator(_EvaluatorBase):
         ascending); returns host E (nroots,), C (nroots, T) and the device copy of C the gradient call reads."""
         e, c = _select(*self._host_eig(ao), nroots, False)
         c = np.ascontiguousarray(c, dtype=np.float64)
-        self._primed = False      # the workspace no longer holds a converged Hermitian solve
         return np.asarray(e, dtype=np.float64) + ao.enuc, c, torch.from_numpy(c).to(self.t.device)
 
     def _roots(self, ao: DeviceAO, nroots: int, pairs, want_d: bool, want_g: bool, hermitian: bool):
@@ -1036,10 +1014,3 @@ class ContinuationEvaluator(_EvaluatorBase):
         if return_density_matrices:
             return e, c, gr, D.cpu().numpy(), G.cpu().numpy()
         return e, c, gr
-
-    def phase_gradient(self, ao: DeviceAO, partial_rank: bool) -> None:
-        g = ao.cstruct()
-        rc = self.lib.evc_phase_gradient(C.byref(self.t.cstruct), C.byref(g), C.byref(self.out),
-                                         (_lib.FLAG_PARTIAL_RANK if partial_rank else 0) | _ip1_flag(self.t, ao),
-                                         self.ws.data_ptr(), self.ws_bytes, self._sp())
-        check(rc, "evc_phase_gradient")
