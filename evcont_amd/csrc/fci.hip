@@ -468,8 +468,8 @@ extern "C" int evc_fci_trdm_rows(int norb, int64_t na, int64_t nb, const int32_t
             Pm, g1, norb, s.npad, s.nblk, dm2 + (int64_t)i * n2 * n2);
         EVC_LAUNCH_CHECK("fci_trdm_reduce2_kernel");
     }
-    note_kernel(EVC_PROF_FCI_TRDM, "fci_trdm_kernel<%d,%d> quadrants=%d blocks=%lld bra_resident=%d", trt, tnbw, nq * nq,
-                (long long)s.nblk, resident ? 1 : 0);
+    note_kernel(EVC_PROF_FCI_TRDM, "fci_trdm_kernel<%d,%d> quadrants=%d blocks=%lld bra_resident=%d ket_blocks=%lld", trt,
+                tnbw, nq * nq, (long long)s.nblk, resident ? 1 : 0, (long long)cb);
     return 0;
 }
 

@@ -48,7 +48,8 @@ class DeviceFCI:
         self._device = None
         self._tables = {}
         self._ws = None
-        self._vecs = {}        # id(host array) -> (host array, device tensor): CI vectors already uploaded
+        # id(host array) -> (host array, host copy of what was uploaded, device tensor): CI vectors already uploaded
+        self._vecs = {}
 
     # ---- plumbing ----------------------------------------------------------------
     def _dev(self) -> torch.device:
@@ -102,12 +103,15 @@ class DeviceFCI:
         else:
             if np.iscomplexobj(v):
                 raise EvcontHipError("DeviceFCI: complex CI vectors are not supported")
+            # A cached copy is used only while the host array still holds what was uploaded: the array may have been
+            # changed in place since (one pass over the host data per vector; a NaN anywhere compares unequal and
+            # uploads again).
             hit = self._vecs.get(id(v))
-            if hit is not None and hit[0] is v:
-                return hit[1]
+            if hit is not None and hit[0] is v and np.array_equal(hit[1], v):
+                return hit[2]
             t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(self._dev())
             if cache:
-                self._vecs[id(v)] = (v, t)
+                self._vecs[id(v)] = (v, np.array(v, copy=True), t)
         if t.numel() != na * nb:
             raise EvcontHipError(f"DeviceFCI: CI vector of {t.numel()} elements, expected {na} x {nb}")
         return t
@@ -179,7 +183,8 @@ class DeviceFCI:
 
     def trans_rdm12_rows(self, bra, kets, norb, nelec):
         """One bra against all ``kets`` in one pass: ``(ovlp (K,), dm1 (K,N,N), dm2 (K,N,N,N,N))``.  The host arrays are
-        uploaded once and remembered by identity, so the next training state does not upload the old vectors again."""
+        uploaded once and remembered by identity and content, so the next training state does not upload the old vectors
+        again, and a vector changed in place since its upload is uploaded anew."""
         nelec = _nelec(nelec)
         kets = list(kets)
         if not kets:

@@ -1,10 +1,13 @@
-"""Host-side closure of the dispatch table: every kernel the library launches (a ``hipLaunchKernelGGL`` in
-``evcont_amd/csrc/*.hip``) occurs as an expected name in ``tests/dispatch_table.py``, or is exempted below with the
-test that covers it.  Adding a kernel branch without a table row fails ``pytest -m "not gpu"``."""
+"""Host-side closure of the dispatch table: every kernel the library launches (a ``hipLaunchKernelGGL`` or a
+``name<<<`` / ``name<...><<<`` in ``evcont_amd/csrc/*.hip``) occurs as an expected name in ``tests/dispatch_table.py``
+or ``tests/fci_dispatch_table.py``, or is exempted below with the test that covers it.  Adding a kernel branch without a
+table row fails ``pytest -m "not gpu"``; so does an instantiation in the full-CI switches of ``fci.hip`` that no tested
+orbital count launches."""
 import glob
 import os
 import re
 
+import fci_dispatch_table as fci
 from dispatch_table import CASES, KNOB_CASES, STAGES
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "evcont_amd", "csrc")
@@ -33,6 +36,11 @@ EXEMPT = {
     # no caller reaches it: the pipeline asks launch_unpack8 for lead_half=1 only together with the unpacked 2-RDM,
     # which takes unpack8_kernel
     "unpack8_half_kernel": "unreachable from the entry points",
+    # full-CI entry points (csrc/fci.hip): launched around the recorded kernels by every evc_fci_trdm_rows /
+    # evc_fci_sigma call
+    "fci_trdm_reduce1_kernel": "tests.test_gpu_fci_shapes::test_every_orbital_count (every t-RDM call)",
+    "fci_trdm_reduce2_kernel": "tests.test_gpu_fci_shapes::test_every_orbital_count (every t-RDM call)",
+    "fci_sigma_prep_kernel": "tests.test_gpu_fci_shapes::test_every_orbital_count (every sigma call)",
 }
 
 
@@ -42,7 +50,35 @@ def launched_kernels():
         with open(p) as f:
             src = f.read()
         names.update(re.findall(r"hipLaunchKernelGGL\(\s*\(?\s*([A-Za-z_]\w*)", src))
+        names.update(re.findall(r"\b([A-Za-z_]\w*)\s*(?:<[^<>;(){}]*>)?\s*<<<", src))
     return names
+
+
+def fci_source():
+    with open(os.path.join(CSRC, "fci.hip")) as f:
+        return f.read()
+
+
+def function_body(src, signature):
+    """The text between the braces of the function whose definition starts with ``signature``."""
+    start = src.index(signature)
+    i = src.index("{", start)
+    depth, j = 0, i
+    while True:
+        depth += {"{": 1, "}": -1}.get(src[j], 0)
+        if depth == 0:
+            return src[i + 1:j]
+        j += 1
+
+
+def fci_table_names():
+    """Kernel names in the expected records of tests/fci_dispatch_table.py."""
+    out = {"fci_sigma_gather_kernel"}       # the second half of every sigma record
+    for n in fci.TILINGS:
+        out.update(re.findall(r"[A-Za-z_]\w*_kernel\b", fci.trdm_record(n, 1) + fci.sigma_record(n)))
+    for rec in fci.EXCITE_KERNELS.values():
+        out.update(re.findall(r"[A-Za-z_]\w*_kernel\b", rec))
+    return out
 
 
 def table_names():
@@ -105,9 +141,44 @@ def test_every_ip1_slot_count_is_in_the_table():
 def test_every_launched_kernel_is_in_the_table():
     launched = launched_kernels()
     assert len(launched) >= 40, sorted(launched)    # the parse found the launch sites
-    listed = table_names()
+    assert {"fci_trdm_kernel", "fci_sigma_gemm_kernel", "fci_excite_det_kernel", "fci_excite_orb_kernel"} <= launched
+    listed = table_names() | fci_table_names()
     missing = sorted(launched - listed - set(EXEMPT))
     assert not missing, f"kernels with neither a dispatch-table row nor an exemption: {missing}"
     stale = sorted((listed | set(EXEMPT)) - launched)
     assert not stale, f"names in the table / exemption list that no launch site has: {stale}"
     assert not (listed & set(EXEMPT)), sorted(listed & set(EXEMPT))
+
+
+def test_fci_table_is_well_formed():
+    assert sorted(fci.TILINGS) == list(range(1, 17))
+    assert {c[0] for c in fci.SHAPE_CASES} == set(fci.TILINGS)        # every orbital count has a GPU case
+    for n, t in fci.TILINGS.items():
+        nt = t["npad"] // 16
+        rt, nbw = t["trdm"]
+        assert t["npad"] % 16 == 0 and n * n <= t["npad"] < n * n + 16, n
+        nq = {1: 1, 4: 2}[t["quadrants"]]
+        assert (nq * nbw - 1) * rt < nt <= nq * nbw * rt, n           # the tiling covers the edge, no idle wave row
+        assert (t["sigma_nbw"] - 1) * t["sigma"] < nt <= t["sigma_nbw"] * t["sigma"] and t["sigma"] <= 4, n
+
+
+def test_every_fci_instantiation_is_launched_by_a_tested_orbital_count():
+    """The switches of launch_trdm and evc_fci_sigma against the table: a ``case`` added without an orbital count in
+    tests/fci_dispatch_table.py that launches it fails here, and so does a table row the switch cannot serve."""
+    src = fci_source()
+    body = function_body(src, "static void launch_trdm(")
+    cases = re.findall(r"(case\s+(\d+)|default)\s*:\s*launch_trdm_t<\s*(\d+)\s*,\s*(\d+)\s*>", body)
+    assert len(cases) == len(re.findall(r"\bcase\b|\bdefault\b", body)) >= 7, body
+    assert len(re.findall(r"launch_trdm_t<\s*\d", src)) == len(cases)      # none is launched from elsewhere
+    for _, code, rt, nbw in cases:
+        assert not code or int(code) == int(rt) * 10 + int(nbw), (code, rt, nbw)
+    switch = {(int(rt), int(nbw)) for _, _, rt, nbw in cases}
+    assert switch == fci.trdm_instantiations(), (sorted(switch), sorted(fci.trdm_instantiations()))
+    body = function_body(src, 'extern "C" int evc_fci_sigma(')
+    cases = re.findall(r"(case\s+(\d+)|default)\s*:\s*launch_sigma_gemm_t<\s*(\d+)\s*>", body)
+    assert len(cases) == len(re.findall(r"\bcase\b|\bdefault\b", body)) >= 4, body
+    assert len(re.findall(r"launch_sigma_gemm_t<\s*\d", src)) == len(cases)
+    for _, code, rt in cases:
+        assert not code or int(code) == int(rt), (code, rt)
+    switch = {int(rt) for _, _, rt in cases}
+    assert switch == fci.sigma_instantiations(), (sorted(switch), sorted(fci.sigma_instantiations()))

@@ -9,7 +9,8 @@ import pytest
 
 from evcont_amd.fci_small import SmallFCI, _excitation_ops
 
-CASES = [(4, 2), (6, 3), (6, 2), (8, 4), (5, 0), (5, 5)]
+CASES = [(4, 2), (6, 3), (6, 2), (8, 4), (5, 0), (5, 5),
+         (9, 1), (9, 2), (9, 3), (13, 1), (13, 2), (13, 3), (16, 1), (16, 2), (16, 3)]
 
 
 @pytest.mark.parametrize("norb,nocc", CASES)
@@ -35,7 +36,8 @@ def test_tables_reproduce_excitation_ops(norb, nocc):
 
 
 @pytest.mark.parametrize("norb,nelec", [(4, (2, 2)), (6, (3, 3)), (6, (3, 2)), (6, (2, 3)), (8, (4, 4)), (5, (0, 5)),
-                                        (5, (5, 0)), (5, (2, 0))])
+                                        (5, (5, 0)), (5, (2, 0)), (9, (1, 2)), (9, (3, 3)), (13, (2, 1)),
+                                        (13, (3, 2)), (16, (1, 1)), (16, (2, 2)), (16, (3, 1))])
 def test_excite_through_tables_is_excite_all_bitwise(norb, nelec):
     from evcont_amd.fci_tables import excite_through_tables, packed_table
     na, nb = packed_table(norb, nelec[0]).shape[0], packed_table(norb, nelec[1]).shape[0]
