@@ -17,7 +17,7 @@
 #pragma once
 #include "common.hpp"
 
-// (dense_small.hip includes this file inside namespace evc, behind its phase-stamp macros)
+// (subspace_small.hip includes this file inside namespace evc, behind its phase-stamp macros)
 #ifndef EVC_FEW_STAMP
 #define EVC_FEW_STAMP(i_) do { } while (0)
 #endif

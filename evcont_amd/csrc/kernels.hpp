@@ -120,8 +120,8 @@ int launch_sym_oao_t(const double *G, int64_t sG, int n, double *out, int64_t so
 int launch_unpack_sym(const double *packed, int64_t sp, int n, double *GsT, double *SB, int64_t sws, double *G,
                       int64_t sG, int count, hipStream_t st);
 // EVC_LAYOUT_SYM8: `packed` is the 8-fold compressed vector p8 of a fully symmetric 2-RDM:
-//   SB[i,j,k,l] = 4 p8(ijkl) (only for i >= j, l <= k when lead_half = 1; lead_half = 2: the dense (pair, pair)
-//   matrix SB[tri(i,j)][tri(k,l)] instead), G[i,j,k,l] = p8(ijkl) (optional)
+//   SB[i,j,k,l] = 4 p8(ijkl) (only for i >= j, l <= k when lead_half = 1, which needs G; lead_half = 2: the dense
+//   (pair, pair) matrix SB[tri(i,j)][tri(k,l)] instead), G[i,j,k,l] = p8(ijkl) (optional)
 int launch_unpack8(const double *packed, int64_t sp, int n, double *SB, int64_t sws, double *G, int64_t sG, int count,
                    int lead_half, hipStream_t st);
 // partial[b][i][a] = sum_{k in slab b} SB[i][k] * K3[k][a]: the Y2 contraction with the row-major operand
@@ -172,7 +172,6 @@ struct Ip1Args {
 constexpr int kIp1MaxSlots = 8;
 int launch_ip1_dh(const Ip1Args &a, int count, hipStream_t st);
 
-// ---- dense_small.hip ---------------------------------------------------------------
 // ---- pair64.hip: the symmetric pipeline's pair step and Y2 for 32 < n <= 64 ----------------------------
 bool pair64_applicable(const PairTransformArgs &a);
 int launch_pair_transform64(const PairTransformArgs &a, int count, hipStream_t st);
@@ -180,6 +179,8 @@ bool y2_64_applicable(int n);
 int y2_64_slabs(int n, int count);
 int launch_y2_64(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial, int64_t sws,
                  int count, hipStream_t st);
+
+// ---- loewdin.hip (loewdin.hpp: the kernel body subspace_small.hip shares) -----------------------------
 struct LoewdinArgs {
     const double *S, *h;   // + g*sS, + g*sh   (h may be NULL)
     double *X, *U, *s, *h1;  // + g*sws        (h1 may be NULL)
@@ -197,7 +198,15 @@ struct LoewdinArgs {
 };
 int launch_loewdin(const LoewdinArgs &a, int count, hipStream_t st);
 bool loewdin_split_available(int n);
-int launch_loewdin_big(const LoewdinArgs &a, int count, hipStream_t st);   // subspace_big.hip: 32 < n <= 64
+// subspace_big.hip: 32 < n <= 64 in LDS alone, up to kMaxOrbitals with a.scratch
+int launch_loewdin_big(const LoewdinArgs &a, int count, hipStream_t st);
+// Host-side knobs, read once per process (loewdin.hip).  EVC_EIGH_F32: 0 = FP64 Jacobi, 1 = FP32 Jacobi + refinement,
+// 2 (default) = FP32 tridiagonal start + refinement.  EVC_SUBSPACE_FEW (default 1): a few lowest roots through the
+// tridiagonal route, in both subspace kernels.
+int eigh_fast_enabled();
+int subspace_few_enabled();
+
+// ---- subspace_small.hip (T <= kSubspaceSmallT), subspace_big.hip (beyond) ------------------------------
 struct SolveArgs {
     const double *h1part;  // (nsp1, T*T) partial sums of the one-body rows      + g*sh1
     int nsp1;
@@ -229,14 +238,20 @@ struct SolveArgs {
     double *scratch;              // T > kSubspaceSmallT: subspace_big_scratch_doubles(T) doubles + g*sscratch
     int64_t sscratch;
 };
-constexpr int kSubspaceSmallT = 32;   // up to here: the register / 32 x 32-tile kernel of dense_small.hip
+constexpr int kSubspaceSmallT = 32;   // up to here: the register / 32 x 32-tile kernel of subspace_small.hip
 constexpr int kSubspaceMaxT = 512;    // beyond kSubspaceSmallT: subspace_big.hip (LDS-resident up to 128, then global)
-// subspace solve + the eigendecomposition half of the Loewdin step (part 2) in one launch (dense_small.hip)
+// subspace solve + the eigendecomposition half of the Loewdin step (part 2) in one launch (subspace_small.hip)
 int launch_subspace_loewdin(const SolveArgs &s, const LoewdinArgs &l, int count, hipStream_t st);
 int launch_subspace_solve(const SolveArgs &a, int count, hipStream_t st);
 // subspace_big.hip: T > kSubspaceSmallT (vstd, when given, holds Tp^2 doubles: the eigenvectors as ROWS at pitch Tp)
 size_t subspace_big_scratch_doubles(int T);
 int launch_subspace_big(const SolveArgs &a, int count, hipStream_t st);
+
+// ---- grad_tail.hip -------------------------------------------------------------------------------------
+// The layout's two-body rows are the pairs a >= b of training states (T(T+1)/2 of them) instead of all T^2.
+__host__ __device__ inline bool layout_pairs(int layout) {
+    return layout == EVC_LAYOUT_PAIR5 || layout == EVC_LAYOUT_PACK2 || layout == EVC_LAYOUT_SYM8;
+}
 // Weights of the t-RDM rows for the predicted RDMs of a GIVEN coefficient vector c[T] (gradients_loewdin.py:343-356):
 // w1[a*T+b] = c_a c_b; w2 = the slice [w2_offset, +w2_count) of the two-body row weights (pairs: 2 c_a c_b, c_a^2 on
 // the diagonal; otherwise c_a c_b).
@@ -270,7 +285,7 @@ struct GradPrepArgs {
     int geo_period;       // geo_of
 };
 int launch_grad_prep(const GradPrepArgs &a, int count, hipStream_t st);
-// grad_prep and the unpack of the packed predicted 2-RDM into the dense (pair, pair) SB in ONE launch (dense_small.hip)
+// grad_prep and the unpack of the packed predicted 2-RDM into the dense (pair, pair) SB in ONE launch
 int launch_unpack8_prep(const GradPrepArgs &a, const double *packed, int64_t sp, double *SB, int64_t sws, int count,
                         hipStream_t st);
 struct GradFinalArgs {

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void rows_reduce_kernel(const double *partial,
 // ---- the Loewdin step in two halves (n <= 64) -------------------------------------------------------------
 // The energy phase needs X = S^-1/2 and h1 only; the eigenvectors and eigenvalues of S enter at the very end of the
 // gradient (the response term, launch_grad_final).  A full call therefore computes X and h1 by Newton-Schulz on the
-// matrix cores (dense_small.hip loewdin_ns / loewdin_ns64_kernel) and keeps the eigensolver off the critical path
+// matrix cores (loewdin.hpp loewdin_ns / loewdin.hip loewdin_ns64_kernel) and keeps the eigensolver off the critical path
 // (loewdin_split_mode below): either in the launch of the subspace solve (Ws.split = 3) or on a side stream, forked at
 // the start of the call and joined by whichever call reads U and s next (Ws.split = 1):
 // one side stream per device and two events per workspace, created at the workspace's first such call; the events live
@@ -357,7 +357,7 @@ static int loewdin_split_mode(int n, int ntrain, int count, bool loewdin_done, b
     if (knob == 0 || loewdin_done || !loewdin_split_available(n)) return 0;
     // Small kernels on both sides (n <= 32 orbitals, T <= 32 states), any number of geometries, cold or warm: the
     // eigensolver half rides in the launch of the subspace solve, one workgroup per geometry beside one workgroup per
-    // geometry (dense_small.hip subspace_loewdin_kernel) -- no second stream.  One geometry per call it performs like the
+    // geometry (subspace_small.hip subspace_loewdin_kernel) -- no second stream.  One geometry per call it performs like the
     // side stream below (H30: 4 480 against 4 500 steps/s, H10: 11 170 against 11 210) without costing the process a
     // hardware queue; 32 geometries per call on one stream: 60 700 -> 64 500 geometries/s, three streams unchanged.
     if (n <= kPairTransformMaxN && ntrain <= kSubspaceSmallT) return 3;

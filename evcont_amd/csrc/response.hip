@@ -5,7 +5,7 @@
 //   get_one_el_grad               (:155-187)  -> evc_one_el_grad             (N,N,A,3)
 //   two_el_grad                   (:190-252)  -> evc_two_el_grad             (A,3)
 // The fused energy+force path never materialises these (it uses the adjoint form in
-// dense_small.hip); they exist so that scripts calling the pieces get device results too.
+// grad_tail.hip); they exist so that scripts calling the pieces get device results too.
 #include <string.h>
 
 #include "common.hpp"

@@ -1,7 +1,7 @@
 // K6 for LARGE training sets (T > 32): the subspace generalised eigenproblem H c = E S c of
 // ab_initio_eigenvector_continuation.py:73-88 / :157-173 with LAPACK dsygvd semantics (lower triangles,
 // Cholesky of S, c^T S c = 1) and the row weights of ab_initio_gradients_loewdin.py:343-356, for training sets the
-// register / 32 x 32-tile kernel of dense_small.hip cannot hold.  The reference puts no bound on T (its Zundel
+// register / 32 x 32-tile kernel of subspace_small.hip cannot hold.  The reference puts no bound on T (its Zundel
 // learning curve evaluates 80 and 100 training states, scripts/MD/Zundel_thermodynamics/continuation/
 // 05_Zundel_test_potential_energy.py:182-210; converge_EVCont_MD grows T without bound, MD_utils.py:128-502).
 //
@@ -801,7 +801,7 @@ __global__ __launch_bounds__(kBT) void subspace_big_kernel(SolveArgs a) {
 // ------------------------------------------------------------------ Loewdin orthogonalisation, 32 < n <= 64
 // S = U diag(s) U^T by the same one-sided Jacobi (S is positive definite: no shift), X = U diag(s > 1e-15 ? s^-1/2 : 0) U^T,
 // h1 = X^T h X (electron_integral_utils.py:6-18,135; gradients_loewdin.py:336-338), three matrices in LDS.  Replaces the
-// two-sided LDS Jacobi of dense_small.hip for these sizes (1.4 ms at n = 58: cc-pVTZ water).
+// two-sided LDS Jacobi of eigh_small.hpp for these sizes (1.4 ms at n = 58: cc-pVTZ water).
 __global__ __launch_bounds__(kBT) void loewdin_big_kernel(LoewdinArgs a) {
     extern __shared__ __align__(16) double sm[];
     const int n = a.n, m = (n + 1) & ~1, Tp = (n + 15) & ~15, Pj = (m + 31) & ~31;
@@ -944,9 +944,7 @@ size_t subspace_big_scratch_doubles(int T) {
 
 int launch_subspace_big(const SolveArgs &a_in, int count, hipStream_t st) {
     SolveArgs a = a_in;
-    // EVC_SUBSPACE_FEW=0: every call through the Jacobi sweeps (A/B timing, tests of that path)
-    static const int few_on = getenv("EVC_SUBSPACE_FEW") ? atoi(getenv("EVC_SUBSPACE_FEW")) : 1;
-    a.few = few_on;
+    a.few = subspace_few_enabled();
     if (!a.scratch) {
         set_error("subspace solve: T=%d needs a scratch buffer (evc_subspace_solve_ws_bytes)", a.T);
         return -1;

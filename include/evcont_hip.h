@@ -115,8 +115,9 @@ int evc_four_index_transform(const double *in, const double *C, int c_transposed
                              double *out, double *tmp, double *three_quarter, void *stream);
 
 /* ---------------------------------------------------------------------------------
- * K1/K2  Loewdin orthogonalisation on one workgroup (Jacobi eigensolver: one-sided on one wave, started in FP32 and
- *        refined in FP64, for n <= 32; two-sided in LDS beyond)
+ * K1/K2  Loewdin orthogonalisation, one workgroup per matrix.  n <= 32: eigensolver started in FP32 (tridiagonal or
+ *        one-sided Jacobi on one wave) and refined in FP64; 32 < n <= 64: one-sided Jacobi on 16 waves; 64 < n <= 80
+ *        through this entry point (no scratch buffer): two-sided Jacobi in LDS
  *   S = U diag(s) U^T ; X = U diag(s>1e-15 ? s^-1/2 : 0) U^T ; h1 = X^T hcore X
  *   replaces get_loewdin_trafo (electron_integral_utils.py:6-18) and the h1 rotation
  *   (:135, ab_initio_gradients_loewdin.py:338).  hcore/h1 may be NULL.  n <= 80 (96 inside the fused pipeline, which lends

@@ -33,9 +33,6 @@ EXEMPT = {
     "dx_tensor_kernel": "tests.test_gpu_api::test_gradient_module_blocks (csrc/response.hip)",
     "one_el_grad_kernel": "tests.test_gpu_api::test_gradient_module_blocks (csrc/response.hip)",
     "contract_kernel": "tests.test_gpu_api::test_gradient_module_blocks (csrc/response.hip)",
-    # no caller reaches it: the pipeline asks launch_unpack8 for lead_half=1 only together with the unpacked 2-RDM,
-    # which takes unpack8_kernel
-    "unpack8_half_kernel": "unreachable from the entry points",
     # full-CI entry points (csrc/fci.hip): launched around the recorded kernels by every evc_fci_trdm_rows /
     # evc_fci_sigma call
     "fci_trdm_reduce1_kernel": "tests.test_gpu_fci_shapes::test_every_orbital_count (every t-RDM call)",

@@ -135,7 +135,9 @@ def test_quarter_transform_asymmetric(n, dev):
     np.testing.assert_allclose(full, ref, rtol=0, atol=1e-11 * n * n)
 
 
-@pytest.mark.parametrize("n", [2, 5, 20, 30, 31, 58])
+# 65 and 80: the LDS-only kernel beyond 64 orbitals (evc_loewdin passes no scratch): two-sided LDS Jacobi and the vector
+# small products.  65 is odd (m = 66 carries the decoupled dummy dimension), 80 is the ABI limit (~154 KB of LDS).
+@pytest.mark.parametrize("n", [2, 5, 20, 30, 31, 58, 65, 80])
 def test_loewdin_sizes(n, dev):
     from evcont_amd import ops
     rng = np.random.default_rng(n)
@@ -143,9 +145,29 @@ def test_loewdin_sizes(n, dev):
     S = B @ B.T / n + np.eye(n)
     X, U, s = ops.loewdin(up(S, dev))
     Xn = X.cpu().numpy()
-    np.testing.assert_allclose(Xn @ S @ Xn, np.eye(n), rtol=0, atol=1e-12)
     w = np.linalg.eigvalsh(S)
+    print(f"loewdin n={n}: |XSX-I|={np.abs(Xn @ S @ Xn - np.eye(n)).max():.3e} "
+          f"|s-eigvalsh|={np.abs(np.sort(s.cpu().numpy()) - w).max():.3e}")
+    np.testing.assert_allclose(Xn @ S @ Xn, np.eye(n), rtol=0, atol=1e-12)
     np.testing.assert_allclose(np.sort(s.cpu().numpy()), w, rtol=0, atol=1e-13 * n)
+
+
+def test_loewdin_hcore_65(dev):
+    """h1 = X h X of the LDS-only kernel beyond 64 orbitals (the vector-product tail of loewdin_body), against numpy
+    on the returned X, at the h1 tolerance of test_loewdin_and_integrals_golden."""
+    from evcont_amd import ops
+    n = 65
+    rng = np.random.default_rng(6500)
+    B = rng.standard_normal((n, n))
+    S = B @ B.T / n + np.eye(n)
+    h = rng.standard_normal((n, n))
+    h = 0.5 * (h + h.T)
+    X, U, s, h1 = ops.loewdin(up(S, dev), up(h, dev))
+    Xn = X.cpu().numpy()
+    print(f"loewdin hcore n={n}: |XSX-I|={np.abs(Xn @ S @ Xn - np.eye(n)).max():.3e} "
+          f"|h1-XhX|={np.abs(h1.cpu().numpy() - Xn @ h @ Xn).max():.3e}")
+    np.testing.assert_allclose(Xn @ S @ Xn, np.eye(n), rtol=0, atol=1e-12)
+    np.testing.assert_allclose(h1.cpu().numpy(), Xn @ h @ Xn, rtol=0, atol=1e-12)
 
 
 # ------------------------------------------------------------------ subspace problem

@@ -24,7 +24,7 @@ def dbg(tag):
     if not hasattr(lib, "evc_debug_read"):      # product library: no stamps
         return
     st = (C.c_longlong * 64)(); va = (C.c_double * 64)()
-    fn = lib.evc_debug_read; fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    fn = lib.evc_debug_read_subspace if tag == "subspace" else lib.evc_debug_read; fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     fn(st, va, 64)
     t = [ (st[i] - st[0]) / 100.0 for i in range(14)]
     print(tag, 'eigh: Af ready %.1f, start vectors %.1f (householder %.1f, multisection %.1f, vectors %.1f), refine passes %s, done %.1f' % (t[1], t[2], t[11], t[12], t[13], [round(t[i],1) for i in (3,4,5)], t[10]))
