@@ -102,6 +102,13 @@ int launch_pair_transform_dma(const PairTransformArgs &a, int count, hipStream_t
 bool y2_dma_applicable(int n);
 int launch_y2_dma(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial, int64_t sws,
                   int count, int slabs, int tiles_per_wg, int ppt, hipStream_t st);
+// Y2 inside the first gradient-side pair step (y2d_kernel<1>): the launch `a` describes (dense (pair, pair) SB in, ct = 1,
+// R out as ptd_kernel<0> writes it) and, from the H = SB_v X it forms, Y2 with M1 (pitch a.in_ld, geometry stride sws)
+// into y2_pairstep_slabs(n, count) slabs of `partial`.  EVC_Y2_PAIRSTEP=0 turns it off (read once per process).
+bool y2_pairstep_applicable(const PairTransformArgs &a, const double *M1, int64_t sws, int count);
+int y2_pairstep_slabs(int n, int count);
+int launch_y2_pairstep(const PairTransformArgs &a, const double *M1, double *partial, int64_t sws, int count,
+                       hipStream_t st);
 int launch_pack(const double *h2, int64_t sh2, int n, double diag_mult, double *out, int64_t sout, int64_t out_len,
                 int count, hipStream_t st);
 // 8-fold compressed vector of a tensor with the index symmetries of real two-electron integrals:

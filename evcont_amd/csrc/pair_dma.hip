@@ -40,6 +40,13 @@ constexpr unsigned kPdStage = 4 * kPdRB;          // byte offset of the stage (a
 constexpr unsigned kPdP = 3872;                   // slot pitch of the stage: >= 8 (465 + 16) bytes, = 32 mod 128
 constexpr unsigned kPdTab = kPdStage + 16 * kPdP;   // MODE 1: multiplicity of pair u (1 on the diagonal i == j, else 2), 512 floats
 constexpr unsigned kPdLds = kPdTab, kPdLds1 = kPdTab + 512 * 4;
+// The pair step that also contracts Y2 (y2d_kernel<1>): the M1 rows of the four waves behind their SB rows, the stage
+// behind those, and per wave a 32 x 32 square (pitch 34 doubles: its fragment reads are conflict free) through which
+// H goes from its accumulator form to the A-operand form.  130 KB: one workgroup per CU.
+constexpr unsigned kPdStageY = 8 * kPdRB;
+constexpr unsigned kPdSqP = 34, kPdSqB = 32 * kPdSqP * 8;
+constexpr unsigned kPdSq = kPdStageY + 16 * kPdP;
+constexpr unsigned kPdLdsY = kPdSq + 4 * kPdSqB;
 
 __device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -75,6 +82,15 @@ __device__ __forceinline__ void wait_vm_dyn(int k) {
     else if (k == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
 }
+// the same for 0..8 (the pair step with Y2 has the DMA of a second row among the younger instructions)
+__device__ __forceinline__ void wait_vm_dyn8(int k) {
+    if (k <= 3) wait_vm_dyn(k);
+    else if (k == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else if (k == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    else if (k == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else if (k == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+}
 
 // (memory, LDS and scalar instructions at a higher priority than the MFMAs: a wave that issues MFMAs back to back
 //  otherwise keeps the issue port from its SIMD mate's loads and stores, profiles/mfma_f64_coissue.txt)
@@ -86,15 +102,35 @@ __device__ __forceinline__ void wait_vm_dyn(int k) {
 
 }  // namespace
 
+// arguments of y2d_kernel: the Y2 contraction alone, or what it adds to the first gradient-side pair step
+struct Y2dArgs {
+    const double *SB, *M1, *X;   // rows v of SB and of the first pair step's intermediate, pitch pair_ld(n); X (n, n)
+    double *partial;             // [slab][n][n] per geometry
+    int64_t sX, sws;
+    int n, tiles_per_wg, ppt;
+};
+
 // MODE 0: dense (pair, pair) result out[tri(r',s')][tri(p,q)], pitch out_ld.
 // MODE 1: the 8-fold compressed packed vector packed[tri(u, v)], u = tri(r',s') >= v = tri(p,q), times the
 //         multiplicities of both pairs (and diag_mult on u == v): the write-out walks the rows u = ur + 64 k from 0 with
 //         lane-constant offsets tri(u) and skips the passes above the diagonal (k < v / 64, wave-uniform); the pass that
 //         holds the diagonal takes a slower, predicated body, once per tile.  Its stores vary from tile to tile, so here
 //         the wait for an operand row is vmcnt(0) (the stores behind it are a phase old by then).
-template <int MODE>
-__global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
+//
+// Y2 (MODE 0, the first gradient-side step, ct = 1): the H = M_e X this step forms is T_e X^T of the Y2 contraction
+//   Y2 = sum_e mult(e) T_e X^T M1_e   (ab_initio_gradients_loewdin.py:210-232),
+// so a third phase per matrix adds (mult(e) / 2) H M1_e to one accumulator set (a wave-uniform branch on the scalar
+// (p, q) of the pair takes the diagonal pairs apart) -- 32 MFMAs instead of the 64 of a kernel of its own, and SB is
+// read once.  H leaves the MFMAs as an accumulator (rows on registers and lane groups), which serves X^T H as its
+// B operand; H M1_e wants it as the A operand (rows on lanes): the wave writes it into its LDS square during the first
+// N-phase steps and reads the fragments back during the last ones, all at lane-constant addresses.  The M1 row comes
+// by LDS-DMA into a second row of the wave: fragments read during the Y phase, the next row requested behind them.
+// Every counted wait gets the DMA instructions and stores that are younger than the row it waits for.
+template <int MODE, bool Y2>
+__device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dArgs &y) {
     constexpr int KS = 8, NT = 2;
+    constexpr unsigned kPdStage = Y2 ? kPdStageY : evc::kPdStage;   // (shadows the namespace constant)
+    static_assert(!Y2 || MODE == 0, "the Y2 phase belongs to the dense step");
     extern __shared__ __align__(16) char lds[];   // the only LDS of this kernel: it starts at LDS address 0
     const int n = a.n;
     const int npairs = n * (n + 1) / 2;
@@ -104,7 +140,13 @@ __global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
     const double *__restrict__ C = a.C + g * a.sC;
     const int ntiles = (npairs + 7) / 8;
     const int t_begin = blockIdx.x * a.tiles_per_wg, t_end = min(ntiles, t_begin + a.tiles_per_wg);
-    if (t_begin >= t_end) return;
+    if (t_begin >= t_end) {
+        if constexpr (Y2) {   // (every workgroup writes its slab)
+            double *dst = y.partial + g * y.sws + (int64_t)blockIdx.x * n * n;
+            for (int idx = threadIdx.x; idx < n * n; idx += 256) dst[idx] = 0.0;
+        }
+        return;
+    }
     const int niter = 2 * (t_end - t_begin);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -142,6 +184,20 @@ __global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
             if ((int)u < npieces) glds16(vo[u], src, rowb + 1024u * u);
     };
     dma_row(e0);
+    // Y2: the M1 row of the same pair (rows on 16-byte granules: the launch checks it, the window is the SB row's)
+    [[maybe_unused]] const double *__restrict__ M1 = Y2 ? y.M1 + g * y.sws : nullptr;
+    constexpr unsigned kRowM = 4 * kPdRB;   // the wave's M1 row: this far behind its SB row
+    [[maybe_unused]] auto dma_mrow = [&](int e) {
+        const int ec = e < npairs ? e : wave;
+        const char *src = reinterpret_cast<const char *>(M1 + (int64_t)ec * in_ld);
+#pragma unroll
+        for (unsigned u = 0; u < kPdRaw; ++u)
+            if ((int)u < npieces) glds16(vo[u], src, rowb + kRowM + 1024u * u);
+    };
+    if constexpr (Y2) {
+        if (lane < 8) *reinterpret_cast<double *>(lds + rowb + kRowM + kPdRaw * 1024 + 8 * lane) = 0.0;
+        dma_mrow(e0);
+    }
 
     // the X fragments straight from global memory (16 rows of 128 bytes per load instruction)
     double xf[KS][NT];
@@ -207,6 +263,30 @@ __global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
     for (int c = 1; c < 4; ++c) {
         cntA += (64 * c < wrows) ? 1 : 0;
         cntB += (64 * (4 + c) < wrows) ? 1 : 0;
+    }
+    // the H square of the wave: written as the accumulator holds it (row 4 reg + l4 of a tile, column l15), read as
+    // A fragments (row l15, column 4 kk + l4)
+    // (a base per 2 KB: the compiler pairs these accesses into ds_write2 / ds_read2, whose offsets reach that far, and
+    //  otherwise forms the bases with vector adds inside the loop)
+    [[maybe_unused]] unsigned sqw[4] = {0, 0, 0, 0}, sqr[2] = {0, 0};
+    if constexpr (Y2) {
+        const unsigned sq = kPdSq + (unsigned)wave * kPdSqB;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) sqw[b] = opaque(sq + 8u * (unsigned)((l4 + 8 * b) * (int)kPdSqP + l15));
+#pragma unroll
+        for (int b = 0; b < 2; ++b) sqr[b] = opaque(sq + 8u * (unsigned)((l15 + 16 * b) * (int)kPdSqP + l4));
+    }
+    [[maybe_unused]] double mb[NT][KS], ha[NT][KS];   // fragments of M1_e (B operand) and of H (A operand)
+    [[maybe_unused]] d4 yy[NT][NT];   // sum_e (mult(e) / 2) H_e M1_e
+    // (p, q) of the wave's pair, advanced by 4 per matrix with scalar arithmetic: on the diagonal <=> q == p
+    [[maybe_unused]] int pp = 0, qq = 0;
+    if constexpr (Y2) {
+        pp = __builtin_amdgcn_readfirstlane(tri_row_small(e0 < npairs ? e0 : 0));
+        qq = (e0 < npairs ? e0 : 0) - pp * (pp + 1) / 2;
+#pragma unroll
+        for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+            for (int ta = 0; ta < NT; ++ta) yy[ti][ta] = (d4){0.0, 0.0, 0.0, 0.0};
     }
 
     double mf[NT][KS];
@@ -303,7 +383,10 @@ __global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
                         if (m == 0) {
                             // the operand row of matrix i+1 (requested one iteration ago) has landed -> fragments;
                             // then the row of matrix i+2 is requested into the same LDS row
-                            if (kk == 0) wait_vm_dyn(K);
+                            if (kk == 0) {
+                                if constexpr (Y2) wait_vm_dyn8(i == 0 ? 0 : K + npieces);   // (+ the M1 row requested behind the last Y phase)
+                                else wait_vm_dyn(K);
+                            }
                             if (kk < 2) {
 #pragma unroll
                                 for (int k2 = 0; k2 < KS; ++k2)
@@ -313,6 +396,27 @@ __global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
                                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                                 dma_row(e0 + 4 * (i + 2));
                             }
+                        }
+                    }
+                    if constexpr (COMPUTE && Y2) {
+                        if (m == 1) {
+                            if (kk < 4) {   // tile kk of H into the square
+#pragma unroll
+                                for (int reg = 0; reg < 4; ++reg)
+                                    lds_st(sqw[2 * (kk / 2) + reg / 2] + 8u * (4u * (reg % 2) * kPdSqP + 16u * (kk % 2)), h[kk / 2][kk % 2][reg]);
+                            } else {        // and back: the A fragments of row tile kk & 1, four k-steps
+                                const int rt = kk & 1, k0 = kk < 6 ? 0 : 4;
+#pragma unroll
+                                for (int k2 = k0; k2 < k0 + 4; ++k2)
+                                    ha[rt][k2] = lds_ld(sqr[rt] + 8u * 4u * k2);
+                            }
+                        }
+                        // the M1 row of this matrix (requested behind the Y phase of the last one) has landed: younger
+                        // than it are this phase's SB row and its stores so far (passes c = 0..2); then its first fragments
+                        if (m == 0 && kk == 7) {
+                            wait_vm_dyn8(npieces + __builtin_popcount((unsigned)(act >> (ODD ? 4 : 0)) & 7u));
+                            mb[0][0] = lds_ld(fa[0][0] + kRowM);
+                            mb[1][0] = lds_ld(fa[1][0] + kRowM);
                         }
                     }
                     if (m == 2 && (kk & 1) == 1) {
@@ -341,6 +445,55 @@ __global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
                 }
             }
         }
+        // ---------------------------------------------------------------- Y += mult(e) H M1_e
+        // The B fragments of M1_e are read one k-step ahead; the pair's multiplicity, halved, is 1 for all but the n
+        // diagonal pairs, whose fragments are halved as they arrive (the only vector arithmetic of the kernel's loop,
+        // in 1 iteration of about 16); the sum is doubled at the end.  The next M1 row is requested behind the last read.
+        if constexpr (COMPUTE && Y2) {
+            auto yphase = [&](auto live_tag, auto diag_tag) {
+                constexpr bool LIVE = decltype(live_tag)::value, DIAG = decltype(diag_tag)::value;
+                if constexpr (DIAG) {
+                    mb[0][0] *= 0.5;
+                    mb[1][0] *= 0.5;
+                }
+#pragma unroll
+                for (int kk = 0; kk < KS; ++kk)
+#pragma unroll
+                    for (int m = 0; m < NT * NT; ++m) {
+                        const int ti = m / NT, ta = m % NT;
+                        if constexpr (LIVE) {
+                            EVC_PTD_PRIO(0);
+                            yy[ti][ta] = mfma_f64(ha[ti][kk], mb[ta][kk], yy[ti][ta]);
+                            EVC_PTD_PRIO(1);
+                            if (m == 0 && kk < KS - 1) {
+                                mb[0][kk + 1] = lds_ld(fa[0][kk + 1] + kRowM);
+                                mb[1][kk + 1] = lds_ld(fa[1][kk + 1] + kRowM);
+                            }
+                            if constexpr (DIAG) {
+                                if (m == 3 && kk < KS - 1) {
+                                    mb[0][kk + 1] *= 0.5;
+                                    mb[1][kk + 1] *= 0.5;
+                                }
+                            }
+                        }
+                        if (m == 1 && kk == KS - 1) {
+                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                            dma_mrow(e0 + 4 * (i + 1));
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+            };
+            using Tt = std::true_type;
+            using Ff = std::false_type;
+            if (e0 + 4 * i >= npairs) yphase(Ff{}, Ff{});   // (idle slots of the last tile add nothing)
+            else if (qq == pp) yphase(Tt{}, Tt{});
+            else yphase(Tt{}, Ff{});
+            qq += 4;
+            while (qq > pp) {
+                qq -= pp + 1;
+                ++pp;
+            }
+        }
     };
     using T = std::true_type;
     using F = std::false_type;
@@ -365,6 +518,32 @@ __global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
         iteration(F{}, P1{}, i + 1, nnA, nnB);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the rows requested beyond the last matrix)
+    if constexpr (Y2) {
+        // cross-wave sum of Y = Yd + 2 Yo over the rows and the stage, once every wave is done with them
+        constexpr int NPAD = 32;
+        __syncthreads();
+        double *red = reinterpret_cast<double *>(lds);   // [4][NPAD][NPAD + 1]
+#pragma unroll
+        for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+            for (int ta = 0; ta < NT; ++ta)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    red[(wave * NPAD + ti * 16 + l4 + 4 * r) * (NPAD + 1) + ta * 16 + l15] = 2.0 * yy[ti][ta][r];
+        __syncthreads();
+        double *dst = y.partial + g * y.sws + (int64_t)blockIdx.x * n * n;
+        for (int idx = threadIdx.x; idx < n * n; idx += 256) {
+            const int ii = idx / n, aa = idx % n;
+            const int o = ii * (NPAD + 1) + aa;
+            constexpr int WS = NPAD * (NPAD + 1);
+            dst[idx] = (red[o] + red[WS + o]) + (red[2 * WS + o] + red[3 * WS + o]);
+        }
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
+    ptd_body<MODE, false>(a, Y2dArgs{});
 }
 
 // ---------------------------------------------------------------------------------- Y2 with LDS-DMA operand rows
@@ -376,9 +555,19 @@ __global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
 // constant "one row younger" vmcnt.  No barrier, no store, no vector instruction in the loop: the multiplicity of the
 // pair (1 on the diagonal i == j, else 2) selects one of two accumulator sets (wave-uniform branch), Y = Yd + 2 Yo at
 // the end.
-__global__ __launch_bounds__(256, 2) void y2d_kernel(const double *__restrict__ SB, const double *__restrict__ M1,
-                                                     const double *__restrict__ X, int64_t sX, int n,
-                                                     double *__restrict__ partial, int64_t sws, int tiles_per_wg, int ppt) {
+//
+// PS = 1: the kernel is the first gradient-side pair step as well (ptd_body above, R = X^T T_v X written as ptd_kernel<0>
+// writes it); one workgroup per CU for its LDS.  PS = 0: Y2 alone, as described here.
+template <int PS>
+__global__ __launch_bounds__(256, PS ? 1 : 2) void y2d_kernel(Y2dArgs ya, PairTransformArgs pa) {
+    if constexpr (PS) {
+        ptd_body<0, true>(pa, ya);
+        return;
+    }
+    const double *__restrict__ SB = ya.SB, *__restrict__ M1 = ya.M1, *__restrict__ X = ya.X;
+    double *__restrict__ partial = ya.partial;
+    const int64_t sX = ya.sX, sws = ya.sws;
+    const int n = ya.n, tiles_per_wg = ya.tiles_per_wg, ppt = ya.ppt;
     constexpr int KS = 8, NT = 2, NPAD = 32;
     extern __shared__ __align__(16) char lds[];
     const int npairs = n * (n + 1) / 2, ld = pair_ld(n);
@@ -547,10 +736,47 @@ bool y2_dma_applicable(int n) {
 int launch_y2_dma(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial, int64_t sws,
                   int count, int slabs, int tiles_per_wg, int ppt, hipStream_t st) {
     constexpr unsigned ldsb = 8 * kPdRB > 4 * 32 * 33 * 8 ? 8 * kPdRB : 4 * 32 * 33 * 8;
-    hipLaunchKernelGGL(y2d_kernel, dim3((unsigned)slabs, (unsigned)count), dim3(256), ldsb, st, SB, M1, X, sX, n, partial,
-                       sws, tiles_per_wg, ppt);
+    Y2dArgs ya{SB, M1, X, partial, sX, sws, n, tiles_per_wg, ppt};
+    hipLaunchKernelGGL((y2d_kernel<0>), dim3((unsigned)slabs, (unsigned)count), dim3(256), ldsb, st, ya, PairTransformArgs{});
     note_kernel(EVC_PROF_Y2, "y2d_kernel");
     EVC_LAUNCH_CHECK("y2_dma");
+    return 0;
+}
+
+// EVC_Y2_PAIRSTEP=0: Y2 and the first gradient-side pair step as two kernels (y2d_kernel<0>, ptd_kernel<0>)
+static bool y2_pairstep_on() {
+    static const bool on = !(getenv("EVC_Y2_PAIRSTEP") && atoi(getenv("EVC_Y2_PAIRSTEP")) == 0);
+    return on;
+}
+// 8-pair tiles per workgroup: one workgroup per CU, so a batch that fills the chip takes 8 (N = 30, 32 geometries: 256
+// workgroups), smaller ones fewer for more workgroups
+static int y2_pairstep_tiles(int count) { return count >= 32 ? 8 : count >= 8 ? 4 : 2; }
+
+int y2_pairstep_slabs(int n, int count) {
+    const int ntiles = (n * (n + 1) / 2 + 7) / 8, t = y2_pairstep_tiles(count);
+    return (ntiles + t - 1) / t;
+}
+
+bool y2_pairstep_applicable(const PairTransformArgs &a, const double *M1, int64_t sws, int count) {
+    const int npairs = a.n * (a.n + 1) / 2;
+    // (both rows of a pair share one DMA window: rows on 16-byte granules, same pitch)
+    const bool aligned = ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(M1)) & 15) == 0 &&
+                         a.in_ld >= npairs && a.in_ld % 2 == 0 && a.sin % 2 == 0 && sws % 2 == 0;
+    return y2_pairstep_on() && y2_dma_applicable(a.n) && pair_transform_dma_applicable(a, count) && a.out && a.ct == 1 &&
+           aligned && a.in != a.out && y2_pairstep_slabs(a.n, count) <= y2_slab_capacity(a.n);
+}
+
+int launch_y2_pairstep(const PairTransformArgs &a_in, const double *M1, double *partial, int64_t sws, int count,
+                       hipStream_t st) {
+    PairTransformArgs a = a_in;
+    a.tiles_per_wg = y2_pairstep_tiles(count);
+    Y2dArgs ya{a.in, M1, a.C, partial, a.sC, sws, a.n, a.tiles_per_wg, 8};
+    static LdsAttr attr;
+    if (int rc = allow_dynamic_lds(y2d_kernel<1>, attr, 160 * 1024, "y2_pairstep")) return rc;
+    hipLaunchKernelGGL((y2d_kernel<1>), dim3((unsigned)y2_pairstep_slabs(a.n, count), (unsigned)count), dim3(256), kPdLdsY,
+                       st, ya, a);
+    note_kernel(EVC_PROF_Y2, "y2d_kernel<1> pairstep");
+    EVC_LAUNCH_CHECK("y2_pairstep");
     return 0;
 }
 

@@ -709,6 +709,22 @@ static int gradient_from_rdms(int n, const Geo &g, const double *D, int64_t sD, 
             for (int c0 = 0; c0 < cnt; c0 += chunk) {
                 const int cc = cnt - c0 < chunk ? cnt - c0 : chunk;
                 const int64_t o = (int64_t)c0 * sw;
+                // the first gradient-side pair step, B1 -> B2 (SB is fully symmetric); the Y2 kernel does it as well where
+                // it can (y2_pairstep_applicable), otherwise it is the first of two pair-transform launches
+                PairTransformArgs first;
+                memset(&first, 0, sizeof(first));
+                first.C = w.X + o;
+                first.sC = sw;
+                first.ct = 1;
+                first.n = n;
+                first.in = w.B1 + o;
+                first.sin = sw;
+                first.out = w.B2 + o;
+                first.sout = sw;
+                first.lead_sym = first.in_lower = first.rs_lower = sym8;
+                first.out_pairs = sym8;
+                first.in_ld = first.out_ld = pair_ld(n);   // (pitch of every dense (pair, pair) form of the pipeline)
+                bool pairstep = false;
                 int pr = prof_start(EVC_PROF_UNPACK, st);
                 if (sym8) {
                     // (K3 was written for l <= k only by the symmetric second step of phase A)
@@ -730,16 +746,24 @@ static int gradient_from_rdms(int n, const Geo &g, const double *D, int64_t sD, 
                     pr = prof_start(EVC_PROF_Y2, st);
                     if (fused_y2) {
                         // (the K3 buffer holds the first pair step's intermediate; with the unpacked 2-RDM requested
-                        //  SB above is N^4-addressed: the dense (pair, pair) form goes to B2, free until the next step)
+                        //  SB above is N^4-addressed: the dense (pair, pair) form goes to B2, free until the next step
+                        //  -- or over it in B1 when the Y2 kernel is the first pair step as well and writes B2)
+                        first.in_pairs = sym8;
+                        pairstep = y2_pairstep_applicable(first, w.K3 + o, sw, cc);
                         const double *sbp = w.B1 + o;
                         if (G && !p64) {
-                            if ((rc = launch_unpack8(packed + (int64_t)c0 * spacked, spacked, n, w.B2 + o, sw, nullptr, 0,
-                                                     cc, 2, st)))
+                            double *dense = (pairstep ? w.B1 : w.B2) + o;
+                            if ((rc = launch_unpack8(packed + (int64_t)c0 * spacked, spacked, n, dense, sw, nullptr, 0, cc, 2, st)))
                                 return rc;
-                            sbp = w.B2 + o;
+                            sbp = dense;
                         }
-                        if ((rc = launch_y2_fused(sbp, w.K3 + o, w.X + o, sw, n, w.y2part + o, sw, cc, st))) return rc;
-                        y2_slabs_used = y2_fused_slabs(n, cc);
+                        if (pairstep) {
+                            if ((rc = launch_y2_pairstep(first, w.K3 + o, w.y2part + o, sw, cc, st))) return rc;
+                            y2_slabs_used = y2_pairstep_slabs(n, cc);
+                        } else {
+                            if ((rc = launch_y2_fused(sbp, w.K3 + o, w.X + o, sw, n, w.y2part + o, sw, cc, st))) return rc;
+                            y2_slabs_used = y2_fused_slabs(n, cc);
+                        }
                     } else {
                         set_error("gradient: the symmetric pipeline needs the fused Y2 contraction (n <= 32)");
                         return -1;
@@ -753,23 +777,13 @@ static int gradient_from_rdms(int n, const Geo &g, const double *D, int64_t sD, 
                     if ((rc = launch_y2(w.B2 + o, w.K3 + o, n, w.y2part + o, sw, cc, st))) return rc;
                 }
                 prof_stop(pr, st);
-                PairTransformArgs pa;
-                memset(&pa, 0, sizeof(pa));
-                pa.C = w.X + o;
-                pa.sC = sw;
-                pa.ct = 1;
-                pa.n = n;
-                pa.in = w.B1 + o;
-                pa.sin = sw;
-                pa.out = w.B2 + o;
-                pa.sout = sw;
-                pa.lead_sym = pa.in_lower = pa.rs_lower = sym8;   // SB is fully symmetric
+                PairTransformArgs pa = first;
                 pa.in_pairs = (sym8 && (!G || p64)) ? 1 : 0;
-                pa.out_pairs = sym8;
-                pa.in_ld = pa.out_ld = pair_ld(n);   // (pitch of every dense (pair, pair) form of the pipeline)
-                pr = prof_start(EVC_PROF_PAIR_TRANSFORM, st);
-                if ((rc = launch_pair_transform(pa, cc, st))) return rc;
-                prof_stop(pr, st);
+                if (!pairstep) {
+                    pr = prof_start(EVC_PROF_PAIR_TRANSFORM, st);
+                    if ((rc = launch_pair_transform(pa, cc, st))) return rc;
+                    prof_stop(pr, st);
+                }
                 // (the second step keeps rs_lower as well: G^AO[m,b,c,d] = G^AO[b,m,c,d], fold_cd reads b <= m)
                 // the result is only valid for d <= c of G^AO[m,b,c,d] (fold_cd below)
                 pa.in = w.B2 + o;
