@@ -130,6 +130,16 @@ SIGNATURES = {
                                     C.c_size_t, C.c_void_p]),
     "evc_fci_sigma": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_fci_solve_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "evc_fci_hdiag": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_fci_dots": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                               C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_fci_combine": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    "evc_fci_davidson_correction": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_profile_begin": (C.c_int, [C.c_int]),
     "evc_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int)]),
@@ -143,6 +153,9 @@ PROF_STAGES = {"k5_rows": 0, "k8_cols": 1, "pair_transform": 2, "ip1": 3, "y2": 
                "subspace": 7}
 # stages of the full-CI entry points (EVC_PROF_FCI_*): named by evc_profile_kernel, not timed by the bench hook
 FCI_PROF_STAGES = {"fci_excite": 8, "fci_trdm": 9, "fci_sigma": 10}
+# the vector kernels of the device eigensolver (EVC_PROF_FCI_SOLVE): kept apart from the three stages above, which every
+# evc_fci_trdm_rows / evc_fci_sigma call sets
+FCI_PROF_SOLVE = 11
 FCI_DET_MAJOR, FCI_DET_MAJOR_T, FCI_ORB_MAJOR = 0, 1, 2
 
 _lib: Optional[C.CDLL] = None

@@ -22,17 +22,7 @@ __device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
-constexpr int kFciMaxOrb = 16;
-constexpr int kFciMinRows = 256;     // determinants per split-K block, at least
-constexpr int kFciMaxBlocks = 256;   // split-K blocks (= partial tiles per ket), at most
-
 static int fci_npad(int norb) { return (norb * norb + 15) / 16 * 16; }
-// The split of the determinants into blocks depends on the determinant count alone -- not on the workspace, not on the
-// number of kets -- so a row call and its single-pair calls sum the same partials in the same order.
-static int64_t fci_rows_per_block(int64_t dim) {
-    const int64_t r = align_up((size_t)ceil_div(dim, kFciMaxBlocks), 64);
-    return r < kFciMinRows ? kFciMinRows : r;
-}
 // sigma: row tiles per wave for nt = npad / 16 tiles
 static int fci_rt(int nt) { return (int)ceil_div(nt, ceil_div(nt, 4)); }
 

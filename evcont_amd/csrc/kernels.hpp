@@ -12,6 +12,18 @@ namespace evc {
 constexpr int kMaxOrbitals = 96;   // N of the fused pipeline (quarter transforms: 16-wide tiles up to 96 padded columns)
 constexpr int kMaxBatchG = 32;  // geometries contracted per pass of the streaming kernels (matrix-core variants)
 
+// ---- fci.hip, fci_solve.hip ----------------------------------------------------------
+constexpr int kFciMaxOrb = 16;
+constexpr int kFciMinRows = 256;     // determinants per split-K block, at least
+constexpr int kFciMaxBlocks = 256;   // split-K blocks (= partial tiles per ket), at most
+// The split of the determinants into blocks depends on the determinant count alone -- not on the workspace, not on the
+// number of kets or vectors -- so a row call and its single-pair calls, and a dot product in any grouping, sum the same
+// partials in the same order.
+inline int64_t fci_rows_per_block(int64_t dim) {
+    const int64_t r = (int64_t)align_up((size_t)ceil_div(dim, kFciMaxBlocks), 64);
+    return r < kFciMinRows ? kFciMinRows : r;
+}
+
 // ---- gemv_stream.hip ---------------------------------------------------------------
 struct RowProblem {
     const double *A;   // (rows, ld)                       shared by the batch

@@ -8,9 +8,12 @@ plus ``trans_rdm12_rows(bra, kets, norb, nelec)``: one bra against all kets in o
 ``FCI_EVCont_obj.append_to_rdms`` needs for a new training state.  Opt in with
 ``FCI_EVCont_obj(cisolver=DeviceFCI(), cibasis="OAO")``.
 
-Limits: ``norb <= 16``, real CI vectors, any ``(n_alpha, n_beta)``.  The eigensolver iteration of ``kernel`` stays on the
-host (``scipy.sparse.linalg.eigsh``); every matrix-vector product it asks for is a device sigma vector.  There is no host
-fallback: without the library or a device every call raises ``EvcontHipError``.
+Limits: ``norb <= 16``, real CI vectors, any ``(n_alpha, n_beta)``.  By default the eigensolver iteration of ``kernel``
+stays on the host (``scipy.sparse.linalg.eigsh``); every matrix-vector product it asks for is a device sigma vector that
+is uploaded and downloaded.  ``DeviceFCI(eigensolver="davidson")`` runs a block Davidson (``fci_davidson.py``) whose
+CI-length vectors stay on the device (``csrc/fci_solve.hip``); the host sees the projected matrix, the Ritz coefficients
+and the residual norms.  There is no host fallback: without the library or a device every call raises
+``EvcontHipError``.
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ import torch
 from scipy.sparse.linalg import LinearOperator, eigsh
 
 from . import _lib
+from .fci_davidson import DavidsonOps, davidson
 from ._lib import EvcontHipError, check
 from .fci_tables import MAX_ORB, packed_table
 
@@ -34,12 +38,118 @@ def _nelec(nelec) -> Tuple[int, int]:
     return int(nelec[0]), int(nelec[1])
 
 
+class _DeviceOps(DavidsonOps):
+    """The vector operations of ``fci_davidson.davidson`` on device storage: ``evc_fci_hdiag``, ``evc_fci_dots``,
+    ``evc_fci_combine``, ``evc_fci_davidson_correction`` and ``evc_fci_sigma``.  Coefficients go up and products come
+    down as small arrays; no CI-length vector crosses but ``load`` (start vectors) and ``fetch`` (results)."""
+
+    def __init__(self, fci: "DeviceFCI", lib, dta, dtb, na, nb, grant, norb, dh1, dh2):
+        self.fci, self.lib, self.dta, self.dtb, self.na, self.nb = fci, lib, dta, dtb, na, nb
+        self.grant, self.norb, self.dh1, self.dh2 = grant, norb, dh1, dh2
+        self.dim = na * nb
+        self.dev = dta.device
+        self.nsigma = 0
+        self.sets = {}
+        self.hd = None
+
+    def prepare(self, nroots, max_space):
+        lib, dim = self.lib, self.dim
+        nvec = max(max_space, 2 * nroots)
+        wsb = lib.evc_fci_solve_workspace_bytes(self.norb, self.na, self.nb, nvec)
+        if wsb == 0:
+            check(-1, "evc_fci_solve_workspace_bytes")
+        rows = 2 * max_space + 2 * nroots + 1
+        small = (nvec * nvec + nvec * 2 * nroots + 4 * nroots) * 8
+        need = rows * dim * 8 + wsb + small
+        key = (self.norb, self.na, self.nb, max_space, nroots)
+        store = self.fci._basis
+        if store is None or store[0] != key:
+            self.fci._basis = store = None
+            free = torch.cuda.mem_get_info(self.dev)[0]
+            if need > free:
+                raise EvcontHipError(f"DeviceFCI: the Davidson basis of {rows} vectors of {dim} determinants needs "
+                                     f"{need} bytes, the device has {free} free (max_space={max_space}, nroots={nroots})")
+            store = (key, torch.empty((rows, dim), dtype=F64, device=self.dev),
+                     torch.empty(wsb, dtype=torch.uint8, device=self.dev))
+            self.fci._basis = store
+        _, basis, self.ws = store
+        self.wsb = wsb
+        self.sets = {"V": basis[:max_space], "W": basis[max_space:2 * max_space],
+                     "S": basis[2 * max_space:2 * max_space + 2 * nroots]}
+        self.hd = basis[rows - 1]
+        self.out = torch.empty(nvec * nvec, dtype=F64, device=self.dev)
+        check(lib.evc_fci_hdiag(self.norb, self.na, self.nb, self.dta.data_ptr(), self.dtb.data_ptr(), self.dh1.data_ptr(),
+                                self.dh2.data_ptr(), self.hd.data_ptr(), self.ws.data_ptr(), wsb, self.fci._stream()),
+              "evc_fci_hdiag")
+
+    def _row(self, name, row):
+        return self.sets[name].data_ptr() + 8 * row * self.dim
+
+    def lowest(self, n):
+        return [int(i) for i in torch.sort(self.hd, stable=True).indices[:n].cpu()]
+
+    def load(self, name, row, vec):
+        self.sets[name][row].copy_(torch.from_numpy(np.ascontiguousarray(vec, dtype=np.float64).reshape(-1)))
+
+    def fetch(self, name, row):
+        return self.sets[name][row].cpu().numpy()
+
+    def copy(self, dst, d0, src, s0, count):
+        self.sets[dst][d0:d0 + count].copy_(self.sets[src][s0:s0 + count])
+
+    def sigma(self, row):
+        self.nsigma += 1
+        check(self.lib.evc_fci_sigma(self.norb, self.na, self.nb, self.dta.data_ptr(), self.dtb.data_ptr(),
+                                     self.dh1.data_ptr(), self.dh2.data_ptr(), self._row("V", row), self._row("W", row),
+                                     self.fci._ws.data_ptr(), self.grant, self.fci._stream()), "evc_fci_sigma")
+
+    def dots(self, x, x0, nx, y, y0, ny):
+        check(self.lib.evc_fci_dots(self.dim, self._row(x, x0), self.dim, nx, self._row(y, y0), self.dim, ny,
+                                    self.out.data_ptr(), self.ws.data_ptr(), self.wsb, self.fci._stream()), "evc_fci_dots")
+        return self.out[:nx * ny].cpu().numpy().reshape(nx, ny)
+
+    def _small(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)
+
+    def combine(self, out, o0, src, s0, coef, beta):
+        m, k = coef.shape
+        dcoef = self._small(coef)
+        check(self.lib.evc_fci_combine(self.dim, self._row(src, s0), self.dim, m, dcoef.data_ptr(), k, k, float(beta),
+                                       self._row(out, o0), self.dim, self.fci._stream()), "evc_fci_combine")
+
+    def correction(self, m, y, theta):
+        k = y.shape[1]
+        dy, dth = self._small(y), self._small(theta)
+        check(self.lib.evc_fci_davidson_correction(self.dim, self._row("V", 0), self.dim, self._row("W", 0), self.dim, m,
+                                                   dy.data_ptr(), k, dth.data_ptr(), k, self.hd.data_ptr(),
+                                                   self._row("S", 0), self.dim, self.out.data_ptr(), self.ws.data_ptr(),
+                                                   self.wsb, self.fci._stream()), "evc_fci_davidson_correction")
+        return self.out[:k].cpu().numpy()
+
+
+EIGENSOLVERS = ("host", "davidson")
+
+
 class DeviceFCI:
     """``workspace_bytes=None`` grants what keeps every intermediate resident (``evc_fci_workspace_bytes``: two
     ``dim x npad`` excitation arrays and the split-K partials; 2.1 GB at (12, (6, 6))); a smaller grant makes the
-    library work in chunks of determinants, with the same results bit for bit."""
+    library work in chunks of determinants, with the same results bit for bit.
 
-    def __init__(self, device=None, tol: float = 1e-13, workspace_bytes: Optional[int] = None, dense_limit: int = 1500):
+    ``eigensolver="host"`` (the default): ``kernel`` diagonalises densely up to ``dense_limit`` determinants and runs
+    ``eigsh`` on the host beyond.  ``eigensolver="davidson"``: block Davidson with resident vectors at every size, a root
+    converged when its residual 2-norm is at most ``conv_tol``; the basis holds at most ``max_space`` vectors (default
+    ``8 nroots + 12``) and ``2 max_space + 2 nroots + 1`` vectors are allocated, once per shape; ``converged`` is False,
+    with a warning, when ``max_cycle`` iterations did not suffice."""
+
+    def __init__(self, device=None, tol: float = 1e-13, workspace_bytes: Optional[int] = None, dense_limit: int = 1500,
+                 eigensolver: str = "host", conv_tol: float = 1e-10, max_space: Optional[int] = None,
+                 max_cycle: int = 300):
+        if eigensolver not in EIGENSOLVERS:
+            raise ValueError(f"DeviceFCI: eigensolver={eigensolver!r}, expected one of {EIGENSOLVERS}")
+        self.eigensolver = eigensolver
+        self.conv_tol, self.max_space, self.max_cycle = conv_tol, max_space, max_cycle
+        self.davidson_info = None
+        self._basis = None
         self.tol = tol
         self.dense_limit = dense_limit
         self.workspace_bytes = workspace_bytes
@@ -140,17 +250,22 @@ class DeviceFCI:
               "evc_fci_sigma")
         return out
 
-    def kernel(self, h1, h2, norb, nelec, nroots: int = 1, **_):
+    def kernel(self, h1, h2, norb, nelec, nroots: int = 1, ci0=None, **_):
         """Lowest ``nroots`` eigenpairs; scalars/array for ``nroots == 1``, lists otherwise; sign convention of
         ``SmallFCI.kernel`` (largest-magnitude coefficient positive).  Up to ``dense_limit`` determinants H is built
         column by column from device sigma vectors and diagonalised densely, beyond that Lanczos (eigsh) runs over
-        them -- the same split as ``SmallFCI``."""
+        them -- the same split as ``SmallFCI``.  With ``eigensolver="davidson"`` the iteration runs on the device at
+        every size and ``ci0`` (one array or a list, as PySCF takes it) replaces the first start vectors; the host
+        route ignores ``ci0``."""
         nelec = _nelec(nelec)
         lib, dta, dtb, na, nb, grant = self._setup(norb, nelec)
         dev = self._dev()
         dim = na * nb
         dh1 = torch.from_numpy(np.ascontiguousarray(h1, dtype=np.float64).reshape(norb, norb)).to(dev)
         dh2 = torch.from_numpy(np.ascontiguousarray(h2, dtype=np.float64).reshape(norb ** 4)).to(dev)
+
+        if self.eigensolver == "davidson":
+            return self._davidson(lib, dta, dtb, na, nb, grant, norb, dh1, dh2, nroots, ci0)
 
         def mv(v):
             dc = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64).reshape(-1)).to(dev)
@@ -175,6 +290,22 @@ class DeviceFCI:
         vecs = []
         for k in range(nroots):
             x = v[:, k].copy()
+            x *= np.sign(x[np.argmax(np.abs(x))])
+            vecs.append(x.reshape(na, nb))
+        if nroots == 1:
+            return float(w[0]), vecs[0]
+        return [float(x) for x in w[:nroots]], vecs
+
+    def _davidson(self, lib, dta, dtb, na, nb, grant, norb, dh1, dh2, nroots, ci0):
+        ops = _DeviceOps(self, lib, dta, dtb, na, nb, grant, norb, dh1, dh2)
+        try:
+            w, v, self.converged, self.davidson_info = davidson(
+                ops, nroots=nroots, conv_tol=self.conv_tol, max_space=self.max_space, max_cycle=self.max_cycle, ci0=ci0)
+        except ValueError as e:
+            raise EvcontHipError(f"DeviceFCI: {e}") from e
+        vecs = []
+        for k in range(nroots):
+            x = v[k] / np.linalg.norm(v[k])
             x *= np.sign(x[np.argmax(np.abs(x))])
             vecs.append(x.reshape(na, nb))
         if nroots == 1:

@@ -39,16 +39,17 @@ p.add_argument("--batch", type=int, default=50)
 p.add_argument("--fixture", action="store_true",
                help="take the five training states from tests/golden/h10_fci_t5.npz (STO-3G, other spacings) instead "
                     "of solving five 63504-determinant FCI problems first (~2 min)")
-p.add_argument("--solver", choices=("host", "device"), default="host",
-               help="FCI solver of the training states and the exact energies: fci_small.SmallFCI (default) or "
-                    "fci_device.DeviceFCI (sigma vectors and transition RDMs on the GPU: seconds instead of minutes)")
+p.add_argument("--solver", choices=("host", "device", "device-davidson"), default="host",
+               help="FCI solver of the training states and the exact energies: fci_small.SmallFCI (default), "
+                    "fci_device.DeviceFCI (sigma vectors and transition RDMs on the GPU: seconds instead of minutes), or "
+                    "DeviceFCI with its block Davidson eigensolver on device-resident vectors")
 a = p.parse_args()
 
 
 def make_solver():
-    if a.solver == "device":
+    if a.solver != "host":
         from evcont_amd.fci_device import DeviceFCI
-        return DeviceFCI()
+        return DeviceFCI(eigensolver="davidson" if a.solver == "device-davidson" else "host")
     return SmallFCI()
 
 

@@ -9,6 +9,7 @@ should be run on this hardware.
 
     python examples/h6_pes.py            # needs a HIP device; writes predicted_surface_*.txt, exact_surface.txt
     python examples/h6_pes.py --solver device     # the FCI training states on the GPU too (fci_device.DeviceFCI)
+    python examples/h6_pes.py --solver device-davidson    # ... and their eigensolver iteration, on resident vectors
 """
 import argparse
 import os
@@ -37,12 +38,13 @@ def get_mol(dist, need_grad=False):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--solver", choices=("host", "device"), default="host",
-                   help="FCI solver of the training states: fci_small.SmallFCI (default) or fci_device.DeviceFCI")
+    p.add_argument("--solver", choices=("host", "device", "device-davidson"), default="host",
+                   help="FCI solver of the training states: fci_small.SmallFCI (default), fci_device.DeviceFCI, or "
+                        "DeviceFCI with its block Davidson eigensolver on device-resident vectors")
     a = p.parse_args()
-    if a.solver == "device":
+    if a.solver != "host":
         from evcont_amd.fci_device import DeviceFCI
-        solver = DeviceFCI()
+        solver = DeviceFCI(eigensolver="davidson" if a.solver == "device-davidson" else "host")
     else:
         solver = SmallFCI()
     continuation_object = FCI_EVCont_obj(cisolver=solver, cibasis="OAO")

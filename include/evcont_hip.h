@@ -41,7 +41,8 @@ extern "C" {
                                  later additions under 10 (no existing signature or behaviour changed):
                                  evc_phase_gradient_roots_batch, evc_workspace_bytes_roots_batch;
                                  evc_fci_excite, evc_fci_trdm_rows, evc_fci_sigma, evc_fci_workspace_bytes and the
-                                 stages EVC_PROF_FCI_* */
+                                 stages EVC_PROF_FCI_*; additive: evc_fci_hdiag, evc_fci_dots, evc_fci_combine,
+                                 evc_fci_davidson_correction, evc_fci_solve_workspace_bytes, EVC_PROF_FCI_SOLVE */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -452,6 +453,37 @@ int evc_fci_sigma(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const 
                   const double *h2, const double *c, double *sigma, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Vector work of an eigensolver around evc_fci_sigma (evcont_amd/fci_davidson.py: block Davidson with the diagonal of H
+ * as preconditioner) on CI vectors that stay on the device.  A set of vectors is a row-major (count, ld) DEVICE array of
+ * doubles, ld >= dim = na * nb; at most 256 vectors per set and call.  Every sum over the determinants is formed per
+ * block of R determinants (R as above) in a fixed order and the blocks are added in order by a second launch: the same
+ * bits for every grouping of the vectors and from run to run, no atomics.
+ *
+ * evc_fci_solve_workspace_bytes(norb, na, nb, nvec): bytes that serve evc_fci_hdiag and every evc_fci_dots /
+ *       evc_fci_davidson_correction call with at most nvec vectors per set.  0 on an argument error.
+ * evc_fci_hdiag: hdiag[I] = <I|H|I> of the operator evc_fci_sigma applies (no symmetry of h2 assumed): with the
+ *       occupations n_p = n_p,alpha + n_p,beta of determinant I,
+ *       sum_p h'_pp n_p + 1/2 sum_pr (pp|rr) n_p n_r + 1/2 sum_{p != q} (pq|qp) sum_spin n_p,spin (1 - n_q,spin).
+ * evc_fci_dots: out[i * ny + j] = X_i . Y_j (out: nx * ny DEVICE doubles).  X and Y may be the same set.
+ * evc_fci_combine: Out_r = beta Out_r + sum_{j < m} coef[j * ldc + r] V_j for r < k; coef on the DEVICE; beta == 0 does
+ *       not read Out; m == 0 scales Out (V and coef are then ignored).  Out must not overlap V (refused).
+ * evc_fci_davidson_correction: for the k Ritz pairs (theta_r, y_r = coef[. * ldc + r]) of the basis V with W = H V,
+ *       r_r = sum_j y_jr W_j - theta_r sum_j y_jr V_j, rnorm2[r] = |r_r|^2 and T_r = r_r / d, d = hdiag - theta_r with |d|
+ *       floored at 1e-8 keeping its sign (d = 0 counts as +1e-8); coef, theta, rnorm2 on the DEVICE.  T must not overlap
+ *       V, W or hdiag (refused).
+ * --------------------------------------------------------------------------------- */
+size_t evc_fci_solve_workspace_bytes(int norb, int64_t na, int64_t nb, int nvec);
+int evc_fci_hdiag(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b, const double *h1,
+                  const double *h2, double *hdiag, void *ws, size_t ws_bytes, void *stream);
+int evc_fci_dots(int64_t dim, const double *X, int64_t ldx, int nx, const double *Y, int64_t ldy, int ny, double *out,
+                 void *ws, size_t ws_bytes, void *stream);
+int evc_fci_combine(int64_t dim, const double *V, int64_t ldv, int m, const double *coef, int ldc, int k, double beta,
+                    double *Out, int64_t ldo, void *stream);
+int evc_fci_davidson_correction(int64_t dim, const double *V, int64_t ldv, const double *W, int64_t ldw, int m,
+                                const double *coef, int ldc, const double *theta, int k, const double *hdiag, double *T,
+                                int64_t ldt, double *rnorm2, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Measurement hook (bench.py): while enabled, the fused pipeline records hipEvents on the launch
  * stream immediately before and after the launches of the stages below, for up to max_samples
  * evaluations.  evc_profile_end synchronises those events, returns the summed durations in
@@ -470,6 +502,8 @@ int evc_fci_sigma(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const 
 #define EVC_PROF_FCI_EXCITE 8     /* evc_fci_*: D = E_pq c (last launch: the layout it wrote) */
 #define EVC_PROF_FCI_TRDM 9       /* evc_fci_trdm_rows: split-K product, with its tiling */
 #define EVC_PROF_FCI_SIGMA 10     /* evc_fci_sigma: G = h2 . D and the gather */
+#define EVC_PROF_FCI_SOLVE 11     /* evc_fci_hdiag / _dots / _combine / _davidson_correction: the kernels of the last such
+                                     call and its grouping (not cleared by the other evc_fci_* entry points) */
 int evc_profile_begin(int max_samples);
 int evc_profile_end(double *rows_ms, int *rows_n, double *cols_ms, int *cols_n);
 int evc_profile_stage(int stage, double *ms, int *launches);
