@@ -146,6 +146,7 @@ SIGNATURES = {
     "evc_profile_stage": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "evc_profile_select": (C.c_int, [C.c_uint]),
     "evc_profile_kernel": (C.c_char_p, [C.c_int]),
+    "evc_trdm_plan_describe": (C.c_int, [C.POINTER(TrdmSet), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "evc_release_workspace": (C.c_int, [C.c_void_p]),
 }
 # stages of evc_profile_stage (include/evcont_hip.h EVC_PROF_*)

@@ -1,5 +1,5 @@
 // The batched streaming contractions with the t-RDM streamed through LDS by LDS-DMA (global_load_lds_dwordx4).
-// K5 (this part of the file; batches of 12 .. 32 geometries per pass), K8 further down (17 .. 32):
+// K5 (this part of the file; batches of 12 .. 64 geometries per pass), K8 further down (17 .. 32):
 //   Y[row][g] = sum_c A[row][c] v[g][c]      (reference: ab_initio_eigenvector_continuation.py:57-64, the
 //   np.einsum / np.sum contractions of the stored transition RDMs with the rotated integrals)
 //
@@ -18,7 +18,7 @@
 // matrix rows, 2 KB per tile.  Slot p of the image is refilled for the NEXT image one position after it was read, so
 // the image is a sliding window and (NSI - 1) tiles = 2 (NSI - 1) instructions are in flight all the time; LDS-DMA
 // completes in order, so the wait in front of the reads of slot p is the constant vmcnt(2 (NSI - 2)).
-// Shapes (NT, NCH) = (14,1) (7,2) (4,3) (2,4): see lds_pick_nt below for what the row groups buy.
+// Shapes (NT, NCH) = (14,1) (7,2) (4,3) (2,4): see lds_pick_nt (gemv_dispatch.hip) for what the row groups buy.
 //
 // LDS image of a tile (rule "linear destination, swizzled SOURCE, same swizzle on the read"): instruction j of a
 // tile writes 1 KB = rows 8j..8j+7 x 128 bytes, lane i -> row 8j + (i >> 3), 16-byte position i & 7; the position
@@ -37,7 +37,7 @@ typedef double d2v __attribute__((ext_vector_type(2)));
 
 namespace {
 
-constexpr int kLW = 16;           // columns per wave chunk
+constexpr int kLW = kLdsChunkCols;  // columns per wave chunk
 constexpr int kTileBytes = 2048;  // 16 rows x 16 columns
 
 __device__ __forceinline__ d4 mfma64(double a, double b, d4 c) {
@@ -369,134 +369,10 @@ __global__ __launch_bounds__(256, 1) void gemv_rows_lds_kernel(GemvRowsLaunch L,
 }
 
 // ---------------------------------------------------------------------------------- host side
-constexpr int kLdsBlocks = 242;     // workgroups of the large problem: one per CU (the images fill the LDS), one round
-constexpr int kLdsBlocksSmall = 8;  // ... of the small (one-body) problem
-
-// These kernels put ONE workgroup on a CU (their LDS images fill it) and size their grids for a whole MI355X: a device
-// (or partition) with fewer CUs than blocks would run them in several rounds -- there the kernels of gemv_mfma.hip stay.
-static bool lds_device_fits() {
-    static std::atomic<uint64_t> known{0}, fits{0};   // bit d: device d examined / large enough
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    const uint64_t bit = (uint64_t)1 << dev;
-    if (!(known.load(std::memory_order_acquire) & bit)) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-        if (cus >= kLdsBlocks + kLdsBlocksSmall) fits.fetch_or(bit, std::memory_order_release);
-        known.fetch_or(bit, std::memory_order_release);
-    }
-    return (fits.load(std::memory_order_acquire) & bit) != 0;
-}
-
-static bool rows_lds_enabled() {
-    static const bool on = !(getenv("EVC_ROWS_LDS") && atoi(getenv("EVC_ROWS_LDS")) == 0);
-    return on && lds_device_fits();
-}
-
-// Kernel shapes (tiles per row group, chunks per image): every shape keeps 16-18 tiles = 32-36 KB in flight per wave.
-// Fewer tiles per row group = more row groups = fewer column spans for the same number of workgroups: the partial sums
-// (spans x rows x geometries, written by every workgroup at the same moment and flushed at the end of the launch) shrink
-// -- measured at H30 / T = 20 / 32 geometries they cost 3 us in the epilogue and 3 us at the kernel boundary with 242
-// spans -- while the geometry vectors are fetched once per row group (the row groups of a span share an XCD: L2 hits).
-struct LdsShape {
-    int nt, nch;
-};
-static const LdsShape kLdsShapes[] = {{14, 1}, {7, 2}, {4, 3}, {2, 4}};
-
-// Tiles per row group for a matrix of `rows` rows (EVC_ROWS_LDS_NT forces a shape): the largest shape that makes at
-// least two row groups and pads the matrix by less than 1/8 (tiles fetched beyond its rows), else the largest one
-// that pads by less than 1/8.  Measured at H30 / T = 20 (14 tiles), 32 geometries, rocprofv3 averages of the launch
-// and of rows_reduce_kernel behind it: 14 tiles per group 52.7 + 5.9 us, 7: 50.1 + 4.6, 4: 51.2 + 4.5, 2: 51.5 + 0
-// (33 spans: summed inside the eigensolver kernel, +2 us there); the fragment-shaped kernel 57.4 + 4.6.
-static int lds_pick_nt(int64_t rows) {
-    static const int forced = getenv("EVC_ROWS_LDS_NT") ? atoi(getenv("EVC_ROWS_LDS_NT")) : 0;
-    const int nt = (int)ceil_div(rows > 0 ? rows : 1, 16);
-    static const int order[] = {7, 4, 2, 14};
-    int best = 0;
-    for (int want_groups = 2; want_groups >= 1 && !best; --want_groups)
-        for (int cand : order) {
-            const int nrg = (int)ceil_div(nt, cand);
-            if (!best && nrg >= want_groups && nrg * cand * 8 <= nt * 9 && nrg <= kLdsBlocks / 8) best = cand;
-        }
-    if (!best) {   // few tiles: the shape that fetches the fewest tiles, the larger one on a tie
-        int fewest = 1 << 30;
-        for (int cand : order) {
-            const int tiles = (int)ceil_div(nt, cand) * cand;
-            if (tiles < fewest || (tiles == fewest && cand > best)) {
-                fewest = tiles;
-                best = cand;
-            }
-        }
-    }
-    for (const LdsShape &sh : kLdsShapes)
-        if (forced == sh.nt) best = forced;
-    return best;
-}
-
-static int lds_row_groups(int64_t rows, int nt) { return (int)ceil_div(ceil_div(rows > 0 ? rows : 1, 16), nt); }
-
-// Span plan of the LDS-staged kernel: spans of 64 m columns (m 16-column chunks for each of the four waves),
-// as many as fit `budget` workgroups in one round; row groups of `ntg` tiles.
-static void plan_one_lds(RowProblem &P, int budget, int ntg) {
-    const int nrg = lds_row_groups(P.rows, ntg);
-    int spans = budget / nrg;
-    if (spans < 1) spans = 1;
-    const int64_t chunks = ceil_div(P.cols, kLW);
-    int64_t m = ceil_div(chunks, 4 * (int64_t)spans);
-    if (m < 1) m = 1;
-    P.span_cols = 4 * kLW * m;
-    P.nspans = (int)ceil_div(P.cols, P.span_cols);
-    P.nblocks = nrg * P.nspans;
-    P.lds_plan = ntg;
-}
-
-bool rows_lds_applicable(const RowProblem &p0, const RowProblem &p1) {
-    // (narrow matrices stay with the fragment-shaped kernel: nothing to stream; EVC_ROWS_LDS_MINCOLS=1 sends the small
-    //  shapes of the parity tests through this kernel)
-    static const int64_t min_cols = getenv("EVC_ROWS_LDS_MINCOLS") ? atoll(getenv("EVC_ROWS_LDS_MINCOLS")) : 4096;
-    if (!rows_lds_enabled() || p0.rows <= 0 || p0.cols < min_cols) return false;
-    // 32-bit lane offsets inside a tile
-    if (16 * p0.ld * 8 >= ((int64_t)1 << 31) || 16 * p1.ld * 8 >= ((int64_t)1 << 31)) return false;
-    return lds_row_groups(p0.rows, 14) <= kLdsBlocks / 8;
-}
-
-// the small (one-body) problem rides in the launch of the large one if its row groups fit a few workgroups; a tall one
-// (T^2 rows: large training sets) keeps its own launch of the fragment-shaped kernel (plan_rows)
-static bool lds_small_rides(const RowProblem &p1) { return lds_row_groups(p1.rows, 14) <= kLdsBlocksSmall; }
-
-// Both problems run in ONE launch, i.e. in one kernel shape (the large problem's); together they fill one round.  A tall
-// second problem (T^2 rows: large training sets) gets a launch of its own -- of this kernel too if its row groups leave
-// room for a few spans, else of the fragment-shaped kernel (plan_rows).
-static bool lds_tall_alone(const RowProblem &p1) {
-    return p1.cols >= 4 * kLW && lds_row_groups(p1.rows, 14) <= (kLdsBlocks + kLdsBlocksSmall) / 4;
-}
-void plan_rows_lds(RowProblem &p0, RowProblem &p1) {
-    const int ntg = lds_pick_nt(p0.rows);
-    if (lds_small_rides(p1)) plan_one_lds(p1, kLdsBlocksSmall, ntg);
-    else if (lds_tall_alone(p1)) {
-        plan_one_lds(p1, kLdsBlocks + kLdsBlocksSmall, 14);
-        p1.lds_plan = -14;   // (< 0: planned for a launch of its own)
-    } else {
-        plan_rows(p1, true);
-        p1.lds_plan = 0;
-    }
-    plan_one_lds(p0, kLdsBlocks + kLdsBlocksSmall - (p1.lds_plan > 0 ? p1.nblocks : 0), ntg);
-}
-
-// most spans any plan makes of this problem (the partial buffers are carved for it)
-int rows_max_spans(const RowProblem &P, bool small) {
-    RowProblem a = P, b = P;
-    plan_rows(a, true);
-    // (the 14-tile shape has the fewest row groups, hence the most spans; a tall small problem is planned for a whole
-    //  round of its own)
-    const int nrg = lds_row_groups(P.rows, 14);
-    int spans = (small && nrg <= kLdsBlocksSmall ? kLdsBlocksSmall : kLdsBlocks + kLdsBlocksSmall) / nrg;
-    if (spans < 1) spans = 1;
-    const int64_t chunks = ceil_div(P.cols > 0 ? P.cols : 1, kLW);
-    const int64_t m = ceil_div(chunks, 4 * (int64_t)spans);
-    b.nspans = (int)ceil_div(P.cols > 0 ? P.cols : 1, 4 * kLW * (m < 1 ? 1 : m));
-    return a.nspans > b.nspans ? a.nspans : b.nspans;
-}
+// These kernels put ONE workgroup on a CU (their LDS images fill it) and size their grids for a whole MI355X (kLdsBlocks,
+// kLdsBlocksSmall of kernels.hpp): the plan of gemv_dispatch.hip names them only on a device with that many CUs, and
+// chooses the kernel shape (NT tiles per row group, NCH chunks per image: every shape keeps 16-18 tiles = 32-36 KB in
+// flight per wave) and the span decomposition with it.
 
 // Blocks are dealt to the 8 XCDs round-robin by their index (each XCD has its own L2): the row groups of one span,
 // which read the same pieces of the geometry vectors, get indices that are congruent mod 8 as long as the XCD has
@@ -536,20 +412,15 @@ static int lds_launch(const GemvRowsLaunch &L, const LdsBlockMap &M, int nblocks
     static LdsAttr attr;
     if (int rc = allow_dynamic_lds(gemv_rows_lds_kernel<GS, NT, NCH>, attr, lds, "gemv_rows_lds")) return rc;
     hipLaunchKernelGGL((gemv_rows_lds_kernel<GS, NT, NCH>), dim3(nblocks), dim3(256), lds, st, L, M, g0, G);
-    note_kernel(EVC_PROF_ROWS, "gemv_rows_lds_kernel<%d,%d,%d> G=%d", GS, NT, NCH, G);
+    EVC_LAUNCH_CHECK("gemv_rows_lds");
     return 0;
 }
 
-// most geometries one launch takes with the span plan of `p0`: 64 (four sets) with row groups of <= 7 tiles, else 32
-int rows_lds_max_g(const RowProblem &p0, const RowProblem &p1) {
-    const int ntg = p0.nblocks ? p0.lds_plan : p1.lds_plan;
-    return (ntg >= 1 && ntg <= 7) ? 64 : 32;
-}
-
-int launch_gemv_rows_lds(const GemvRowsLaunch &Lin, int g0, int G, hipStream_t st) {
-    GemvRowsLaunch L = Lin;
-    // one kernel shape per launch: the large problem's (the small problem's row groups are dealt for the same shape)
-    const int ntg = L.p[0].nblocks ? L.p[0].lds_plan : L.p[1].lds_plan;
+// <GS, NT, NCH> = ps.t: one kernel shape per launch, the large problem's (the small problem's row groups are dealt for
+// the same shape).  Four geometry sets (33 .. 64 geometries per pass): 8 accumulator registers per (set, tile) -- 7 tiles
+// at most -- and fewer chunks per image, the four vector tiles of a chunk count.
+int launch_rows_lds(GemvRowsLaunch L, const GemvPass &ps, hipStream_t st) {
+    const int ntg = ps.t[1];
     for (int k = 0; k < 2; ++k) {
         const int nt = (int)ceil_div(L.p[k].rows > 0 ? L.p[k].rows : 1, 16);
         L.nrg[k] = (int)ceil_div(nt, ntg);
@@ -569,26 +440,17 @@ int launch_gemv_rows_lds(const GemvRowsLaunch &Lin, int g0, int G, hipStream_t s
     L.nblk1 = nb1;
     LdsBlockMap M;
     lds_block_map(L, nb1, nb0, M);
-    int rc = -1;
-    // (four geometry sets, 33 .. 64 geometries per pass: 8 accumulator registers per (set, tile) -- 7 tiles at most --
-    //  and fewer chunks per image, the four vector tiles of a chunk count)
-#define EVC_LDS_CASE(NT_, NCH_, NCH4_)                                                 \
-    case NT_:                                                                          \
-        if (G > 32) {                                                                  \
-            if constexpr (NT_ <= 7) rc = lds_launch<4, NT_, NCH4_>(L, M, nb0 + nb1, g0, G, st);                 \
-            else { set_error("gemv_rows_lds: %d geometries need <= 7 tiles per row group", G); return -1; }     \
-        } else                                                                         \
-            rc = G > 16 ? lds_launch<2, NT_, NCH_>(L, M, nb0 + nb1, g0, G, st)         \
-                        : lds_launch<1, NT_, NCH_>(L, M, nb0 + nb1, g0, G, st);        \
-        break;
+    const int nb = nb0 + nb1, gs = ps.t[0], g0 = ps.g0, G = ps.G;
+#define EVC_LDS_12(NT_, NCH_) (gs == 2 ? lds_launch<2, NT_, NCH_>(L, M, nb, g0, G, st) : lds_launch<1, NT_, NCH_>(L, M, nb, g0, G, st))
     switch (ntg) {
-        EVC_LDS_CASE(14, 1, 1) EVC_LDS_CASE(7, 2, 1) EVC_LDS_CASE(4, 3, 2) EVC_LDS_CASE(2, 4, 2)
-        default: set_error("gemv_rows_lds: no kernel for %d tiles per row group", ntg); return -1;
+        case 14: if (gs <= 2) return EVC_LDS_12(14, 1); break;
+        case 7: return gs == 4 ? lds_launch<4, 7, 1>(L, M, nb, g0, G, st) : EVC_LDS_12(7, 2);
+        case 4: return gs == 4 ? lds_launch<4, 4, 2>(L, M, nb, g0, G, st) : EVC_LDS_12(4, 3);
+        case 2: return gs == 4 ? lds_launch<4, 2, 2>(L, M, nb, g0, G, st) : EVC_LDS_12(2, 4);
     }
-#undef EVC_LDS_CASE
-    if (rc) return rc;
-    EVC_LAUNCH_CHECK("gemv_rows_lds");
-    return 0;
+#undef EVC_LDS_12
+    set_error("gemv_rows_lds: no kernel <%d,%d,%d>", ps.t[0], ntg, ps.t[2]);
+    return -1;
 }
 
 // ================================================================================== K8 through LDS-DMA
@@ -981,103 +843,56 @@ __global__ __launch_bounds__(64 * NW, 1) void gemv_cols_lds_kernel(GemvColsLaunc
     else cols_lds_body<GS, D0, NW>(L.p[0], g0, G, blockIdx.x - nblk1, gridDim.x - nblk1, lds_cols, wave, lane);
 }
 
-// ring depth of a problem with `rows` rows and nw waves per workgroup: 24, 12 or 6 pieces, 0: the weights
-// (rows x 32) and the rings do not fit the LDS
-static int cols_lds_depth(int64_t rows, int nw) {
-    const int64_t rows_w = ((rows + 15) / 16) * 16;
-    const int64_t d = (160 * 1024 - rows_w * 256) / (nw * 1024);
-    return d >= 24 ? 24 : (d >= 12 ? 12 : (d >= 6 ? 6 : 0));
-}
-// eight waves per workgroup (two per SIMD): with one wave per SIMD and rings of 24 the loop was bound by its own
-// scalar instructions (54 us against 43 at H30; removed)
-static int cols_lds_waves() { return 8; }
-
-// 0: not applicable; 1: both problems in one launch of gemv_cols_lds_kernel (the weights of all rows fit LDS); 2: tall
-// matrix, both problems in one launch of gemv_cols_lds_slab_kernel
-int cols_lds_mode(const ColProblem &p0, const ColProblem &p1, int G) {
-    static const bool on = !(getenv("EVC_COLS_LDS") && atoi(getenv("EVC_COLS_LDS")) == 0);
-    constexpr bool slab_on = true;
-    static const int64_t min_cols = getenv("EVC_ROWS_LDS_MINCOLS") ? atoll(getenv("EVC_ROWS_LDS_MINCOLS")) : 4096;
-    if (!on || !lds_device_fits() || p0.cols < min_cols || p0.rows <= 0 || !aligned16(p0.A) || p0.ld % 2 ||
-        p0.rows > (1 << 20))
-        return 0;
-    if (16 * p0.ld * 8 >= ((int64_t)1 << 31) || 16 * p1.ld * 8 >= ((int64_t)1 << 31)) return 0;
-    // one set of geometries (G <= 16): the row-split kernel of gemv_mfma.hip is faster (31.8 against 36.1 us at H30)
-    if (G <= 16) return 0;
-    const int nw = cols_lds_waves();
-    if (cols_lds_depth(p0.rows, nw) >= 12) {
-        if (p1.cols > 0 && (cols_lds_depth(p1.rows, nw) < 6 || !aligned16(p1.A) || p1.ld % 2 || p1.part)) return 0;
-        return 1;
-    }
-    // slab kernel: every wave's tiles in one round of <= 4, transposed weights for the LDS-DMA staging, a small second
-    // problem (<= 128 tiles: one per wave of <= 16 workgroups)
-    if (!slab_on || !p0.wt || !aligned16(p0.wt)) return 0;
-    if (ceil_div(ceil_div(p0.cols, 16), (int64_t)8 * kLdsBlocks) > 4) return 0;
-    if (p1.cols > 0 && (p1.cols > 2048 || !aligned16(p1.A) || p1.ld % 2)) return 0;
-    return 2;
-}
-
 template <int GS, int D0, int D1, int NW>
 static int cols_lds_launch(const GemvColsLaunch &L, int nblk1, int nblk0, size_t lds, int g0, int G, hipStream_t st) {
     static LdsAttr attr;
     if (int rc = allow_dynamic_lds(gemv_cols_lds_kernel<GS, D0, D1, NW>, attr, 160 * 1024, "gemv_cols_lds")) return rc;
     hipLaunchKernelGGL((gemv_cols_lds_kernel<GS, D0, D1, NW>), dim3(nblk0 + nblk1), dim3(64 * NW), lds, st, L, nblk1, g0, G);
-    note_kernel(EVC_PROF_COLS, "gemv_cols_lds_kernel<%d,%d,%d,%d>", GS, D0, D1, NW);
+    EVC_LAUNCH_CHECK("gemv_cols_lds");
     return 0;
 }
 
-int launch_gemv_cols_lds(const GemvColsLaunch &L, int g0, int G, hipStream_t st) {
-    const int nw = cols_lds_waves();
-    int d0 = cols_lds_depth(L.p[0].rows, nw);
-    if (nw == 8 && d0 > 12) d0 = 12;
-    const int d1 = L.p[1].cols > 0 ? (cols_lds_depth(L.p[1].rows, nw) >= 12 ? 12 : 6) : 12;
+// <2, 12, D1, 8> = ps.t: two geometry sets (one set stays with the row-split kernel); ring depths of the two problems
+// (the weights, rows x 32, and the rings fit the LDS); eight waves per workgroup (two per SIMD: with one wave per SIMD
+// and rings of 24 the loop was bound by its own scalar instructions, 54 us against 43 at H30; removed).
+// (Both LDS-staged K8 kernels need A 16-byte aligned with an even pitch: every caller has checked that -- check_set of
+// pipeline.hip for the calls on a training set, the roots calls among them, and evc_gemv_cols.)
+int launch_cols_lds(GemvColsLaunch L, const GemvPass &ps, hipStream_t st) {
+    const int d1 = ps.t[2], nw = 8;
     const int nblk1 = L.p[1].cols > 0 ? kLdsBlocksSmall : 0;
     // workgroups of the large problem: every wave the same number of 16-column tiles (rounds), in one round of blocks
     const int64_t ntiles = ceil_div(L.p[0].cols, 16);
     const int64_t rounds = ceil_div(ntiles, (int64_t)nw * kLdsBlocks);
     const int nblk0 = (int)ceil_div(ntiles, nw * rounds);
-    auto need = [&](const ColProblem &P, int d) {
-        const int64_t rows_w = ((P.rows + 15) / 16) * 16;
-        return (size_t)(rows_w * 256 + (int64_t)nw * d * 1024);
-    };
-    size_t lds = need(L.p[0], d0);
+    auto need = [&](const ColProblem &P, int d) { return (size_t)(((P.rows + 15) / 16) * 16 * 256 + (int64_t)nw * d * 1024); };
+    size_t lds = need(L.p[0], 12);
     if (L.p[1].cols > 0 && need(L.p[1], d1) > lds) lds = need(L.p[1], d1);
-    int rc = -1;
-#define EVC_CL_CASE(GS_, D0_, D1_, NW_)                                                              \
-    if ((G > 16 ? 2 : 1) == GS_ && d0 == D0_ && d1 == D1_ && nw == NW_)                              \
-        rc = cols_lds_launch<GS_, D0_, D1_, NW_>(L, nblk1, nblk0, lds, g0, G, st);
-    // (two geometry sets only: one set stays with the row-split kernel, cols_lds_applicable)
-    EVC_CL_CASE(2, 12, 12, 8) EVC_CL_CASE(2, 12, 6, 8)
-#undef EVC_CL_CASE
-    if (rc == -1) set_error("gemv_cols_lds: no kernel for ring depths %d / %d, %d waves", d0, d1, nw);
-    if (rc) return rc;
-    EVC_LAUNCH_CHECK("gemv_cols_lds");
+    return d1 == 12 ? cols_lds_launch<2, 12, 12, 8>(L, nblk1, nblk0, lds, ps.g0, ps.G, st)
+                    : cols_lds_launch<2, 12, 6, 8>(L, nblk1, nblk0, lds, ps.g0, ps.G, st);
+}
+
+template <int NTW>
+static int cols_lds_slab_launch(const GemvColsLaunch &L, int nblk1, int nblk0, int g0, int G, hipStream_t st) {
+    const size_t lds = (size_t)2 * kSlabRows * 256 + (size_t)8 * kSlabRing * 1024;
+    static LdsAttr attr;
+    if (int rc = allow_dynamic_lds(gemv_cols_lds_slab_kernel<2, NTW>, attr, 160 * 1024, "gemv_cols_lds_slab")) return rc;
+    hipLaunchKernelGGL((gemv_cols_lds_slab_kernel<2, NTW>), dim3(nblk0 + nblk1), dim3(512), lds, st, L, nblk1, g0, G);
+    EVC_LAUNCH_CHECK("gemv_cols_lds_slab");
     return 0;
 }
 
-int launch_gemv_cols_lds_slab(const GemvColsLaunch &L, int g0, int G, hipStream_t st) {
-    const int64_t ntiles = ceil_div(L.p[0].cols, 16);
-    const int64_t rounds = ceil_div(ntiles, (int64_t)8 * kLdsBlocks);
-    const int nblk0 = (int)ceil_div(ntiles, 8 * rounds);
+// <2, NTW> = ps.t: every wave's NTW tiles in one round of workgroups
+int launch_cols_lds_slab(GemvColsLaunch L, const GemvPass &ps, hipStream_t st) {
+    const int nblk0 = (int)ceil_div(ceil_div(L.p[0].cols, 16), 8 * ps.t[1]);
     const int nblk1 = L.p[1].cols > 0 ? (int)ceil_div(ceil_div(L.p[1].cols, 16), 8) : 0;
-    const size_t lds = (size_t)2 * kSlabRows * 256 + (size_t)8 * kSlabRing * 1024;
-    int rc = -1;
-#define EVC_SLAB_CASE(NTW_)                                                                                   \
-    if (rounds == NTW_) {                                                                                    \
-        static LdsAttr attr;                                                                                 \
-        if ((rc = allow_dynamic_lds(gemv_cols_lds_slab_kernel<2, NTW_>, attr, 160 * 1024, "gemv_cols_lds_slab"))) \
-            return rc;                                                                                       \
-        hipLaunchKernelGGL((gemv_cols_lds_slab_kernel<2, NTW_>), dim3(nblk0 + nblk1), dim3(512), lds, st, L, nblk1, g0, G); \
-        note_kernel(EVC_PROF_COLS, "gemv_cols_lds_slab_kernel<2,%d>", NTW_);                                  \
+    switch (ps.t[1]) {
+        case 1: return cols_lds_slab_launch<1>(L, nblk1, nblk0, ps.g0, ps.G, st);
+        case 2: return cols_lds_slab_launch<2>(L, nblk1, nblk0, ps.g0, ps.G, st);
+        case 3: return cols_lds_slab_launch<3>(L, nblk1, nblk0, ps.g0, ps.G, st);
+        case 4: return cols_lds_slab_launch<4>(L, nblk1, nblk0, ps.g0, ps.G, st);
     }
-    EVC_SLAB_CASE(1) EVC_SLAB_CASE(2) EVC_SLAB_CASE(3) EVC_SLAB_CASE(4)
-#undef EVC_SLAB_CASE
-    if (rc == -1) {
-        set_error("gemv_cols_lds_slab: no kernel for %lld rounds", (long long)rounds);
-        return -1;
-    }
-    EVC_LAUNCH_CHECK("gemv_cols_lds_slab");
-    return 0;
+    set_error("gemv_cols_lds_slab: no kernel <2,%d>", ps.t[1]);
+    return -1;
 }
 
 }  // namespace evc

@@ -273,39 +273,14 @@ __global__ __launch_bounds__(256, MINW) void gemv_rows_mfma_pipe_kernel(GemvRows
     EVC_K5_WG(2);
 }
 
-int launch_gemv_rows_mfma(const GemvRowsLaunch &Lin, int g0, int G, int tiles, hipStream_t st) {
-    // spans planned for the LDS-staged kernel (gemv_lds.hip: whole-line LDS-DMA instead of fragment-shaped loads)
-    if (Lin.p[0].nblocks ? Lin.p[0].lds_plan : Lin.p[1].lds_plan) {
-        if (Lin.p[0].nblocks && Lin.p[1].nblocks && Lin.p[1].lds_plan <= 0) {
-            // a tall second problem (large training sets: T^2 rows) in its own launch: of the LDS-staged kernel as the
-            // only problem (plan < 0), else of the fragment-shaped kernel
-            GemvRowsLaunch La = Lin, Lb = Lin;
-            La.p[1].nblocks = 0;
-            if (int rc = launch_gemv_rows_lds(La, g0, G, st)) return rc;
-            if (Lin.p[1].lds_plan < 0 && G <= 32) {
-                Lb.p[0] = Lin.p[1];
-                Lb.p[0].lds_plan = -Lin.p[1].lds_plan;
-                Lb.p[1].nblocks = 0;
-                return launch_gemv_rows_lds(Lb, g0, G, st);
-            }
-            Lb.p[0].nblocks = 0;
-            Lb.p[0].lds_plan = 0;
-            Lb.p[1].lds_plan = 0;
-            return launch_gemv_rows_mfma(Lb, g0, G, tiles, st);
-        }
-        return launch_gemv_rows_lds(Lin, g0, G, st);
-    }
-    GemvRowsLaunch L = Lin;
-    const int gs = G > 16 ? 2 : 1;
-    // ONE shape per case, 100*MAXT + 10*MINW + PIPE (the alternatives of rounds 1-3 were measured slower and removed in
-    // round 4 with their knobs): one geometry set 421 (pipelined, in situ at G=16: 189 us against 194-221 for the lean
-    // shapes); two sets 321 on wide matrices (226 us against 238-300) and 711 on narrow ones (< 200 000 columns, the
-    // 8-fold compressed layout: the vectors of the 32 geometries weigh as much as the matrix itself when five row groups
-    // re-read them; two groups of seven tiles on ONE wave per SIMD read them twice: 66 against 76 us)
-    const int shape = gs == 2 ? (Lin.p[0].cols <= 200000 ? 711 : 321) : 421;
-    const int kernel_maxt = shape / 100;
-    int max_tiles = tiles <= 0 ? (kernel_maxt >= 5 ? kernel_maxt : kernel_maxt >= 3 ? 3 : kernel_maxt) : tiles;   // see the measurements above
-    if (max_tiles > kernel_maxt) max_tiles = kernel_maxt;
+// ONE shape (GS, MAXT, MINW, pipelined) per case -- the plan names it (gemv_dispatch.hip); the alternatives of rounds
+// 1-3 were measured slower and removed in round 4 with their knobs: one geometry set <1,4,2> (pipelined, in situ at
+// G=16: 189 us against 194-221 for the lean shapes); two sets <2,3,2> on wide matrices (226 us against 238-300) and
+// <2,7,1> on narrow ones (the 8-fold compressed layout: the vectors of the 32 geometries weigh as much as the matrix
+// itself when five row groups re-read them; two groups of seven tiles on ONE wave per SIMD read them twice: 66 against
+// 76 us)
+int launch_rows_mfma(GemvRowsLaunch L, const GemvPass &ps, hipStream_t st) {
+    const int max_tiles = ps.t[1] == 7 ? 7 : 3;   // (groups of <= 3 tiles also for the 4-tile shape: see the measurements above)
     for (int k = 0; k < 2; ++k) {
         // balanced row groups of at most max_tiles tiles
         const int nt = (int)ceil_div(L.p[k].rows > 0 ? L.p[k].rows : 1, 16);
@@ -318,16 +293,10 @@ int launch_gemv_rows_mfma(const GemvRowsLaunch &Lin, int g0, int G, int tiles, h
     const int nb1 = L.p[1].nblocks ? (int)ceil_div((int64_t)L.nrg[1] * L.p[1].nspans, 8) * 8 : 0;
     L.nblk0 = nb0;
     L.nblk1 = nb1;
-#define EVC_ROWS_LAUNCH(GS_, MAXT_, MINW_, PIPE_)                                                      \
-    do {                                                                                               \
-        hipLaunchKernelGGL((gemv_rows_mfma_pipe_kernel<GS_, MAXT_, MINW_, PIPE_ != 0>), dim3(nb0 + nb1), \
-                           dim3(256), 0, st, L, g0, G);                                                \
-        note_kernel(EVC_PROF_ROWS, "gemv_rows_mfma_pipe_kernel<%d,%d,%d,%d> G=%d", GS_, MAXT_, MINW_, PIPE_, G); \
-    } while (0)
-    if (shape == 711) EVC_ROWS_LAUNCH(2, 7, 1, 1);
-    else if (shape == 321) EVC_ROWS_LAUNCH(2, 3, 2, 1);
-    else EVC_ROWS_LAUNCH(1, 4, 2, 1);
-#undef EVC_ROWS_LAUNCH
+    const dim3 grid(nb0 + nb1);
+    if (ps.t[1] == 7) hipLaunchKernelGGL((gemv_rows_mfma_pipe_kernel<2, 7, 1, true>), grid, dim3(256), 0, st, L, ps.g0, ps.G);
+    else if (ps.t[1] == 3) hipLaunchKernelGGL((gemv_rows_mfma_pipe_kernel<2, 3, 2, true>), grid, dim3(256), 0, st, L, ps.g0, ps.G);
+    else hipLaunchKernelGGL((gemv_rows_mfma_pipe_kernel<1, 4, 2, true>), grid, dim3(256), 0, st, L, ps.g0, ps.G);
     EVC_LAUNCH_CHECK("gemv_rows_mfma");
     return 0;
 }
@@ -514,12 +483,17 @@ __global__ __launch_bounds__(256, MINW) void gemv_cols_mfma_rs_kernel(GemvColsLa
     }
 }
 
-template <int KSN, int MINW, int GS>
-static void cols_mfma_rs_launch(GemvColsLaunch L, int g0, int G, hipStream_t st) {
+// ONE shape per case and number of geometry sets (in situ at H30 / T = 20, us per launch: lean shapes with many waves per
+// SIMD won by a wide margin over wide register-blocked ones -- G=16: 126 -> 138, 224 -> 147, 343 (the first design) ->
+// 193; G=32: 224 -> 182, 214 -> 197, 342 -> 312; the alternatives were removed in round 4 with their knobs): the
+// row-split kernel <KSN, MINW, GS> (K steps 2 / 8, waves per SIMD 6 / 3 for one / two geometry sets) ...
+int launch_cols_mfma_rs(GemvColsLaunch L, const GemvPass &ps, hipStream_t st) {
     L.nblk0 = (int)ceil_div(L.p[0].cols, 32);
-    const int total = L.nblk0 + (int)ceil_div(L.p[1].cols, 32);
-    hipLaunchKernelGGL((gemv_cols_mfma_rs_kernel<KSN, MINW, GS>), dim3(total), dim3(256), 0, st, L, g0, G);
-    note_kernel(EVC_PROF_COLS, "gemv_cols_mfma_rs_kernel<%d,%d,%d>", KSN, MINW, GS);
+    const dim3 grid(L.nblk0 + (int)ceil_div(L.p[1].cols, 32));
+    if (ps.t[2] == 2) hipLaunchKernelGGL((gemv_cols_mfma_rs_kernel<8, 3, 2>), grid, dim3(256), 0, st, L, ps.g0, ps.G);
+    else hipLaunchKernelGGL((gemv_cols_mfma_rs_kernel<2, 6, 1>), grid, dim3(256), 0, st, L, ps.g0, ps.G);
+    EVC_LAUNCH_CHECK("gemv_cols_mfma_rs");
+    return 0;
 }
 
 template <int CT, int KSN, int MINW, int GS>
@@ -535,34 +509,13 @@ static int cols_mfma_launch(GemvColsLaunch L, int g0, int G, hipStream_t st) {
                                    kRowTile * 16 * GS * (int)sizeof(double), "gemv_cols_mfma"))
         return rc;
     hipLaunchKernelGGL((gemv_cols_mfma_kernel<CT, KSN, MINW, GS>), dim3(total), dim3(256), lds, st, L, g0, G);
-    note_kernel(EVC_PROF_COLS, "gemv_cols_mfma_kernel<%d,%d,%d,%d>", CT, KSN, MINW, GS);
+    EVC_LAUNCH_CHECK("gemv_cols_mfma");
     return 0;
 }
 
-int launch_gemv_cols_mfma(GemvColsLaunch L, int g0, int G, hipStream_t st) {
-    if (L.p[0].cols + L.p[1].cols == 0) return 0;
-    // whole-line LDS-DMA pieces, a wave sums over all rows of its column tiles (gemv_lds.hip)
-    const int lds_mode = cols_lds_mode(L.p[0], L.p[1], G);
-    if (lds_mode == 1) return launch_gemv_cols_lds(L, g0, G, st);
-    if (lds_mode == 2 && g0 % kMaxBatchG == 0) return launch_gemv_cols_lds_slab(L, g0, G, st);
-    // ONE shape per case (in situ at H30 / T = 20, us per launch: lean shapes with many waves per SIMD won by a wide
-    // margin over wide register-blocked ones -- G=16: 126 -> 138, 224 -> 147, 343 (the first design) -> 193; G=32:
-    // 224 -> 182, 214 -> 197, 342 -> 312; the alternatives were removed in round 4 with their knobs): the row-split
-    // kernel below 200 000 columns (K steps 2 / 8, waves per SIMD 6 / 3 for one / two geometry sets), the column-tiled
-    // kernel beyond
-    if (L.p[0].cols <= 200000) {
-        if (G > 16) cols_mfma_rs_launch<8, 3, 2>(L, g0, G, st);
-        else cols_mfma_rs_launch<2, 6, 1>(L, g0, G, st);
-        EVC_LAUNCH_CHECK("gemv_cols_mfma_rs");
-        return 0;
-    }
-    if (G > 16) {
-        if (int rc_ = cols_mfma_launch<2, 2, 4, 2>(L, g0, G, st)) return rc_;
-    } else {
-        if (int rc_ = cols_mfma_launch<1, 2, 6, 1>(L, g0, G, st)) return rc_;
-    }
-    EVC_LAUNCH_CHECK("gemv_cols_mfma");
-    return 0;
+// ... and the column-tiled kernel <CT, KSN, MINW, GS>
+int launch_cols_mfma(GemvColsLaunch L, const GemvPass &ps, hipStream_t st) {
+    return ps.t[3] == 2 ? cols_mfma_launch<2, 2, 4, 2>(L, ps.g0, ps.G, st) : cols_mfma_launch<1, 2, 6, 1>(L, ps.g0, ps.G, st);
 }
 
 }  // namespace evc

@@ -2,8 +2,8 @@
 //   K5/K4  rows GEMV   y[g][r]   = sum_c A[r,c] v[g][c]     (H_ab build,      evcont.py:38-68)
 //   K8/K7  cols GEMV   out[g][c] = sum_r w[g][r] A[r,c]     (predicted RDMs,  gradients_loewdin.py:343-356)
 // A (the t-RDM) is shared by a batch of geometries, so one pass over the 0.68-2.6 GB matrix serves
-// G evaluations: G <= 8 per pass with the VALU kernels of this file, 12..32 with the matrix-core
-// variants of gemv_mfma.hip (the dispatch at the bottom of this file picks per group).
+// G evaluations: G <= 8 per pass with the VALU kernels of this file, 12..64 with the matrix-core
+// variants of gemv_mfma.hip and gemv_lds.hip (gemv_dispatch.hip plans the passes of a call).
 // Each launch carries TWO problems (the two-body and the one-body t-RDM) so the small one rides
 // along with the big one instead of costing a kernel boundary.
 #include <stdlib.h>
@@ -207,105 +207,35 @@ __global__ void gemv_rows_reduce_kernel(const double *partial, int64_t rows, int
     y[r] = alpha * s;
 }
 
-constexpr int kRBPlan = 8;  // row-block height the workspace/partials are planned for (all variants use it)
-
-// Span plan.  `batched` selects the finer decomposition the batched (G > 1) kernels want (they own whole
-// row groups, so they need more spans for the same number of workgroups); the partial buffers are sized
-// for the finer plan and the single-geometry kernels simply use fewer spans of the same layout.
-void plan_rows(RowProblem &P, bool batched) {
-    const int64_t nchunks = ceil_div(P.cols, kChunk);
-    const int64_t nrb = ceil_div(P.rows, kRBPlan);
-    // aim at `target` 8-row blocks (span count = target / row blocks) while keeping spans >= min_cps chunks
-    const int target = batched ? 8192 : 2048;
-    const int min_cps = batched ? 2 : 4;
-    int64_t want_spans = ceil_div(target, nrb);
-    int64_t cps = nchunks / want_spans;
-    if (cps < min_cps) cps = nchunks < min_cps ? nchunks : min_cps;
-    if (cps < 1) cps = 1;
-    P.span_cols = cps * kChunk;
-    P.nspans = (int)ceil_div(P.cols, P.span_cols);
-    P.nblocks = (int)(nrb * P.nspans);
-    P.lds_plan = 0;
-}
-
-size_t rows_ws_doubles(int64_t rows, int64_t cols) {
-    RowProblem P{};
-    P.rows = rows;
-    P.cols = cols;
-    return (size_t)rows * rows_max_spans(P, false);
-}
-
-// The span decomposition (span_cols, nspans -> layout of the partials) is fixed by plan_rows; the row-block
-// height RB is a property of the kernel variant only: nblocks = ceil(rows/RB) * nspans.
-template <int RB, int G>
-static void rows_launch(GemvRowsLaunch L, int g0, hipStream_t st) {
-    for (int k = 0; k < 2; ++k)
-        L.p[k].nblocks = L.p[k].nblocks ? (int)(ceil_div(L.p[k].rows, RB) * L.p[k].nspans) : 0;
+// The span decomposition (span_cols, nspans -> layout of the partials) comes with the plan; the rows a block takes are
+// a property of the kernel variant only: nblocks = ceil(rows / rows per block) * nspans.
+static dim3 rows_grid(GemvRowsLaunch &L, int rows_per_block) {
+    for (RowProblem &P : L.p) P.nblocks = P.nblocks ? (int)(ceil_div(P.rows, rows_per_block) * P.nspans) : 0;
     L.nblk0 = L.p[0].nblocks;
-    hipLaunchKernelGGL((gemv_rows_kernel<RB, G>), dim3(L.p[0].nblocks + L.p[1].nblocks), dim3(256), 0, st, L, g0);
-    note_kernel(EVC_PROF_ROWS, "gemv_rows_kernel<%d,%d> G=%d", RB, G, G);
+    return dim3(L.p[0].nblocks + L.p[1].nblocks);
 }
 
-template <int RBW, int G>
-static void rows_wr_launch(GemvRowsLaunch L, int g0, hipStream_t st) {
-    for (int k = 0; k < 2; ++k)
-        L.p[k].nblocks = L.p[k].nblocks ? (int)(ceil_div(L.p[k].rows, 4 * RBW) * L.p[k].nspans) : 0;
-    L.nblk0 = L.p[0].nblocks;
-    hipLaunchKernelGGL((gemv_rows_wr_kernel<RBW, G, 16 / RBW>), dim3(L.p[0].nblocks + L.p[1].nblocks), dim3(256), 0, st,
-                       L, g0);
-    note_kernel(EVC_PROF_ROWS, "gemv_rows_wr_kernel<%d,%d,%d> G=%d", RBW, G, 16 / RBW, G);
+int launch_rows_valu(GemvRowsLaunch L, const GemvPass &ps, hipStream_t st) {
+    const dim3 grid = rows_grid(L, 8);
+    if (ps.G == 2) hipLaunchKernelGGL((gemv_rows_kernel<8, 2>), grid, dim3(256), 0, st, L, ps.g0);
+    else hipLaunchKernelGGL((gemv_rows_kernel<8, 1>), grid, dim3(256), 0, st, L, ps.g0);
+    EVC_LAUNCH_CHECK("gemv_rows");
+    return 0;
 }
 
-static constexpr int mfma_min_g() { return 12; }          // groups of >= this many geometries use the matrix cores
-static constexpr int mfma_max_g() { return kMaxBatchG; }   // geometries per pass over the matrix
-// the grouping of launch_gemv_rows below: true if no group of fewer than mfma_min geometries is left over
-bool rows_groups_all_mfma(int count) {
-    int left = count;
-    while (left > 0) {
-        if (left < mfma_min_g()) return false;
-        left -= left < mfma_max_g() ? left : mfma_max_g();
-    }
-    return count > 0;
+// (wave-rows kernels for 4 / 8 geometries: the lane-private ones were slower)
+int launch_rows_wave_rows(GemvRowsLaunch L, const GemvPass &ps, hipStream_t st) {
+    const dim3 grid = rows_grid(L, ps.G == 8 ? 16 : 32);   // four waves of RBW = 4 / 8 rows
+    if (ps.G == 8) hipLaunchKernelGGL((gemv_rows_wr_kernel<4, 8, 4>), grid, dim3(256), 0, st, L, ps.g0);
+    else hipLaunchKernelGGL((gemv_rows_wr_kernel<8, 4, 2>), grid, dim3(256), 0, st, L, ps.g0);
+    EVC_LAUNCH_CHECK("gemv_rows");
+    return 0;
 }
 
-int launch_gemv_rows(RowProblem p0, RowProblem p1, int count, hipStream_t st) {
-    GemvRowsLaunch L;
-    L.p[0] = p0;
-    L.p[1] = p1;
-    L.nblk0 = p0.nblocks;
-    if (p0.nblocks + p1.nblocks == 0 || count <= 0) return 0;
-    const int mfma_min = mfma_min_g(), mfma_max = mfma_max_g();
-    int g0 = 0;
-    while (g0 < count) {
-        const int left = count - g0;
-        if (left >= mfma_min) {
-            // (the LDS-staged kernel takes up to 64 geometries per pass over the matrix; 64 = 2 x 32 leaves the same
-            //  remainder as the grouping rows_groups_all_mfma assumed when the span plan was chosen)
-            int gmax = mfma_max;
-            const bool lds = p0.nblocks ? p0.lds_plan : p1.lds_plan;
-            if (lds && mfma_max == 32 && left > 32 && !(p0.nblocks && p1.nblocks && p1.lds_plan <= 0))
-                gmax = rows_lds_max_g(p0, p1);
-            const int G = left < gmax ? left : gmax;
-            int rc = launch_gemv_rows_mfma(L, g0, G, 0, st);
-            if (rc) return rc;
-            g0 += G;
-            continue;
-        }
-        if (left >= 8) {
-            rows_wr_launch<4, 8>(L, g0, st);   // (wave-rows kernels for 4 / 8 geometries: the lane-private ones were slower)
-            g0 += 8;
-        } else if (left >= 4) {
-            rows_wr_launch<8, 4>(L, g0, st);
-            g0 += 4;
-        } else if (left >= 2) {
-            rows_launch<8, 2>(L, g0, st);
-            g0 += 2;
-        } else {
-            rows_launch<8, 1>(L, g0, st);
-            g0 += 1;
-        }
-        EVC_LAUNCH_CHECK("gemv_rows");
-    }
+int launch_rows_reduce(const double *partial, int64_t rows, int nspans, double alpha, double *y, hipStream_t st) {
+    hipLaunchKernelGGL(gemv_rows_reduce_kernel, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, partial, rows,
+                       nspans, alpha, y);
+    EVC_LAUNCH_CHECK("gemv_rows_reduce");
     return 0;
 }
 
@@ -413,7 +343,6 @@ __global__ __launch_bounds__(256) void gemv_cols_kernel(GemvColsLaunch L, int g0
 // Row-split variant for matrices with few columns (the 8-fold compressed layout: 212 chunks of 512 columns do not
 // fill 256 CUs): a block owns 128 columns, its four waves take every fourth group of 8 rows and the four partial
 // sums are added in fixed order through LDS.  The row weights are wave-uniform loads.
-constexpr int kColsRsMaxCols = 200000;
 template <int G>
 __global__ __launch_bounds__(256) void gemv_cols_rs_kernel(GemvColsLaunch L, int g0) {
     __shared__ double2 red[4][G][64];
@@ -464,21 +393,6 @@ __global__ __launch_bounds__(256) void gemv_cols_rs_kernel(GemvColsLaunch L, int
             else *o = vx;
         }
     }
-}
-
-template <int G>
-static void cols_launch(const GemvColsLaunch &Lin, int total, int g0, hipStream_t st) {
-    if (Lin.p[0].cols <= kColsRsMaxCols) {
-        GemvColsLaunch L = Lin;
-        L.nblk0 = (int)ceil_div(L.p[0].cols, 128);
-        const int tot = L.nblk0 + (int)ceil_div(L.p[1].cols, 128);
-        hipLaunchKernelGGL((gemv_cols_rs_kernel<G>), dim3(tot), dim3(256), 0, st, L, g0);
-        note_kernel(EVC_PROF_COLS, "gemv_cols_rs_kernel<%d>", G);
-        return;
-    }
-    const GemvColsLaunch &L = Lin;
-    hipLaunchKernelGGL((gemv_cols_kernel<G>), dim3(total), dim3(256), 0, st, L, g0);
-    note_kernel(EVC_PROF_COLS, "gemv_cols_kernel<%d>", G);
 }
 
 // Row-slab form for a NARROW matrix with MANY rows -- the one-body t-RDM of a large training set, (T^2, N^2): 10 000 x 784
@@ -549,96 +463,41 @@ __global__ __launch_bounds__(256) void gemv_cols_slab_reduce_kernel(ColProblem P
     P.out[(int64_t)blockIdx.y * P.ostride + c] = s0 + s1;
 }
 
-int launch_gemv_cols(ColProblem p0, ColProblem p1, int count, hipStream_t st) {
-    if (p1.part && p1.cols > 0 && p1.rows >= 1024 && p1.cols <= 16384 && count > 0 && count < mfma_min_g()) {
-        // (groups of >= 12 geometries go through the matrix-core kernel, whose four waves split the rows of a tile)
-        // the narrow second problem in row slabs (its own two launches), the wide one alone below
-        const int nslab = (int)(p1.rows / 64 < kColSlabs ? p1.rows / 64 : kColSlabs);
-        hipLaunchKernelGGL(gemv_cols_slab_kernel, dim3((unsigned)nslab, (unsigned)ceil_div(p1.cols, kChunk)), dim3(256), 0,
-                           st, p1, count, nslab);
-        EVC_LAUNCH_CHECK("gemv_cols_slab");
-        hipLaunchKernelGGL(gemv_cols_slab_reduce_kernel, dim3((unsigned)ceil_div(p1.cols, 256), (unsigned)count),
-                           dim3(256), 0, st, p1, nslab);
-        EVC_LAUNCH_CHECK("gemv_cols_slab_reduce");
-        p1.cols = 0;
-    }
-    GemvColsLaunch L;
-    L.p[0] = p0;
-    L.p[1] = p1;
-    L.nblk0 = (int)ceil_div(p0.cols, kChunk);
-    const int total = L.nblk0 + (int)ceil_div(p1.cols, kChunk);
-    if (total == 0 || count <= 0) return 0;
-    const int mfma_min = mfma_min_g(), mfma_max = mfma_max_g();
-    int g0 = 0;
-    while (g0 < count) {
-        const int left = count - g0;
-        if (left >= mfma_min) {
-            const int G = left < mfma_max ? left : mfma_max;
-            int rc = launch_gemv_cols_mfma(L, g0, G, st);
-            if (rc) return rc;
-            g0 += G;
-            continue;
-        }
-        if (left >= 8) { cols_launch<8>(L, total, g0, st); g0 += 8; }
-        else if (left >= 4) { cols_launch<4>(L, total, g0, st); g0 += 4; }
-        else if (left >= 2) { cols_launch<2>(L, total, g0, st); g0 += 2; }
-        else { cols_launch<1>(L, total, g0, st); g0 += 1; }
-        EVC_LAUNCH_CHECK("gemv_cols");
-    }
+// G = 1, 2, 4 or 8 geometries [g0, g0 + G): the column-tiled kernel, 512 columns per block
+int launch_cols_valu(GemvColsLaunch L, const GemvPass &ps, hipStream_t st) {
+    L.nblk0 = (int)ceil_div(L.p[0].cols, kChunk);
+    const dim3 grid(L.nblk0 + (int)ceil_div(L.p[1].cols, kChunk));
+    if (ps.G == 8) hipLaunchKernelGGL((gemv_cols_kernel<8>), grid, dim3(256), 0, st, L, ps.g0);
+    else if (ps.G == 4) hipLaunchKernelGGL((gemv_cols_kernel<4>), grid, dim3(256), 0, st, L, ps.g0);
+    else if (ps.G == 2) hipLaunchKernelGGL((gemv_cols_kernel<2>), grid, dim3(256), 0, st, L, ps.g0);
+    else hipLaunchKernelGGL((gemv_cols_kernel<1>), grid, dim3(256), 0, st, L, ps.g0);
+    EVC_LAUNCH_CHECK("gemv_cols");
+    return 0;
+}
+
+// ... the row-split kernel, 128 columns per block
+int launch_cols_valu_rs(GemvColsLaunch L, const GemvPass &ps, hipStream_t st) {
+    L.nblk0 = (int)ceil_div(L.p[0].cols, 128);
+    const dim3 grid(L.nblk0 + (int)ceil_div(L.p[1].cols, 128));
+    if (ps.G == 8) hipLaunchKernelGGL((gemv_cols_rs_kernel<8>), grid, dim3(256), 0, st, L, ps.g0);
+    else if (ps.G == 4) hipLaunchKernelGGL((gemv_cols_rs_kernel<4>), grid, dim3(256), 0, st, L, ps.g0);
+    else if (ps.G == 2) hipLaunchKernelGGL((gemv_cols_rs_kernel<2>), grid, dim3(256), 0, st, L, ps.g0);
+    else hipLaunchKernelGGL((gemv_cols_rs_kernel<1>), grid, dim3(256), 0, st, L, ps.g0);
+    EVC_LAUNCH_CHECK("gemv_cols");
+    return 0;
+}
+
+// the narrow problem L.p[1] in row slabs for all ps.G geometries: the slab launch and the fixed-order sum of the slabs
+int launch_cols_slab(GemvColsLaunch L, const GemvPass &ps, hipStream_t st) {
+    const ColProblem &P = L.p[1];
+    const int nslab = (int)(P.rows / 64 < kColSlabs ? P.rows / 64 : kColSlabs);
+    hipLaunchKernelGGL(gemv_cols_slab_kernel, dim3((unsigned)nslab, (unsigned)ceil_div(P.cols, kChunk)), dim3(256), 0, st,
+                       P, ps.G, nslab);
+    EVC_LAUNCH_CHECK("gemv_cols_slab");
+    hipLaunchKernelGGL(gemv_cols_slab_reduce_kernel, dim3((unsigned)ceil_div(P.cols, 256), (unsigned)ps.G), dim3(256), 0,
+                       st, P, nslab);
+    EVC_LAUNCH_CHECK("gemv_cols_slab_reduce");
     return 0;
 }
 
 }  // namespace evc
-
-// ------------------------------------------------------------------ C ABI
-using namespace evc;
-
-extern "C" size_t evc_gemv_rows_ws_bytes(int64_t rows, int64_t cols) {
-    if (rows <= 0 || cols <= 0) return 0;
-    return rows_ws_doubles(rows, cols) * sizeof(double);
-}
-
-extern "C" int evc_gemv_rows(const double *A, int64_t rows, int64_t cols, int64_t ld, const double *v,
-                             double alpha, double *y, void *ws, size_t ws_bytes, void *stream) {
-    EVC_REQUIRE(rows > 0 && cols > 0, "evc_gemv_rows: rows=%lld cols=%lld must be positive",
-                (long long)rows, (long long)cols);
-    EVC_REQUIRE(A && v && y && ws, "evc_gemv_rows: null pointer");
-    EVC_REQUIRE(ld >= cols && (ld % 2) == 0, "evc_gemv_rows: ld=%lld must be even and >= cols=%lld",
-                (long long)ld, (long long)cols);
-    EVC_REQUIRE(aligned16(A) && aligned16(v), "evc_gemv_rows: A and v must be 16-byte aligned");
-    EVC_REQUIRE(ws_bytes >= evc_gemv_rows_ws_bytes(rows, cols), "evc_gemv_rows: workspace too small");
-    RowProblem P{};
-    P.A = A;
-    P.v = v;
-    P.partial = static_cast<double *>(ws);
-    P.rows = rows;
-    P.cols = cols;
-    P.ld = ld;
-    plan_rows(P, false);
-    RowProblem none{};
-    int rc = launch_gemv_rows(P, none, 1, as_stream(stream));
-    if (rc) return rc;
-    hipLaunchKernelGGL(gemv_rows_reduce_kernel, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0,
-                       as_stream(stream), P.partial, rows, P.nspans, alpha, y);
-    EVC_LAUNCH_CHECK("gemv_rows_reduce");
-    return 0;
-}
-
-extern "C" int evc_gemv_cols(const double *A, int64_t rows, int64_t cols, int64_t ld, const double *w,
-                             double *out, void *stream) {
-    EVC_REQUIRE(rows > 0 && cols > 0, "evc_gemv_cols: rows=%lld cols=%lld must be positive",
-                (long long)rows, (long long)cols);
-    EVC_REQUIRE(A && w && out, "evc_gemv_cols: null pointer");
-    EVC_REQUIRE(ld >= cols && (ld % 2) == 0, "evc_gemv_cols: ld=%lld must be even and >= cols=%lld",
-                (long long)ld, (long long)cols);
-    EVC_REQUIRE(aligned16(A) && aligned16(out), "evc_gemv_cols: A and out must be 16-byte aligned");
-    ColProblem P{};
-    P.A = A;
-    P.w = w;
-    P.out = out;
-    P.rows = rows;
-    P.cols = cols;
-    P.ld = ld;
-    ColProblem none{};
-    return launch_gemv_cols(P, none, 1, as_stream(stream));
-}

@@ -5,6 +5,8 @@
 // to geometry 0 is paired with a stride `sp` in doubles; geometry g uses p + g*sp.  Workspace
 // buffers all share one stride (the per-geometry workspace size), inputs/outputs have their own.
 #pragma once
+#include <vector>
+
 #include "common.hpp"
 
 namespace evc {
@@ -24,15 +26,16 @@ inline int64_t fci_rows_per_block(int64_t dim) {
     return r < kFciMinRows ? kFciMinRows : r;
 }
 
-// ---- gemv_stream.hip ---------------------------------------------------------------
+// ---- K5 / K8, the streaming t-RDM contractions: kernels in gemv_stream.hip (VALU), gemv_mfma.hip (matrix cores,
+//      fragment-shaped loads), gemv_lds.hip (matrix cores, LDS-staged); gemv_dispatch.hip plans the passes of a call
 struct RowProblem {
     const double *A;   // (rows, ld)                       shared by the batch
     const double *v;   // (cols)            + g*vstride
     double *partial;   // (nspans, rows)    + g*pstride
     int64_t rows, cols, ld, vstride, pstride;
-    int nspans, nblocks;
+    int nspans, nblocks;   // nblocks: != 0 = the launch carries this problem (the VALU launchers put their block count here)
     int64_t span_cols;  // columns per span (a multiple of 32; the last span may be shorter): span s = [s, s+1) * span_cols
-    int lds_plan;       // spans planned for the LDS-staged matrix-core kernel (gemv_lds.hip: plan_rows_lds)
+    int reserved;       // (the kernels take two of these by value: the size of the struct is part of their argument layout)
 };
 struct GemvRowsLaunch {
     RowProblem p[2];
@@ -57,24 +60,83 @@ struct GemvColsLaunch {
     ColProblem p[2];
     int nblk0;
 };
-// gemv_mfma.hip: matrix-core variants, G <= kMaxBatchG geometries [g0, g0+G) per launch
-int launch_gemv_rows_mfma(const GemvRowsLaunch &L, int g0, int G, int tiles, hipStream_t st);
-int launch_gemv_cols_mfma(GemvColsLaunch L, int g0, int G, hipStream_t st);
-void plan_rows(RowProblem &P, bool batched);
-// gemv_lds.hip: the LDS-staged rows kernel for groups of 12 .. 32 geometries and its span plan
-bool rows_lds_applicable(const RowProblem &p0, const RowProblem &p1);
-void plan_rows_lds(RowProblem &p0, RowProblem &p1);
-int rows_max_spans(const RowProblem &P, bool small);
-int launch_gemv_rows_lds(const GemvRowsLaunch &L, int g0, int G, hipStream_t st);
-int rows_lds_max_g(const RowProblem &p0, const RowProblem &p1);
-int cols_lds_mode(const ColProblem &p0, const ColProblem &p1, int G);
-int launch_gemv_cols_lds(const GemvColsLaunch &L, int g0, int G, hipStream_t st);
-int launch_gemv_cols_lds_slab(const GemvColsLaunch &L, int g0, int G, hipStream_t st);
-bool rows_groups_all_mfma(int count);   // gemv_stream.hip: every group of a batch of `count` runs on the matrix cores
+
+// One pass over the matrices: geometries [g0, g0 + G) through one kernel instantiation.
+enum GemvKernel {
+    kRowsValu,       // gemv_rows_kernel<RB, G>                          lane-private accumulators, G = 1, 2
+    kRowsWaveRows,   // gemv_rows_wr_kernel<RBW, G, SUB>                 a wave per row set, G = 4, 8
+    kRowsMfma,       // gemv_rows_mfma_pipe_kernel<GS, MAXT, MINW, PIPE> fragment-shaped loads, G = 12 .. 32
+    kRowsLds,        // gemv_rows_lds_kernel<GS, NT, NCH>                LDS-staged, G = 12 .. 64
+    kColsValu,       // gemv_cols_kernel<G>                              column tiles, G = 1, 2, 4, 8
+    kColsValuRs,     // gemv_cols_rs_kernel<G>                           ... the rows split over the waves (narrow matrices)
+    kColsSlab,       // gemv_cols_slab_kernel + its reduce               the small problem in row slabs, all geometries
+    kColsMfma,       // gemv_cols_mfma_kernel<CT, KSN, MINW, GS>         G = 12 .. 32
+    kColsMfmaRs,     // gemv_cols_mfma_rs_kernel<KSN, MINW, GS>          ... narrow matrices
+    kColsLds,        // gemv_cols_lds_kernel<GS, D0, D1, NW>             LDS-staged, all weights in LDS, G = 17 .. 32
+    kColsLdsSlab,    // gemv_cols_lds_slab_kernel<GS, NTW>               ... tall matrices, the weights in slabs
+};
+struct GemvPass {
+    int g0, G;
+    GemvKernel kernel;
+    int t[4];      // the kernel's template parameters, in the order above
+    int slot[2];   // the problem (0: large / two-body, 1: small / one-body) in slot k of the launch, -1: empty.  A tall
+                   // one-body problem in a launch of its own is a second pass with the same g0 and G.
+};
+// The kernel name of a pass as the stage record keeps it (evc_profile_kernel) and evc_trdm_plan_describe prints it
+// (a thread's buffer: valid until its next call).
+const char *gemv_pass_name(const GemvPass &ps);
+
+struct GemvShape {
+    int64_t rows, cols, ld;   // rows <= 0: the call has no such problem
+};
+inline GemvShape gemv_shape(const RowProblem &P) { return {P.rows, P.cols, P.ld}; }
+struct GemvKnobs {       // read once per process (gemv_knobs)
+    bool rows_lds;         // EVC_ROWS_LDS (default 1): the LDS-staged K5 kernel
+    bool cols_lds;         // EVC_COLS_LDS (default 1): the LDS-staged K8 kernels
+    int rows_lds_nt;       // EVC_ROWS_LDS_NT: forces the K5 kernel's tiles per row group (14, 7, 4, 2)
+    int64_t lds_min_cols;  // EVC_ROWS_LDS_MINCOLS (default 4096): narrower matrices stay with the fragment-shaped kernels
+                           // (nothing to stream); 1 sends the small shapes of the parity tests through the LDS kernels
+};
+const GemvKnobs &gemv_knobs();
+// CUs of the current device (0: unknown), the one place that asks HIP.  The LDS-staged kernels put one workgroup on a CU
+// and size their grids for a whole MI355X, kLdsBlocks + kLdsBlocksSmall workgroups in one round: a device (or partition)
+// with fewer CUs keeps the kernels of gemv_mfma.hip.
+int lds_device_cus();
+constexpr int kLdsBlocks = 242;      // workgroups of the large problem: one per CU (the images fill the LDS), one round
+constexpr int kLdsBlocksSmall = 8;   // ... of the small (one-body) problem
+constexpr int kLdsChunkCols = 16;    // columns per wave chunk of the LDS-staged K5 kernel (a span: a multiple of 4 chunks)
+constexpr int kMfmaMinG = 12;        // groups of >= this many geometries use the matrix cores
+
+// The K5 plan of a call: pure functions of the shapes, the batch size, the CU count and the knobs.
+struct GemvSpans {
+    int64_t span_cols;
+    int nspans;
+};
+struct RowsPlan {
+    GemvSpans spans[2];   // span decomposition of the two problems (-> layout of the partials)
+    std::vector<GemvPass> passes;
+    void apply(RowProblem &p0, RowProblem &p1) const;   // span_cols, nspans; nblocks != 0 iff the call has the problem
+};
+RowsPlan plan_gemv_rows(const GemvShape &p0, const GemvShape &p1, int count, int device_cus, const GemvKnobs &knobs);
+// ... and the K8 plan; wt / part: the call brings the transposed weights / the slab scratch of the small problem
+std::vector<GemvPass> plan_gemv_cols(const GemvShape &p0, const GemvShape &p1, int count, bool wt, bool part,
+                                     int device_cus, const GemvKnobs &knobs);
+// most spans any plan makes of a problem, on any device with any knobs (the partial buffers are carved for it)
+int rows_max_spans(const GemvShape &P, bool small);
 size_t rows_ws_doubles(int64_t rows, int64_t cols);
-// `count` geometries; launched in groups of up to kMaxBatchG that share one read of A.
+// `count` geometries in the passes of the plan.  PRECONDITION of launch_gemv_rows: span_cols / nspans of p0, p1 are those
+// of plan_gemv_rows for the same shapes and `count` on this device (RowsPlan::apply: pipeline.hip replan, evc_gemv_rows)
+// -- the kernels write, and the consumer sums, the spans the caller names; a problem with nblocks == 0 is left out.
 int launch_gemv_rows(RowProblem p0, RowProblem p1, int count, hipStream_t st);
 int launch_gemv_cols(ColProblem p0, ColProblem p1, int count, hipStream_t st);
+// One launcher per kernel family, in the order of GemvKernel: exactly the instantiation ps.t for the geometries of the
+// pass (the plan names only instantiations that exist).
+using RowsLauncher = int(GemvRowsLaunch L, const GemvPass &ps, hipStream_t st);
+using ColsLauncher = int(GemvColsLaunch L, const GemvPass &ps, hipStream_t st);
+RowsLauncher launch_rows_valu, launch_rows_wave_rows, launch_rows_mfma, launch_rows_lds;
+ColsLauncher launch_cols_valu, launch_cols_valu_rs, launch_cols_slab, launch_cols_mfma, launch_cols_mfma_rs, launch_cols_lds,
+    launch_cols_lds_slab;
+int launch_rows_reduce(const double *partial, int64_t rows, int nspans, double alpha, double *y, hipStream_t st);
 
 // ---- transform.hip, pack.hip, y2.hip, ip1.hip ----------------------------------------
 int launch_quarter_transform(const double *in, int64_t sin, const double *C, int64_t sC, int c_transposed, int n,

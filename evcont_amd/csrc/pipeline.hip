@@ -201,15 +201,12 @@ static void carve(const evc_trdm_set *t, int natm, char *base, Ws &w) {
     w.rp2.rows = t->rows2;
     w.rp2.cols = t->cols2;
     w.rp2.ld = t->ld2;
-    // buffers are sized for the finer (batched) span plan; replan() picks the plan of the actual call
-    if (t->rows2 > 0) plan_rows(w.rp2, true);
     w.rp1.rows = (int64_t)T * T;
     w.rp1.cols = (int64_t)n2;
     w.rp1.ld = t->ld1;
-    plan_rows(w.rp1, true);
-    // (carved for whichever span plan makes more spans: plan_rows or the LDS-staged kernel's, gemv_lds.hip)
-    w.h2part = take((size_t)t->rows2 * (t->rows2 > 0 ? rows_max_spans(w.rp2, false) : 1) + 1);
-    w.h1part = take((size_t)T * T * rows_max_spans(w.rp1, true));
+    // (carved for the span plan with the most spans, gemv_dispatch.hip; replan() picks the plan of the actual call)
+    w.h2part = take((size_t)t->rows2 * (t->rows2 > 0 ? rows_max_spans(gemv_shape(w.rp2), false) : 1) + 1);
+    w.h1part = take((size_t)T * T * rows_max_spans(gemv_shape(w.rp1), true));
     w.h2rows = take((size_t)t->rows2_total);
     w.w2 = take((size_t)t->rows2 + 1);
     w.w2t = take((size_t)t->rows2 * kMaxBatchG + 1);
@@ -376,14 +373,8 @@ static int loewdin_split_mode(int n, int ntrain, int count, bool loewdin_done, b
 }
 
 // Span plan of this call (never more spans than the buffers were carved for).
-static void replan(const evc_trdm_set *t, Ws &w, int count) {
-    const bool batched = count > 1;
-    if (t->rows2 > 0 && rows_groups_all_mfma(count) && rows_lds_applicable(w.rp2, w.rp1)) {
-        plan_rows_lds(w.rp2, w.rp1);
-        return;
-    }
-    if (t->rows2 > 0) plan_rows(w.rp2, batched);
-    plan_rows(w.rp1, batched);
+static void replan(Ws &w, int count) {
+    plan_gemv_rows(gemv_shape(w.rp2), gemv_shape(w.rp1), count, lds_device_cus(), gemv_knobs()).apply(w.rp2, w.rp1);
 }
 
 // The Loewdin step of the geometries g into the workspace slots w (part 0: everything in one launch).
@@ -1009,7 +1000,7 @@ static int setup(const char *who, const evc_trdm_set *t, Geo &g, int flags, void
     carve(t, g.natm, static_cast<char *>(ws), w);
     EVC_REQUIRE(ws_bytes >= w.bytes * (size_t)slots, "%s: workspace too small: %zu < %zu", who, ws_bytes,
                 w.bytes * (size_t)slots);
-    replan(t, w, slots);
+    replan(w, slots);
     w.warm = (flags & EVC_FLAG_WARM_START) != 0;
     w.loewdin_done = (flags & EVC_FLAG_LOEWDIN_DONE) != 0;
     g.eri_s4 = (flags & EVC_FLAG_ERI_S4) ? 1 : 0;

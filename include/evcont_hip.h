@@ -42,7 +42,8 @@ extern "C" {
                                  evc_phase_gradient_roots_batch, evc_workspace_bytes_roots_batch;
                                  evc_fci_excite, evc_fci_trdm_rows, evc_fci_sigma, evc_fci_workspace_bytes and the
                                  stages EVC_PROF_FCI_*; additive: evc_fci_hdiag, evc_fci_dots, evc_fci_combine,
-                                 evc_fci_davidson_correction, evc_fci_solve_workspace_bytes, EVC_PROF_FCI_SOLVE */
+                                 evc_fci_davidson_correction, evc_fci_solve_workspace_bytes, EVC_PROF_FCI_SOLVE;
+                                 evc_trdm_plan_describe */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -516,6 +517,17 @@ int evc_profile_select(unsigned stage_mask);
  * evc_energy_with_grad_batch all eight, an evc_phase_* call the stages of its phase), so a stage the last call did not
  * run reads "".  Process-wide: not meaningful while calls run concurrently on several host threads. */
 const char *evc_profile_kernel(int stage);
+
+/* The K5 / K8 dispatch of a call of `count` geometries (slots) on `t`, as text, one line per pass over the t-RDM -- first
+ * the K5 passes, then the K8 passes of the gradient phase:
+ *   "K5 g0=<first geometry> G=<geometries> <kernel> nspans=<two-body>,<one-body>"   (0: not carried by this pass)
+ *   "K8 g0=<first geometry> G=<geometries> <kernel>"
+ * <kernel> is the name evc_profile_kernel reports when that pass is the stage's last.  A pure function of the integer
+ * fields of `t` (n, ntrain, rows2, cols2, ld2, ld1; no pointer is read), count, the knobs EVC_ROWS_LDS, EVC_ROWS_LDS_NT,
+ * EVC_ROWS_LDS_MINCOLS, EVC_COLS_LDS and the CU count of the device: device_cus > 0 names it (no device is needed),
+ * device_cus <= 0 asks the current device.  Writes at most buf_len - 1 characters and a NUL; returns the length of the
+ * whole text, -1 on an invalid argument. */
+int evc_trdm_plan_describe(const evc_trdm_set *t, int count, int device_cus, char *buf, size_t buf_len);
 
 #ifdef __cplusplus
 }

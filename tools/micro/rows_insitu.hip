@@ -1,8 +1,9 @@
-// Microbenchmark 3: the PRODUCT batched rows kernels (csrc/gemv_mfma.hip, csrc/gemv_stream.hip compiled
+// Microbenchmark 3: the PRODUCT batched rows kernels (csrc/gemv_dispatch.hip and the three kernel files compiled
 // in) on a bare matrix, to bisect what separates them from a plain stream: rows 192/208/210, with and
 // without the small second problem, with the V vectors close together or a workspace apart.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../include -I../../evcont_amd/csrc rows_insitu.hip \
-//         ../../evcont_amd/csrc/gemv_mfma.hip ../../evcont_amd/csrc/gemv_stream.hip -o /tmp/rows_insitu
+//         ../../evcont_amd/csrc/gemv_dispatch.hip ../../evcont_amd/csrc/gemv_stream.hip \
+//         ../../evcont_amd/csrc/gemv_mfma.hip ../../evcont_amd/csrc/gemv_lds.hip -o /tmp/rows_insitu
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -18,6 +19,7 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
     fputc('\n', stderr);
 }
+void note_kernel(int, const char *, ...) {}
 }  // namespace evc
 
 __global__ void fill(double *p, int64_t n, unsigned seed) {
@@ -65,7 +67,6 @@ int main(int argc, char **argv) {
                 p0.ld = ld;
                 p0.vstride = far ? wsstride : ld;
                 p0.pstride = wsstride;
-                evc::plan_rows(p0, true);
                 p1.A = A1;
                 p1.v = V + 1000000;
                 p1.partial = part + 1500000;
@@ -74,8 +75,9 @@ int main(int argc, char **argv) {
                 p1.ld = 900;
                 p1.vstride = far ? wsstride : ld;
                 p1.pstride = wsstride;
-                evc::plan_rows(p1, true);
-                if (!with_p1) p1.nblocks = 0;
+                if (!with_p1) p1.rows = 0;
+                evc::plan_gemv_rows(evc::gemv_shape(p0), evc::gemv_shape(p1), G, evc::lds_device_cus(), evc::gemv_knobs())
+                    .apply(p0, p1);
                 for (int i = 0; i < 3; ++i) evc::launch_gemv_rows(p0, p1, G, 0);
                 hipDeviceSynchronize();
                 const int reps = 20;
@@ -87,8 +89,9 @@ int main(int argc, char **argv) {
                 hipEventElapsedTime(&ms, e0, e1);
                 ms /= reps;
                 const double bytes = rows * cols * 8.0;
-                printf("rows %3lld  p1 %d  V %s  spans %4d cps %d : %.1f us  %.0f GB/s (A only)\n", (long long)rows,
-                       with_p1, far ? "far " : "near", p0.nspans, p0.cps, ms * 1e3, bytes / (ms * 1e-3) / 1e9);
+                printf("rows %3lld  p1 %d  V %s  spans %4d of %lld columns : %.1f us  %.0f GB/s (A only)\n", (long long)rows,
+                       with_p1, far ? "far " : "near", p0.nspans, (long long)p0.span_cols, ms * 1e3,
+                       bytes / (ms * 1e-3) / 1e9);
             }
     return 0;
 }
