@@ -7,6 +7,8 @@ PySCF's ``kernel(h1, h2, norb, nelec, nroots=)`` / ``trans_rdm12(bra, ket, norb,
 default is ``pyscf.fci.direct_spin0.FCI()`` when PySCF is importable and ``fci_small.SmallFCI`` otherwise.
 A solver that also has ``trans_rdm12_rows(bra, kets, norb, nelec) -> (ovlp, dm1, dm2)`` (``fci_device.DeviceFCI``: the
 sigma vector and the t-RDMs on the GPU, opt-in) is asked for the t-RDMs of a new state in that one call.
+With ``cibasis != "OAO"`` the states are solved in that basis and rotated into the OAO basis by the solver's
+``transform_ci(ci, nelec, u)`` when it has one (``SmallFCI``, ``DeviceFCI``), by PySCF's otherwise.
 """
 from __future__ import annotations
 
@@ -54,8 +56,11 @@ class FCI_EVCont_obj(TRDMContainer):
         if nroots_train == 1:
             e_all, fcivec_all = [e_all], [fcivec_all]
         if self.cibasis != "OAO":
-            # rotate the CI vectors from the solver's basis into the OAO basis (:80-87)
-            from pyscf.fci.addons import transform_ci
+            # rotate the CI vectors from the solver's basis into the OAO basis (:80-87): with the solver's own
+            # transform_ci where it has one (fci_small.SmallFCI on the host, fci_device.DeviceFCI on the GPU)
+            transform_ci = getattr(self.cisolver, "transform_ci", None)
+            if transform_ci is None:
+                from pyscf.fci.addons import transform_ci
             S = mol.S if is_array_mol(mol) else mol.intor("int1e_ovlp")
             u = np.einsum("ji,jk,kl->il", basis, S, get_basis(mol))
             fcivec_all = [transform_ci(v, mol.nelec, u) for v in fcivec_all]

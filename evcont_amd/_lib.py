@@ -140,6 +140,9 @@ SIGNATURES = {
     "evc_fci_davidson_correction": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_fci_rotate_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "evc_fci_rotate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_profile_begin": (C.c_int, [C.c_int]),
     "evc_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int)]),
@@ -157,6 +160,8 @@ FCI_PROF_STAGES = {"fci_excite": 8, "fci_trdm": 9, "fci_sigma": 10}
 # the vector kernels of the device eigensolver (EVC_PROF_FCI_SOLVE): kept apart from the three stages above, which every
 # evc_fci_trdm_rows / evc_fci_sigma call sets
 FCI_PROF_SOLVE = 11
+# evc_fci_rotate (EVC_PROF_FCI_ROTATE)
+FCI_PROF_ROTATE = 12
 FCI_DET_MAJOR, FCI_DET_MAJOR_T, FCI_ORB_MAJOR = 0, 1, 2
 
 _lib: Optional[C.CDLL] = None

@@ -29,7 +29,7 @@ void set_error(const char *fmt, ...) {
 // recorded on the launch stream right before/after the kernel, so the figure is the kernel's own
 // duration inside the real per-geometry DAG.  Process-wide, off by default.
 // Stages: EVC_PROF_* of include/evcont_hip.h.
-constexpr int kProfStages = 12;
+constexpr int kProfStages = 13;
 static char g_kernel_ran[kProfStages][96];
 void note_kernel(int stage, const char *fmt, ...) {
     if (stage < 0 || stage >= kProfStages) return;

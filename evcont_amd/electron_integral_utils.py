@@ -48,10 +48,19 @@ def restore_electron_exchange_symmetry(h2, norb):
 
 def get_basis(mol, basis_type="OAO"):
     """AO->MO coefficients of an orthogonal basis (reference :91-119).  Only the OAO branch is on
-    the accelerated path; the canonical / split-localised branches are PySCF host code."""
+    the accelerated path; the canonical / split-localised branches are host code: PySCF for PySCF mols, for
+    array-level mols ``scf_small.rhf`` (canonical only)."""
     if basis_type == "OAO":
         S = mol.S if is_array_mol(mol) else mol.intor("int1e_ovlp")
         return get_loewdin_trafo(S)
+    if is_array_mol(mol):
+        if basis_type == "split":
+            raise NotImplementedError("get_basis: the split-localised basis needs PySCF's Boys localisation, which reads "
+                                      "dipole integrals a PySCF Mole provides and an array-level mol does not carry")
+        assert basis_type == "canonical"
+        from .scf_small import rhf
+        ao = ao_arrays(mol, need_grad=False)
+        return rhf(ao.S, ao.hcore, ao.eri, mol.nelec)[0]
     from pyscf import scf, lo  # host-side PySCF, exactly as the reference does
     myhf = scf.RHF(mol)
     _ = myhf.scf()

@@ -5,8 +5,10 @@ GPU (``csrc/fci.hip``): the sigma vector ``H c`` and the transition RDMs.  Same 
     dm1, dm2 = solver.trans_rdm12(cibra, ciket, norb, nelec)       # dm1[p,q] = <q^+ p>, dm2[p,q,r,s] = <p^+ r^+ s q>
 
 plus ``trans_rdm12_rows(bra, kets, norb, nelec)``: one bra against all kets in one pass, which is what
-``FCI_EVCont_obj.append_to_rdms`` needs for a new training state.  Opt in with
-``FCI_EVCont_obj(cisolver=DeviceFCI(), cibasis="OAO")``.
+``FCI_EVCont_obj.append_to_rdms`` needs for a new training state, and ``transform_ci(ci, nelec, u)``
+(``csrc/fci_rotate.hip``), which rotates a state solved in another orbital basis into the OAO basis.  Opt in with
+``FCI_EVCont_obj(cisolver=DeviceFCI(), cibasis="OAO")``, or ``cibasis="canonical"`` to solve in the Hartree-Fock basis,
+where the Davidson solver's diagonal preconditioner works best near equilibrium.
 
 Limits: ``norb <= 16``, real CI vectors, any ``(n_alpha, n_beta)``.  By default the eigensolver iteration of ``kernel``
 stays on the host (``scipy.sparse.linalg.eigsh``); every matrix-vector product it asks for is a device sigma vector that
@@ -27,6 +29,7 @@ from scipy.sparse.linalg import LinearOperator, eigsh
 from . import _lib
 from .fci_davidson import DavidsonOps, davidson
 from ._lib import EvcontHipError, check
+from .fci_small import _strings
 from .fci_tables import MAX_ORB, packed_table
 
 F64 = torch.float64
@@ -128,6 +131,7 @@ class _DeviceOps(DavidsonOps):
 
 
 EIGENSOLVERS = ("host", "davidson")
+ROTATE_RESIDENT_BYTES = 1 << 28     # transform_ci: largest workspace granted without being asked (256 MiB)
 
 
 class DeviceFCI:
@@ -157,6 +161,7 @@ class DeviceFCI:
         self._device_arg = device
         self._device = None
         self._tables = {}
+        self._masks = {}    # (norb, nelec) -> occupation masks of the alpha / beta strings on the device (transform_ci)
         self._ws = None
         # id(host array) -> (host array, host copy of what was uploaded, device tensor): CI vectors already uploaded
         self._vecs = {}
@@ -198,6 +203,9 @@ class DeviceFCI:
             dta = torch.from_numpy(ta).to(dev)
             dtb = dta if tb is ta else torch.from_numpy(tb).to(dev)
             self._tables[key] = (dta, dtb, na, nb, min(grant, full))
+            dsa = torch.tensor(_strings(norb, nelec[0]), dtype=torch.int32, device=dev)
+            dsb = dsa if nelec[1] == nelec[0] else torch.tensor(_strings(norb, nelec[1]), dtype=torch.int32, device=dev)
+            self._masks[key] = (dsa, dsb)
         dta, dtb, na, nb, grant = self._tables[key]
         if self._ws is None or self._ws.numel() < grant:
             self._ws = None
@@ -351,6 +359,44 @@ class DeviceFCI:
 
     def make_rdm12(self, ci, norb, nelec):
         return self.trans_rdm12(ci, ci, norb, nelec)
+
+    def transform_ci(self, ci, nelec, u):
+        """The CI vector in the orbitals ``new_q = sum_p old_p u[p, q]`` (``fci_small.transform_ci``; ``u`` square, or a
+        pair ``(u_a, u_b)``), numpy ``(na, nb)``: the minors of ``u`` and the two products ``T_a^T c T_b`` on the device
+        (``csrc/fci_rotate.hip``).  ``workspace_bytes`` bounds the workspace of this call as it does the others'; the
+        result has the same bits for every accepted value.  Without it the workspace keeps both matrices of minors
+        resident where that takes at most ``ROTATE_RESIDENT_BYTES`` (up to about (14, (6, 6))) and is the least one
+        beyond (7 MB instead of 2.7 GB at (16, (8, 8)))."""
+        nelec = _nelec(nelec)
+        if isinstance(u, (tuple, list)):
+            ua, ub = (np.ascontiguousarray(x, dtype=np.float64) for x in u)
+        else:
+            ua = ub = np.ascontiguousarray(u, dtype=np.float64)
+        norb = ua.shape[0]
+        if ua.shape != (norb, norb) or ub.shape != (norb, norb):
+            raise EvcontHipError(f"DeviceFCI.transform_ci: u of shape {ua.shape} / {ub.shape} (square matrices of one size)")
+        lib, _, _, na, nb, _ = self._setup(norb, nelec)
+        dsa, dsb = self._masks[(norb, nelec)]
+        least = lib.evc_fci_rotate_workspace_bytes(norb, nelec[0], nelec[1], na, nb, 1)
+        full = lib.evc_fci_rotate_workspace_bytes(norb, nelec[0], nelec[1], na, nb, 0)
+        if least == 0 or full == 0:
+            check(-1, "evc_fci_rotate_workspace_bytes")
+        # by default both matrices of minors stay resident up to ROTATE_RESIDENT_BYTES, beyond that T is formed and
+        # consumed in panels (the same bits, one T formed twice when both spins share it)
+        grant = ((full if full <= ROTATE_RESIDENT_BYTES else least) if self.workspace_bytes is None
+                 else min(int(self.workspace_bytes), full))
+        if grant < least:
+            raise EvcontHipError(f"DeviceFCI.transform_ci: workspace_bytes={grant}, but {na} x {nb} strings need at least "
+                                 f"{least} bytes ({full} to keep both matrices of minors resident)")
+        if self._ws.numel() < grant:
+            self._ws = None
+            self._ws = torch.empty(grant, dtype=torch.uint8, device=self._dev())
+        dc = self._upload(ci, na, nb, cache=False)
+        out = torch.empty(na * nb, dtype=F64, device=dc.device)
+        check(lib.evc_fci_rotate(norb, nelec[0], nelec[1], na, nb, dsa.data_ptr(), dsb.data_ptr(), ua.ctypes.data,
+                                 ub.ctypes.data, dc.data_ptr(), out.data_ptr(), self._ws.data_ptr(), grant,
+                                 self._stream()), "evc_fci_rotate")
+        return out.cpu().numpy().reshape(na, nb)
 
     def energy(self, h1, h2, ci, norb, nelec) -> float:
         dm1, dm2 = self.make_rdm12(ci, norb, nelec)

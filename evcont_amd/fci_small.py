@@ -10,6 +10,9 @@ over alpha/beta occupation strings ordered by their integer value; ``dm1[p,q] = 
 ``dm2[p,q,r,s] = <p^+ r^+ s q>`` (chemists' order, spin summed), so that
 ``E = h1:dm1 + 1/2 h2:dm2`` with ``h2`` in chemists' notation.
 
+``transform_ci(ci, nelec, u)`` rotates a CI vector under an orbital transformation (PySCF's ``fci.addons.transform_ci``),
+so that a state solved in the canonical basis can be stored in the OAO basis.
+
 Host code for up to ~12 orbitals (training-state generation is outside the accelerated hot path).
 """
 from __future__ import annotations
@@ -49,6 +52,46 @@ def _excitation_ops(norb: int, nocc: int):
                 rows.append(index[t]); cols.append(j); vals.append(-1.0 if between & 1 else 1.0)
             ops[p][q] = sp.csr_matrix((vals, (rows, cols)), shape=(ns, ns))
     return ops, ns
+
+
+def _nelec_pair(nelec) -> Tuple[int, int]:
+    if isinstance(nelec, (int, np.integer)):
+        return (int(nelec) + 1) // 2, int(nelec) // 2
+    return int(nelec[0]), int(nelec[1])
+
+
+def minor_matrix(u, norb: int, nocc: int) -> np.ndarray:
+    """``T[I, J] = det(u[occ(I)][:, occ(J)])`` over the strings of ``nocc`` electrons in ``norb`` orbitals, ordered by
+    integer value; ``occ(I)`` ascending.  ``[[1]]`` for ``nocc == 0``."""
+    u = np.asarray(u, dtype=np.float64)
+    if u.shape != (norb, norb):
+        raise ValueError(f"transform_ci: u of shape {u.shape} for {norb} orbitals (square u only)")
+    occ = [[p for p in range(norb) if (s >> p) & 1] for s in _strings(norb, nocc)]
+    if nocc == 0:
+        return np.ones((1, 1))
+    occ = np.array(occ)
+    ns = len(occ)
+    T = np.empty((ns, ns))
+    rows = max(1, (1 << 21) // (ns * nocc * nocc))          # row blocks of about 16 MB of (rows, ns, k, k) submatrices
+    for i0 in range(0, ns, rows):
+        T[i0:i0 + rows] = np.linalg.det(u[occ[i0:i0 + rows, None, :, None], occ[None, :, None, :]])
+    return T
+
+
+def transform_ci(ci, nelec, u) -> np.ndarray:
+    """The CI vector in the orbitals ``new_q = sum_p old_p u[p, q]`` (``pyscf.fci.addons.transform_ci`` for a square
+    ``u``, or a pair ``(u_a, u_b)``): ``T_a^T c T_b`` with the matrices of minors above.  Nothing assumes ``u``
+    orthogonal."""
+    na_el, nb_el = _nelec_pair(nelec)
+    if isinstance(u, (tuple, list)):
+        ua, ub = (np.asarray(x, dtype=np.float64) for x in u)
+    else:
+        ua = ub = np.asarray(u, dtype=np.float64)
+    norb = ua.shape[0]
+    Ta = minor_matrix(ua, norb, na_el)
+    Tb = Ta if (ub is ua and nb_el == na_el) else minor_matrix(ub, norb, nb_el)
+    c = np.asarray(ci, dtype=np.float64).reshape(Ta.shape[0], Tb.shape[0])
+    return Ta.T @ c @ Tb
 
 
 class SmallFCI:
@@ -143,6 +186,11 @@ class SmallFCI:
 
     def make_rdm12(self, ci, norb, nelec):
         return self.trans_rdm12(ci, ci, norb, nelec)
+
+    def transform_ci(self, ci, nelec, u):
+        """``fci_small.transform_ci``: what ``FCI_EVCont_obj`` calls to bring a state solved in another orbital basis
+        into the OAO basis."""
+        return transform_ci(ci, nelec, u)
 
     def energy(self, h1, h2, ci, norb, nelec) -> float:
         dm1, dm2 = self.make_rdm12(ci, norb, nelec)

@@ -43,6 +43,10 @@ p.add_argument("--solver", choices=("host", "device", "device-davidson"), defaul
                help="FCI solver of the training states and the exact energies: fci_small.SmallFCI (default), "
                     "fci_device.DeviceFCI (sigma vectors and transition RDMs on the GPU: seconds instead of minutes), or "
                     "DeviceFCI with its block Davidson eigensolver on device-resident vectors")
+p.add_argument("--cibasis", choices=("OAO", "canonical"), default="OAO",
+               help="orbital basis the training states are solved in: the Loewdin basis (default), or the Hartree-Fock "
+                    "basis (scf_small.rhf; fewer Davidson iterations near equilibrium), from which the solver's "
+                    "transform_ci rotates each state into the Loewdin basis")
 a = p.parse_args()
 
 
@@ -64,7 +68,7 @@ def get_mol(positions, need_grad=True):
     return s_gaussian_mol(np.asarray(positions), exponents=ex, coefficients=co, need_grad=need_grad)
 
 
-continuation_object = FCI_EVCont_obj(cisolver=make_solver(), cibasis="OAO")
+continuation_object = FCI_EVCont_obj(cisolver=make_solver(), cibasis=a.cibasis)
 if a.fixture:
     with np.load(os.path.join(REPO, "tests", "golden", "h10_fci_t5.npz")) as z:
         continuation_object.overlap, continuation_object.one_rdm = z["overlap"], z["one_rdm"]

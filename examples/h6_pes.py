@@ -41,13 +41,16 @@ def main():
     p.add_argument("--solver", choices=("host", "device", "device-davidson"), default="host",
                    help="FCI solver of the training states: fci_small.SmallFCI (default), fci_device.DeviceFCI, or "
                         "DeviceFCI with its block Davidson eigensolver on device-resident vectors")
+    p.add_argument("--cibasis", choices=("OAO", "canonical"), default="OAO",
+                   help="orbital basis the FCI is solved in: the Loewdin basis (default), or the Hartree-Fock basis "
+                        "(scf_small.rhf), from which the solver's transform_ci rotates each state into the Loewdin basis")
     a = p.parse_args()
     if a.solver != "host":
         from evcont_amd.fci_device import DeviceFCI
         solver = DeviceFCI(eigensolver="davidson" if a.solver == "device-davidson" else "host")
     else:
         solver = SmallFCI()
-    continuation_object = FCI_EVCont_obj(cisolver=solver, cibasis="OAO")
+    continuation_object = FCI_EVCont_obj(cisolver=solver, cibasis=a.cibasis)
     test_dists = np.linspace(0.8, 3.0)
     test_mols = [get_mol(d) for d in test_dists]
     for i, trn_dist in enumerate([1.0, 1.8, 2.6]):

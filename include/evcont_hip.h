@@ -43,6 +43,7 @@ extern "C" {
                                  evc_fci_excite, evc_fci_trdm_rows, evc_fci_sigma, evc_fci_workspace_bytes and the
                                  stages EVC_PROF_FCI_*; additive: evc_fci_hdiag, evc_fci_dots, evc_fci_combine,
                                  evc_fci_davidson_correction, evc_fci_solve_workspace_bytes, EVC_PROF_FCI_SOLVE;
+                                 additive: evc_fci_rotate, evc_fci_rotate_workspace_bytes, EVC_PROF_FCI_ROTATE;
                                  evc_trdm_plan_describe */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
@@ -485,6 +486,29 @@ int evc_fci_davidson_correction(int64_t dim, const double *V, int64_t ldv, const
                                 int64_t ldt, double *rnorm2, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Rotation of a CI vector under an orbital transformation (PySCF's fci.addons.transform_ci for a square u;
+ * evcont_amd/fci_small.py: transform_ci).  With occ(I) the ascending occupied orbitals of string I and k electrons of a
+ * spin,
+ *       T[I, J] = det( u[occ(I)][:, occ(J)] )   (1 x 1 = [1] for k = 0),      out = T_a^T . c . T_b.
+ * Row index of u: the old orbital, column index: the new one; nothing assumes u orthogonal.
+ *   strs_a (na), strs_b (nb)  DEVICE int32 occupation masks of the strings, ascending (bit p = orbital p); may alias.
+ *   u_a, u_b                  HOST doubles, (norb, norb) row-major, one per spin; may alias.
+ *   c, out                    DEVICE (na, nb); out must not alias c (refused); c is not written.
+ *   ws                        DEVICE workspace, 16-byte aligned, ws_bytes >= evc_fci_rotate_workspace_bytes(..., 1).
+ * Minors of order k <= 8 are computed directly (LU with partial pivoting); for k >= 9 they come from the complementary
+ * minors of u^-1 (Jacobi), which the entry point forms on the host: a u whose smallest pivot is below 1e-12 of its largest
+ * is then refused.  T is formed in panels of columns whose width depends on na / nb alone, and no sum is split: every
+ * accepted workspace gives the same bits, from run to run.
+ * evc_fci_rotate_workspace_bytes(..., minimal): bytes that keep T_a, T_b and the intermediate c . T_b resident
+ *       (minimal = 0), or the least accepted (minimal != 0: the intermediate and one panel of each T).  0 on an argument
+ *       error.  na, nb must be the binomials C(norb, nocc_a), C(norb, nocc_b); 1 <= norb <= 16.
+ * --------------------------------------------------------------------------------- */
+size_t evc_fci_rotate_workspace_bytes(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, int minimal);
+int evc_fci_rotate(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, const int32_t *strs_a,
+                   const int32_t *strs_b, const double *u_a, const double *u_b, const double *c, double *out, void *ws,
+                   size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Measurement hook (bench.py): while enabled, the fused pipeline records hipEvents on the launch
  * stream immediately before and after the launches of the stages below, for up to max_samples
  * evaluations.  evc_profile_end synchronises those events, returns the summed durations in
@@ -505,6 +529,8 @@ int evc_fci_davidson_correction(int64_t dim, const double *V, int64_t ldv, const
 #define EVC_PROF_FCI_SIGMA 10     /* evc_fci_sigma: G = h2 . D and the gather */
 #define EVC_PROF_FCI_SOLVE 11     /* evc_fci_hdiag / _dots / _combine / _davidson_correction: the kernels of the last such
                                      call and its grouping (not cleared by the other evc_fci_* entry points) */
+#define EVC_PROF_FCI_ROTATE 12    /* evc_fci_rotate: the minor kernel of each spin, whether it took the complementary
+                                     minors, the panels of each T, and the product kernel */
 int evc_profile_begin(int max_samples);
 int evc_profile_end(double *rows_ms, int *rows_n, double *cols_ms, int *cols_n);
 int evc_profile_stage(int stage, double *ms, int *launches);

@@ -1,5 +1,6 @@
 """Where the time of ``DeviceFCI.kernel`` goes, for the two eigensolvers, at H10 (5,5) and H12 (6,6), one and two roots
-(hydrogen chain at spacing 1.8 Bohr in the Loewdin basis):
+(hydrogen chain at spacing 1.8 Bohr; ``--cibasis OAO``: the Loewdin basis, ``--cibasis canonical``: the Hartree-Fock
+basis of scf_small.rhf; ``--cibasis OAO canonical`` writes both, one after the other):
 
   host      ``DeviceFCI()``: scipy's eigsh on the host, every product a device sigma vector that is uploaded and downloaded
   davidson  ``DeviceFCI(eigensolver="davidson")``: block Davidson on device-resident vectors (csrc/fci_solve.hip)
@@ -9,7 +10,8 @@ For each: the wall time of one ``kernel`` call (the second of two; the first pay
 vectors, and for the Davidson runs the device time of every kind of call, from HIP events around each call, summed over
 the run and per iteration.
 
-usage: python tools/micro/fci_solve_time.py [--out profiles/fci_solve_time.txt] [--sizes 10 12] [--roots 1 2]"""
+usage: python tools/micro/fci_solve_time.py [--out profiles/fci_solve_time.txt] [--sizes 10 12] [--roots 1 2]
+                                            [--cibasis OAO canonical]"""
 import argparse
 import os
 import sys
@@ -66,9 +68,9 @@ class CountingHost(DeviceFCI):
         return super()._sigma(*a)
 
 
-def integrals(norb, d):
+def integrals(norb, d, cibasis="OAO"):
     mol = hydrogen_chain(norb, d, need_grad=False)
-    return get_integrals(mol, get_basis(mol))
+    return get_integrals(mol, get_basis(mol, cibasis))
 
 
 def wall(fn):
@@ -84,15 +86,16 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "fci_solve_time.txt"))
     ap.add_argument("--sizes", type=int, nargs="*", default=[10, 12])
     ap.add_argument("--roots", type=int, nargs="*", default=[1, 2])
+    ap.add_argument("--cibasis", nargs="*", choices=("OAO", "canonical"), default=["OAO"])
     args = ap.parse_args()
     lines = [f"# tools/micro/fci_solve_time.py on {torch.cuda.get_device_name(0)}: wall time of the second of two "
              f"DeviceFCI.kernel calls; device ms from HIP events around each call of the Davidson back-end (the events "
              f"of dots / correction include the small download that follows the kernels)"]
     plain = fci_device._DeviceOps
-    for norb in args.sizes:
+    for norb, cibasis in ((n, b) for n in args.sizes for b in args.cibasis):
         nelec = (norb // 2, norb // 2)
-        h1, h2 = integrals(norb, 1.8)
-        g1, g2 = integrals(norb, 1.85)
+        h1, h2 = integrals(norb, 1.8, cibasis)
+        g1, g2 = integrals(norb, 1.85, cibasis)
         for nroots in args.roots:
             host = CountingHost()
             host.kernel(h1, h2, norb, nelec, nroots=nroots)
@@ -105,9 +108,10 @@ def main():
             _, near = dav.kernel(g1, g2, norb, nelec, nroots=nroots)
             t_warm, (e_warm, _) = wall(lambda: dav.kernel(h1, h2, norb, nelec, nroots=nroots, ci0=near))
             winfo = dict(dav.davidson_info)
-            de = np.abs(np.atleast_1d(e_host) - np.atleast_1d(e_dav)).max()
             dim = dav._basis[1].shape[1]
-            lines.append(f"\nH{norb} {nelec}, {dim} determinants, {nroots} root(s): |E_davidson - E_host| = {de:.1e}, "
+            de = np.abs(np.atleast_1d(e_host) - np.atleast_1d(e_dav)).max()
+            lines.append(f"\nH{norb} {nelec}, {cibasis} basis, {dim} determinants, {nroots} root(s): "
+                         f"|E_davidson - E_host| = {de:.1e}, "
                          f"|E_warm - E_host| = {np.abs(np.atleast_1d(e_host) - np.atleast_1d(e_warm)).max():.1e}")
             lines.append(f"  host      {1e3 * t_host:9.1f} ms wall, {host.nsigma:4d} sigma vectors "
                          f"({1e3 * t_host / host.nsigma:.2f} ms per product, up- and download included)")
