@@ -55,9 +55,11 @@ def integrals_oao_batch(S: torch.Tensor, hcore: torch.Tensor, eri: torch.Tensor)
 
 
 def subspace_energies(H: torch.Tensor, S: torch.Tensor, e_shift: Optional[torch.Tensor] = None,
-                      nroots: int = 1) -> torch.Tensor:
+                      nroots: int = 1, max_ws_bytes: int = 1 << 30, return_vectors: bool = False):
     """Lowest ``nroots`` generalised eigenvalues of ``count`` problems ``H[g] c = E S[g] c`` (lower triangles,
-    ``scipy.linalg.eigh(H, S)`` semantics) -> (count, nroots).  ``S`` is (T,T) (shared) or (count,T,T)."""
+    ``scipy.linalg.eigh(H, S)`` semantics) -> (count, nroots).  ``S`` is (T,T) (shared) or (count,T,T).
+    ``max_ws_bytes`` bounds the kernel's scratch (at least one problem per launch); with ``return_vectors`` also the
+    eigenvectors (count, nroots, T), row k of a block the k-th vector, ``c S c^T = 1``."""
     lib = _lib.load()
     assert H.dim() == 3 and H.shape[1] == H.shape[2] and H.dtype == F64
     count, T = int(H.shape[0]), int(H.shape[1])
@@ -68,9 +70,10 @@ def subspace_energies(H: torch.Tensor, S: torch.Tensor, e_shift: Optional[torch.
     evals = torch.empty((count, T), dtype=F64, device=H.device)
     evecs = torch.empty((count, T, T), dtype=F64, device=H.device)
     es = e_shift.contiguous() if e_shift is not None else None
-    # T > 32: the kernel needs scratch per problem (evc_subspace_solve_ws_bytes); many problems go in chunks of <= 1 GiB
+    # T > 32: the kernel needs scratch per problem (evc_subspace_solve_ws_bytes); many problems go in chunks of at most
+    # max_ws_bytes
     per = lib.evc_subspace_solve_ws_bytes(T, 1)
-    chunk = count if per == 0 else max(1, min(count, (1 << 30) // per))
+    chunk = count if per == 0 else max(1, min(count, int(max_ws_bytes) // per))
     ws = torch.empty(per * chunk, dtype=torch.uint8, device=H.device) if per else None
     for c0 in range(0, count, chunk):
         c1 = min(count, c0 + chunk)
@@ -79,6 +82,8 @@ def subspace_energies(H: torch.Tensor, S: torch.Tensor, e_shift: Optional[torch.
                                            es[c0:c1].data_ptr() if es is not None else None, evals[c0:c1].data_ptr(),
                                            evecs[c0:c1].data_ptr(), ws.data_ptr() if ws is not None else None,
                                            per * (c1 - c0), _stream_ptr(H.device)), "evc_subspace_solve_batch")
+    if return_vectors:
+        return evals[:, :nroots], evecs[:, :nroots, :]
     return evals[:, :nroots]
 
 

@@ -16,6 +16,9 @@ SUBSET = ["tests/test_gpu_sym8.py::test_packed_ip1_input", "tests/test_gpu_sym8.
           "tests/test_gpu_bench_config.py::test_k5_every_row_group_body"]
 # excited-state forces and couplings (root-pair slots) through the kernels a knob selects
 _ROOTS_LARGE_T = ["tests/test_gpu_excited_forces_batch.py::test_batch_roots_large_T_subspace_kernel"]
+# the batched subspace solve on both kernels (T = 8 | 33): routes, eigenvalues and vectors of mixed spectra in one call
+SUBSPACE_BATCH = ["tests/test_gpu_subspace_batch.py::test_size_and_route_grid[8]",
+                  "tests/test_gpu_subspace_batch.py::test_size_and_route_grid[33]"]
 ROOTS = {
     "EVC_COLS_LDS": ["tests/test_gpu_excited_slots.py::test_batch_roots_eight_slots[P10]"],        # 30 slots in K8
     "EVC_PT_DMA": ["tests/test_gpu_excited_forces_batch.py::test_batch_roots_pair_routes"],
@@ -55,6 +58,8 @@ def test_variant_passes_parity_subset(env):
         subset = ["tests/test_gpu_bench_config.py::test_k5_every_row_group_body",
                   "tests/test_gpu_bench_config.py::test_k5_row_groups_wide_matrix", "tests/test_gpu_sym8.py::test_sym8_batched"]
     subset = subset + [t for k, tests in ROOTS.items() if k in env for t in tests]
+    if "EVC_SUBSPACE_FEW" in env or "EVC_EIGH_F32" in env:
+        subset = subset + SUBSPACE_BATCH
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + subset,
                        cwd=REPO, env=e, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
