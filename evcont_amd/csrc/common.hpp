@@ -39,6 +39,12 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
         }                                                                           \
     } while (0)
 
+// a launcher's error returns from the calling function
+#define EVC_TRY(call)                     \
+    do {                                  \
+        if (int rc_ = (call)) return rc_; \
+    } while (0)
+
 #define EVC_LAUNCH_CHECK(name)                                                      \
     do {                                                                            \
         hipError_t e_ = hipGetLastError();                                          \

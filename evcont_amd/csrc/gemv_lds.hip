@@ -856,7 +856,7 @@ static int cols_lds_launch(const GemvColsLaunch &L, int nblk1, int nblk0, size_t
 // (the weights, rows x 32, and the rings fit the LDS); eight waves per workgroup (two per SIMD: with one wave per SIMD
 // and rings of 24 the loop was bound by its own scalar instructions, 54 us against 43 at H30; removed).
 // (Both LDS-staged K8 kernels need A 16-byte aligned with an even pitch: every caller has checked that -- check_set of
-// pipeline.hip for the calls on a training set, the roots calls among them, and evc_gemv_cols.)
+// workspace.hip for the calls on a training set, the roots calls among them, and evc_gemv_cols.)
 int launch_cols_lds(GemvColsLaunch L, const GemvPass &ps, hipStream_t st) {
     const int d1 = ps.t[2], nw = 8;
     const int nblk1 = L.p[1].cols > 0 ? kLdsBlocksSmall : 0;

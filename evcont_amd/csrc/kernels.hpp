@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "route.hpp"
 
 namespace evc {
 
@@ -125,7 +126,7 @@ std::vector<GemvPass> plan_gemv_cols(const GemvShape &p0, const GemvShape &p1, i
 int rows_max_spans(const GemvShape &P, bool small);
 size_t rows_ws_doubles(int64_t rows, int64_t cols);
 // `count` geometries in the passes of the plan.  PRECONDITION of launch_gemv_rows: span_cols / nspans of p0, p1 are those
-// of plan_gemv_rows for the same shapes and `count` on this device (RowsPlan::apply: pipeline.hip replan, evc_gemv_rows)
+// of plan_gemv_rows for the same shapes and `count` on this device (RowsPlan::apply: workspace.hip setup, evc_gemv_rows)
 // -- the kernels write, and the consumer sums, the spans the caller names; a problem with nblocks == 0 is left out.
 int launch_gemv_rows(RowProblem p0, RowProblem p1, int count, hipStream_t st);
 int launch_gemv_cols(ColProblem p0, ColProblem p1, int count, hipStream_t st);
@@ -162,9 +163,7 @@ struct PairTransformArgs {
     int in_ld, out_ld;  // row pitch (doubles) of the dense (pair, pair) operand / result; 0: n(n+1)/2 (the caller's s4 `int2e`);
                         // the pipeline's own intermediates use pair_ld(n): rows start on 128-byte lines
 };
-// Row pitch of the pipeline's dense (pair, pair) intermediates: n(n+1)/2 rounded up to 16 doubles.
-__host__ __device__ inline int pair_ld(int n) { return (n * (n + 1) / 2 + 15) & ~15; }
-constexpr int kPairTransformMaxN = 32;
+// (pair_ld(n), the row pitch of the pipeline's dense (pair, pair) intermediates, and kPairTransformMaxN: route.hpp)
 // one packed operand row of the pair kernels in LDS (transform.hip pt_kernel, y2.hip y2_fused_kernel)
 constexpr int kPtRawMax = (kPairTransformMaxN * (kPairTransformMaxN + 1) / 2 + 1 + 127) / 128;   // double2 per lane: 5
 constexpr int kPtRowLen = kPtRawMax * 128 + 4;   // + two zero slots (padding fragments), 16-byte multiple
@@ -215,7 +214,6 @@ int launch_y2_sb(const double *SB, const double *K3, int n, double *partial, int
 int launch_y2_fused(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial,
                     int64_t sws, int count, hipStream_t st);
 int y2_fused_slabs(int n, int count);
-bool y2_fused_available(int n);
 // partial[b][i][a] = sum_{k in slab b} GsT[k][i] * K3[k][a]   (k = jkl)
 int y2_slabs(int n);
 int y2_slab_capacity(int n);   // slabs the pipeline's partial buffer holds (>= y2_slabs)
@@ -274,7 +272,7 @@ struct LoewdinArgs {
     double *flag;      // + g*sws: one word per geometry (32 < n <= 64, part != 0): 1 = the Newton-Schulz launch wrote X, h1
     int part;          // 0: X, h1, U, s.  loewdin_split_available(n) only: 1 = X and h1 alone (Newton-Schulz on the matrix
                        // cores, no eigensolver; U and s are not touched), 2 = U and s alone (X, h1 are not touched) -- the
-                       // two halves of a step whose gradient tail alone needs the eigendecomposition (pipeline.hip);
+                       // two halves of a step whose gradient tail alone needs the eigendecomposition (side_stream.hip);
                        // 3 (internal, 32 < n <= 64): X and h1 by the eigensolver for the geometries whose flag is 0
 };
 int launch_loewdin(const LoewdinArgs &a, int count, hipStream_t st);

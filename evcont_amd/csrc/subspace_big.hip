@@ -820,7 +820,7 @@ __global__ __launch_bounds__(kBT) void loewdin_big_kernel(LoewdinArgs a) {
     double *A = ext ? a.scratch + g * a.sscratch : G + gsz, *B = A + Tp2;
     double *f = ext ? G + gsz : B + Tp2, *red = f + Tp;
     const int tid = threadIdx.x;
-    // part 2: U and s only (the response half of a split step, pipeline.hip); part 3: X and h1 only, and only where the
+    // part 2: U and s only (the response half of a split step, side_stream.hip); part 3: X and h1 only, and only where the
     // Newton-Schulz launch in front of this one declined (its flag word)
     const bool want_u = a.part != 1 && a.part != 3, want_x = a.part != 2;
     if (a.part == 3 && a.flag[g * a.sws] != 0.0) return;

@@ -378,7 +378,7 @@ __global__ __launch_bounds__(kThreads) void subspace_kernel(SolveArgs a) { subsp
 // kernel alone reads) in ONE launch: `count` workgroups each, both one workgroup per geometry and latency-bound, neither
 // depending on the other -- the eigensolver (~75 us) then runs beside the subspace solve (~54 us) instead of in front of
 // the whole energy phase, with no second stream (batches of 12 and more geometries; smaller calls send it to the side
-// stream, pipeline.hip).
+// stream, side_stream.hip).
 __global__ __launch_bounds__(kThreads) void subspace_loewdin_kernel(SolveArgs sa, LoewdinArgs la, int count) {
     if ((int)blockIdx.x < count) subspace_body(sa, blockIdx.x);
     else loewdin_body(la, (int64_t)blockIdx.x - count);

@@ -315,7 +315,6 @@ static int y2_fused_tiles(int n, int count) {
     while ((ntiles + t - 1) / t > y2_slab_capacity(n)) ++t;
     return t;
 }
-bool y2_fused_available(int n) { return n >= 1 && (n <= kPairTransformMaxN || y2_64_applicable(n)); }
 int y2_fused_slabs(int n, int count) {
     if (y2_64_applicable(n)) return y2_64_slabs(n, count);
     const int ppt = y2_fused_ppt(count);

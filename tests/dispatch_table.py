@@ -31,7 +31,7 @@ a batch that is split in groups name the last group's kernel.
 
 STAGES = ("k5_rows", "k8_cols", "pair_transform", "ip1", "y2", "unpack", "loewdin", "subspace")
 
-# records every split / side-stream form of the Loewdin step leaves (csrc/pipeline.hip phase_hamiltonian)
+# records every split / side-stream form of the Loewdin step leaves (csrc/pipeline.hip phase_hamiltonian, csrc/side_stream.hip)
 L_RIDE = "loewdin_kernel part=1"                                        # n <= 32, T <= 32: rides in the solve launch
 L_SIDE32 = "loewdin_kernel part=1; side stream: loewdin_kernel part=2"  # n <= 32, T > 32, < 12 geometries
 L_ONE32 = "loewdin_kernel part=0"

@@ -1,4 +1,4 @@
-"""The Loewdin step in two halves (csrc/pipeline.hip "the Loewdin step in two halves", csrc/loewdin.hpp loewdin_ns):
+"""The Loewdin step in two halves (csrc/side_stream.hip "the Loewdin step in two halves", csrc/loewdin.hpp loewdin_ns):
 full calls compute X = S^-1/2 by a Newton-Schulz iteration on the matrix cores and run the eigendecomposition of S
 (needed by the response term only, ab_initio_gradients_loewdin.py:41-134) off the critical path -- in the launch of
 the subspace solve (N <= 32, T <= 32) or, for a few geometries of 33 ... 64 orbitals, on a side stream.

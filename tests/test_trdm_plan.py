@@ -34,7 +34,7 @@ def golden():
 
 
 def trdm_set(n, T, layout, rows2=None):
-    """The integer fields of a set as check_set (csrc/pipeline.hip) wants them and the evaluator pads them: ld2 = cols2
+    """The integer fields of a set as check_set (csrc/workspace.hip) wants them and the evaluator pads them: ld2 = cols2
     rounded up to 16, ld1 = n^2 rounded up to even.  The pointers only have to pass the NULL / alignment checks of the
     workspace functions; nothing reads them."""
     from evcont_amd._lib import TrdmSet
