@@ -3,7 +3,9 @@ backend "gloo" (the only way to have more than one rank on a one-GPU box; the co
 rank holds its row slice of the compressed training set and drives the real HIP phases through
 ``distributed.PipelinedPairSharded`` (three pair-sharded batches in flight on internal streams, the collectives of all of
 them issued in program order on one communicator) and through ``PairShardedContinuation(return_density_matrices=True)``,
-against the CPU oracle.  Rank 0 prints one JSON line."""
+against the CPU oracle.  Rank 0 prints one JSON line.  Optional arguments ``n T G`` (default 13 7 14) choose another shape:
+tests/test_gpu_rccl.py::test_pipelined_pair_sharded_rank_without_rows runs T = 1, one pair row, so that rank 1 owns
+no row at all."""
 import json
 import os
 import sys
@@ -27,9 +29,12 @@ def main():
     dist.init_process_group("gloo")
     world, rank = dist.get_world_size(), dist.get_rank()
     n, T, A, G = 13, 7, 3, 14
+    if len(sys.argv) > 1:
+        n, T, G = (int(x) for x in sys.argv[1:4])
+    sizes = (9, 2, 2) if n == 13 else None          # (None: AO blocks as equal as possible)
     S, one, two = make_trdms(n, T, 4601)
     two_p = pack_rows(two, True, True)
-    batches = [[make_ao_arrays(n, A, 4700 + 50 * b + k, ao_sizes=(9, 2, 2), ip1_rs_symmetric=True) for k in range(G)]
+    batches = [[make_ao_arrays(n, A, 4700 + 50 * b + k, ao_sizes=sizes, ip1_rs_symmetric=True) for k in range(G)]
                for b in range(4)]
     bundle = lambda ao: orc.AOBundle(ao.S, ao.hcore, ao.eri, ao.ipovlp, ao.dhcore, ao.eri_ip1, ao.aoslices, ao.enuc,
                                      ao.gnuc)

@@ -87,8 +87,8 @@ def test_pass_sequences_equal_the_recorded_ones(lib, golden):
     """H30 / T = 20 and n = 6 / T = 3 (sym8) around every group boundary, on a whole device (256 CUs) and on one the
     LDS-staged kernels do not fit (128); the Zundel shape with T = 100, whose one-body problem takes an LDS-staged launch
     of its own (the shape of tests/test_gpu_large_T.py::test_zundel_shape_T100_against_oracle[32], which runs it on the
-    GPU); and a 3500-row shard of T = 118, whose one-body problem falls back to the fragment-shaped kernel (on the GPU
-    that kernel's arithmetic is covered by the large-T tests; this branch needs a sharded set)."""
+    GPU); and a 3500-row shard of T = 118, whose one-body problem falls back to the fragment-shaped kernel (run on the
+    GPU, on both halves of a T = 118 set, by tests/test_gpu_shard_routes.py::test_sharded_phases[C_fragment_*])."""
     assert {p["count"] for p in golden["plans"]} == {1, 2, 3, 4, 8, 9, 11, 12, 16, 17, 32, 33, 44, 64, 65, 76, 96}
     assert {(p["n"], p["T"], p["cus"]) for p in golden["plans"]} >= {(30, 20, 256), (30, 20, 128), (6, 3, 256), (6, 3, 128)}
     for p in golden["plans"]:
