@@ -68,23 +68,26 @@ class FCI_EVCont_obj(TRDMContainer):
         for ind in range(len(e_all)):
             if ind not in self.roots_train:
                 continue
-            fcivec = fcivec_all[ind]
-            self.fcivecs.append(fcivec)
-            self.ens.append(e_all[ind] + energy_nuc(mol))
-            self.mol_index.append(mindex)
-            T1 = len(self.fcivecs)
-            if hasattr(self.cisolver, "trans_rdm12_rows"):
-                # one bra against all stored states in one pass (fci_device.DeviceFCI)
-                ovlp, one, two = self.cisolver.trans_rdm12_rows(self.fcivecs[-1], self.fcivecs, n, mol.nelec)
-                self._append_state(ovlp, one, two)
-                continue
-            ovlp = np.empty(T1)
-            one = np.empty((T1, n, n))
-            two = np.empty((T1, n, n, n, n))
-            for i in range(T1):
-                ovlp[i] = np.dot(np.ravel(self.fcivecs[-1]).conj(), np.ravel(self.fcivecs[i]))
-                one[i], two[i] = self.cisolver.trans_rdm12(self.fcivecs[-1], self.fcivecs[i], n, mol.nelec)
+            self._append_root(fcivec_all[ind], e_all[ind] + energy_nuc(mol), mindex, n, mol.nelec)
+
+    def _append_root(self, fcivec, energy, mindex, n, nelec):
+        """One trained root: store the vector, get its t-RDM rows against every stored state, grow the arrays."""
+        self.fcivecs.append(fcivec)
+        self.ens.append(energy)
+        self.mol_index.append(mindex)
+        T1 = len(self.fcivecs)
+        if hasattr(self.cisolver, "trans_rdm12_rows"):
+            # one bra against all stored states in one pass (fci_device.DeviceFCI)
+            ovlp, one, two = self.cisolver.trans_rdm12_rows(self.fcivecs[-1], self.fcivecs, n, nelec)
             self._append_state(ovlp, one, two)
+            return
+        ovlp = np.empty(T1)
+        one = np.empty((T1, n, n))
+        two = np.empty((T1, n, n, n, n))
+        for i in range(T1):
+            ovlp[i] = np.dot(np.ravel(self.fcivecs[-1]).conj(), np.ravel(self.fcivecs[i]))
+            one[i], two[i] = self.cisolver.trans_rdm12(self.fcivecs[-1], self.fcivecs[i], n, nelec)
+        self._append_state(ovlp, one, two)
 
     def prune_datapoints(self, keep_ids):
         """Keep the listed training states (``FCI_EVCont.py:133-151``)."""

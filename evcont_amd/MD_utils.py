@@ -213,15 +213,17 @@ def get_state_scanner(mol, one_rdm, two_rdm, overlap, root, hermitian=True):
 
 
 def get_trajectory(init_mol, overlap, one_rdm, two_rdm, dt=10.0, steps=10, init_veloc=None, hermitian=True,
-                   trajectory_output=None, energy_output=None, compress="default"):
+                   trajectory_output=None, energy_output=None, compress="default", device_trdms=None):
     """NVE trajectory from the continuation (reference :60-125).  Single process: the reference's
     rank-0-computes / Bcast split exists only to coexist with MPI-parallel training code.
 
     PySCF molecules are propagated by ``pyscf.md.NVE`` exactly as in the reference; array-level molecules
     that can be rebuilt at new coordinates (``with_coords``, e.g. ``evcont_amd.hchain.HChainMol``) by the
     velocity-Verlet integrator below, with the same conventions (Bohr, atomic time units, frame 0 = the
-    initial geometry, ``steps`` frames)."""
-    scanner_fun = get_scanner(init_mol, one_rdm, two_rdm, overlap, hermitian=hermitian, compress=compress)
+    initial geometry, ``steps`` frames).  ``device_trdms``: as for ``get_scanner`` (training data already on the
+    device, e.g. ``resident.ResidentFCI_EVCont_obj.device_trdms()``; ``two_rdm`` may then be ``None``)."""
+    scanner_fun = get_scanner(init_mol, one_rdm, two_rdm, overlap, hermitian=hermitian, compress=compress,
+                              device_trdms=device_trdms)
     if hasattr(init_mol, "with_coords"):
         frames = nve_velocity_verlet(scanner_fun, init_mol, dt=dt, steps=steps, veloc=init_veloc,
                                      trajectory_output=trajectory_output, energy_output=energy_output)

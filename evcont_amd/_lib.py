@@ -128,6 +128,10 @@ SIGNATURES = {
     "evc_fci_trdm_rows": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_size_t, C.c_void_p]),
+    "evc_fci_rows_packed_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "evc_fci_trdm_rows_packed": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_fci_sigma": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_fci_solve_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int]),
@@ -162,6 +166,8 @@ FCI_PROF_STAGES = {"fci_excite": 8, "fci_trdm": 9, "fci_sigma": 10}
 FCI_PROF_SOLVE = 11
 # evc_fci_rotate (EVC_PROF_FCI_ROTATE)
 FCI_PROF_ROTATE = 12
+# evc_fci_trdm_rows_packed (EVC_PROF_FCI_PACK): the packing kernel of the last call, with its rows, columns and pitch
+FCI_PROF_PACK = 13
 FCI_DET_MAJOR, FCI_DET_MAJOR_T, FCI_ORB_MAJOR = 0, 1, 2
 
 _lib: Optional[C.CDLL] = None

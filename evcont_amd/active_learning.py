@@ -184,6 +184,11 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
     (``trn_times`` given) is not supported.  Returns the last trajectory ``(steps, A, 3)``.
     """
     from .MD_utils import get_trajectory
+    from .ab_initio_eigenvector_continuation import get_trdm_compression, integrals_have_symmetry
+    from .resident import ResidentFCI_EVCont_obj
+    # a resident container has its two-body rows on the device alone: trajectories and the subset energies read its
+    # view, the checkpoint gets the packed rows ((P, M) as two_rdm.npy for pack2, (P, cols8) as two_rdm_sym8.npy)
+    resident = isinstance(EVCont_obj, ResidentFCI_EVCont_obj)
     if trn_times:
         raise NotImplementedError("converge_EVCont_MD: restart from a previous run (trn_times) is not supported")
     if not hasattr(init_mol, "with_coords"):
@@ -199,13 +204,28 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
         suffix = f"_{i}" if prune_irrelevant_data else ""
         np.save(path(f"overlap{suffix}.npy"), EVCont_obj.overlap)
         np.save(path(f"one_rdm{suffix}.npy"), EVCont_obj.one_rdm)
-        np.save(path(f"two_rdm{suffix}.npy"), EVCont_obj.two_rdm)
+        if not resident:
+            np.save(path(f"two_rdm{suffix}.npy"), EVCont_obj.two_rdm)
+        else:
+            # only one of the two files may be there (load_checkpoint prefers two_rdm.npy): a checkpoint of the other
+            # form left in workdir by an earlier run is the user's to move, not this loop's to delete
+            name, other = ("two_rdm_sym8", "two_rdm") if EVCont_obj.layout == "sym8" else ("two_rdm", "two_rdm_sym8")
+            if os.path.exists(path(f"{other}{suffix}.npy")):
+                raise _lib.EvcontHipError(f"converge_EVCont_MD: {path(other + suffix + '.npy')} exists; next to it "
+                                          f"{name}{suffix}.npy would be ambiguous for trdm_io.load_checkpoint (use an "
+                                          "empty workdir or move the old checkpoint)")
+            np.save(path(f"{name}{suffix}.npy"), EVCont_obj.rows_host())
         if i > 0:
             np.savetxt(path(f"trn_times{suffix}.txt"), np.array(trn_times))
 
     def run_trajectory(i):
-        traj = get_trajectory(init_mol, EVCont_obj.overlap, EVCont_obj.one_rdm, EVCont_obj.two_rdm, steps=steps, dt=dt,
-                              trajectory_output=path(f"traj_EVCont_{i}.xyz"), energy_output=path(f"ens_EVCont_{i}.xyz"))
+        if resident and EVCont_obj.layout == "sym8" and not integrals_have_symmetry(init_mol):
+            raise _lib.EvcontHipError("converge_EVCont_MD: a sym8 resident container needs integrals with the index "
+                                      "symmetries of real two-electron integrals (use layout='pack2')")
+        traj = get_trajectory(init_mol, EVCont_obj.overlap, EVCont_obj.one_rdm, None if resident else EVCont_obj.two_rdm,
+                              steps=steps, dt=dt, trajectory_output=path(f"traj_EVCont_{i}.xyz"),
+                              energy_output=path(f"ens_EVCont_{i}.xyz"),
+                              device_trdms=EVCont_obj.device_trdms() if resident else None)
         np.save(path(f"traj_EVCont_{i}.npy"), traj)
         ens = np.atleast_2d(np.genfromtxt(path(f"ens_EVCont_{i}.xyz")))[:, 1]
         return traj, np.ascontiguousarray(ens)
@@ -240,9 +260,10 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
         # energies of the new trajectory with subsets of the training set: ONE t-RDM contraction per geometry
         T = EVCont_obj.ntrain
         traj_mols = [init_mol.with_coords(g, need_grad=False) for g in trajectory]
-        from .ab_initio_eigenvector_continuation import get_trdm_compression, integrals_have_symmetry
         mode = get_trdm_compression()
         lay = "sym8" if mode == "sym8" or (mode == "auto" and integrals_have_symmetry(traj_mols[0])) else "pack2"
+        if resident:
+            lay = None          # the container's own layout (its sym8 form was checked against the integrals above)
         H, _, enuc = trajectory_hamiltonians(EVCont_obj.device_trdms(lay, device=dev), _device_aos(traj_mols, dev))
         S_dev = torch.from_numpy(np.ascontiguousarray(EVCont_obj.overlap, dtype=np.float64)).to(dev)
         reference_ens = subset_energies(H, S_dev, enuc, [list(range(T - 1))])[:, 0].cpu().numpy()

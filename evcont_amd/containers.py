@@ -10,6 +10,8 @@ On top of that the containers keep a device-resident copy in step (``device_trdm
 streams the two-body t-RDM from HBM twice per geometry, so it is uploaded once per change of the
 training set — in the electron-pair-packed ``(P, M)`` layout by default, a quarter of the bytes of the
 six-index array (``ab_initio_eigenvector_continuation.py:59-68``) — and reused by every evaluation.
+(``resident.ResidentFCI_EVCont_obj`` turns this round: its two-body rows are written on the device and the host keeps
+``overlap`` and ``one_rdm`` only.)
 """
 from __future__ import annotations
 

@@ -3,6 +3,9 @@
 //   t-RDM       M = D~_bra . D_ket^T  (N^2 x dim x N^2)       split-K FP64 MFMA, partial tiles summed in a fixed order
 //   sigma       G = h2 . D            (N^2 x N^2 x dim)       FP64 MFMA over determinant tiles, then the signed gather of
 //               sigma = sum_pq E_pq (G[pq]/2 + h'_pq c)       G back through the tables
+//   rows        evc_fci_trdm_rows: the dense t-RDMs of one bra against K kets; evc_fci_trdm_rows_packed: the same product
+//               (one function, fci_trdm_rows_run) with each ket's two-body block packed on the device into a row of the
+//               evaluator's matrix (fci_pack.hip)
 // D is materialised in HBM in chunks (the caller's workspace), so that the MFMA kernels issue nothing but operand
 // loads and MFMAs and the gather work runs in launches of its own (FP64 MFMA blocks its SIMD's vector issue).
 //
@@ -407,20 +410,15 @@ extern "C" int evc_fci_excite(int norb, int64_t na, int64_t nb, const int32_t *t
     return launch_excite(layout, norb, nb, s.dim, tab_a, tab_b, c, k0, nk, D, ld, as_stream(stream));
 }
 
-extern "C" int evc_fci_trdm_rows(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
-                                 const double *bra, const double *const *kets, int nkets, double *ovlp, double *dm1,
-                                 double *dm2, void *ws, size_t ws_bytes, void *stream) {
-    FciShape s;
-    if (int rc = fci_shape("evc_fci_trdm_rows", norb, na, nb, s)) return rc;
-    EVC_REQUIRE(tab_a && tab_b && bra && kets && ovlp && dm1 && dm2 && ws, "evc_fci_trdm_rows: null pointer");
-    EVC_REQUIRE(nkets >= 1 && nkets <= 4096, "evc_fci_trdm_rows: nkets=%d (1 ... 4096)", nkets);
-    for (int i = 0; i < nkets; ++i) EVC_REQUIRE(kets[i], "evc_fci_trdm_rows: kets[%d] is null", i);
-    EVC_REQUIRE(aligned16(ws), "evc_fci_trdm_rows: workspace not 16-byte aligned");
-    const size_t need = s.trdm_fixed + 2 * s.trdm_block;
-    EVC_REQUIRE(ws_bytes >= need, "evc_fci_trdm_rows: workspace of %zu bytes, at least %zu needed for %lld determinants",
-                ws_bytes, need, (long long)s.dim);
-    hipStream_t st = as_stream(stream);
-    clear_fci_kernels(EVC_PROF_FCI_TRDM);
+// The row call behind evc_fci_trdm_rows and evc_fci_trdm_rows_packed: the bra against every ket, the determinant blocks in
+// order, then the two reductions per ket.  `dm2` (nkets, norb^4): the dense two-body results; NULL: fci_trdm_reduce2_kernel
+// writes each ket's dense block into `slot` (norb^4 doubles) and fci_row_pack_kernel (fci_pack.hip) packs it into row i of
+// `rows` (pitch ld) in `layout`.  ws / ws_bytes: the t-RDM workspace alone (at least trdm_fixed + 2 trdm_block).
+static int fci_trdm_rows_run(const FciShape &s, const int32_t *tab_a, const int32_t *tab_b, const double *bra,
+                             const double *const *kets, int nkets, double *ovlp, double *dm1, double *dm2, double *slot,
+                             int layout, double *rows, int64_t ld, void *ws, size_t ws_bytes, hipStream_t st) {
+    const int norb = s.norb;
+    const int64_t nb = s.nb;
     const int64_t nfit = (int64_t)((ws_bytes - s.trdm_fixed) / s.trdm_block);
     const bool resident = nfit >= s.nblk + 1;   // D~_bra whole: formed once for all the kets
     const int64_t cb = resident ? (nfit - s.nblk < s.nblk ? nfit - s.nblk : s.nblk) : nfit / 2;
@@ -455,11 +453,67 @@ extern "C" int evc_fci_trdm_rows(int norb, int64_t na, int64_t nb, const int32_t
             Pg, Po, norb, s.npad, s.nblk, g1, dm1 + (int64_t)i * n2, ovlp + i);
         EVC_LAUNCH_CHECK("fci_trdm_reduce1_kernel");
         fci_trdm_reduce2_kernel<<<(unsigned)ceil_div((int64_t)n2 * n2, 256), 256, 0, st>>>(
-            Pm, g1, norb, s.npad, s.nblk, dm2 + (int64_t)i * n2 * n2);
+            Pm, g1, norb, s.npad, s.nblk, dm2 ? dm2 + (int64_t)i * n2 * n2 : slot);
         EVC_LAUNCH_CHECK("fci_trdm_reduce2_kernel");
+        if (!dm2)
+            if (int rc = launch_fci_row_pack(layout, norb, slot, rows + (int64_t)i * ld, ld, st)) return rc;
     }
     note_kernel(EVC_PROF_FCI_TRDM, "fci_trdm_kernel<%d,%d> quadrants=%d blocks=%lld bra_resident=%d ket_blocks=%lld", trt,
                 tnbw, nq * nq, (long long)s.nblk, resident ? 1 : 0, (long long)cb);
+    return 0;
+}
+
+extern "C" int evc_fci_trdm_rows(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
+                                 const double *bra, const double *const *kets, int nkets, double *ovlp, double *dm1,
+                                 double *dm2, void *ws, size_t ws_bytes, void *stream) {
+    FciShape s;
+    if (int rc = fci_shape("evc_fci_trdm_rows", norb, na, nb, s)) return rc;
+    EVC_REQUIRE(tab_a && tab_b && bra && kets && ovlp && dm1 && dm2 && ws, "evc_fci_trdm_rows: null pointer");
+    EVC_REQUIRE(nkets >= 1 && nkets <= 4096, "evc_fci_trdm_rows: nkets=%d (1 ... 4096)", nkets);
+    for (int i = 0; i < nkets; ++i) EVC_REQUIRE(kets[i], "evc_fci_trdm_rows: kets[%d] is null", i);
+    EVC_REQUIRE(aligned16(ws), "evc_fci_trdm_rows: workspace not 16-byte aligned");
+    const size_t need = s.trdm_fixed + 2 * s.trdm_block;
+    EVC_REQUIRE(ws_bytes >= need, "evc_fci_trdm_rows: workspace of %zu bytes, at least %zu needed for %lld determinants",
+                ws_bytes, need, (long long)s.dim);
+    clear_fci_kernels(EVC_PROF_FCI_TRDM);
+    return fci_trdm_rows_run(s, tab_a, tab_b, bra, kets, nkets, ovlp, dm1, dm2, nullptr, 0, nullptr, 0, ws, ws_bytes,
+                             as_stream(stream));
+}
+
+// the scratch slot of the packed row call: one dense dm2 block, in front of the t-RDM workspace
+static size_t fci_pack_slot_bytes(int norb) { return align_up((size_t)norb * norb * norb * norb * 8, 256); }
+
+extern "C" size_t evc_fci_rows_packed_workspace_bytes(int norb, int64_t na, int64_t nb, int minimal) {
+    const size_t base = evc_fci_workspace_bytes(norb, na, nb, minimal);
+    return base ? base + fci_pack_slot_bytes(norb) : 0;
+}
+
+extern "C" int evc_fci_trdm_rows_packed(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
+                                        const double *bra, const double *const *kets, int nkets, double *ovlp,
+                                        double *dm1, int layout, double *rows, int64_t ld, void *ws, size_t ws_bytes,
+                                        void *stream) {
+    FciShape s;
+    if (int rc = fci_shape("evc_fci_trdm_rows_packed", norb, na, nb, s)) return rc;
+    EVC_REQUIRE(tab_a && tab_b && bra && kets && ovlp && dm1 && rows && ws, "evc_fci_trdm_rows_packed: null pointer");
+    EVC_REQUIRE(nkets >= 1 && nkets <= 4096, "evc_fci_trdm_rows_packed: nkets=%d (1 ... 4096)", nkets);
+    for (int i = 0; i < nkets; ++i) EVC_REQUIRE(kets[i], "evc_fci_trdm_rows_packed: kets[%d] is null", i);
+    EVC_REQUIRE(layout == EVC_LAYOUT_PACK2 || layout == EVC_LAYOUT_SYM8,
+                "evc_fci_trdm_rows_packed: layout=%d (EVC_LAYOUT_PACK2 or EVC_LAYOUT_SYM8)", layout);
+    const int64_t cols = fci_row_pack_cols(layout, norb);
+    EVC_REQUIRE(ld >= (cols + 15) / 16 * 16 && ld % 16 == 0 && ld < ((int64_t)1 << 31),
+                "evc_fci_trdm_rows_packed: ld=%lld (a multiple of 16, at least %lld columns rounded up to 16, below 2^31)",
+                (long long)ld, (long long)cols);
+    EVC_REQUIRE(aligned16(ws) && aligned16(rows), "evc_fci_trdm_rows_packed: workspace or rows not 16-byte aligned");
+    const size_t slot = fci_pack_slot_bytes(norb), need = slot + s.trdm_fixed + 2 * s.trdm_block;
+    EVC_REQUIRE(ws_bytes >= need,
+                "evc_fci_trdm_rows_packed: workspace of %zu bytes, at least %zu needed for %lld determinants", ws_bytes,
+                need, (long long)s.dim);
+    clear_fci_kernels(EVC_PROF_FCI_TRDM);
+    clear_fci_kernels(EVC_PROF_FCI_PACK);
+    if (int rc = fci_trdm_rows_run(s, tab_a, tab_b, bra, kets, nkets, ovlp, dm1, nullptr, static_cast<double *>(ws), layout,
+                                   rows, ld, static_cast<char *>(ws) + slot, ws_bytes - slot, as_stream(stream)))
+        return rc;
+    note_fci_row_pack(layout, norb, nkets, ld);
     return 0;
 }
 

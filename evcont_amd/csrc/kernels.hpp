@@ -15,7 +15,7 @@ namespace evc {
 constexpr int kMaxOrbitals = 96;   // N of the fused pipeline (quarter transforms: 16-wide tiles up to 96 padded columns)
 constexpr int kMaxBatchG = 32;  // geometries contracted per pass of the streaming kernels (matrix-core variants)
 
-// ---- fci.hip, fci_solve.hip ----------------------------------------------------------
+// ---- fci.hip, fci_solve.hip, fci_pack.hip ----------------------------------------------------------
 constexpr int kFciMaxOrb = 16;
 constexpr int kFciMinRows = 256;     // determinants per split-K block, at least
 constexpr int kFciMaxBlocks = 256;   // split-K blocks (= partial tiles per ket), at most
@@ -26,6 +26,12 @@ inline int64_t fci_rows_per_block(int64_t dim) {
     const int64_t r = (int64_t)align_up((size_t)ceil_div(dim, kFciMaxBlocks), 64);
     return r < kFciMinRows ? kFciMinRows : r;
 }
+
+// fci_pack.hip: the dense dm2 (norb^4) of one ket -> one row of the evaluator's (pairs, ld) matrix in EVC_LAYOUT_PACK2 or
+// EVC_LAYOUT_SYM8 (fci_row_pack_cols columns, the rest of the row up to ld zero); note_fci_row_pack: the stage record
+int64_t fci_row_pack_cols(int layout, int norb);
+int launch_fci_row_pack(int layout, int norb, const double *dm2, double *row, int64_t ld, hipStream_t st);
+void note_fci_row_pack(int layout, int norb, int nrows, int64_t ld);
 
 // ---- K5 / K8, the streaming t-RDM contractions: kernels in gemv_stream.hip (VALU), gemv_mfma.hip (matrix cores,
 //      fragment-shaped loads), gemv_lds.hip (matrix cores, LDS-staged); gemv_dispatch.hip plans the passes of a call

@@ -14,7 +14,7 @@
 namespace evc {
 
 // ---- profile.hip ---------------------------------------------------------------------------------------------------
-constexpr int kProfStages = 13;   // EVC_PROF_* of include/evcont_hip.h
+constexpr int kProfStages = 14;  // EVC_PROF_* of include/evcont_hip.h
 // Entry points clear the records of the stages they can launch, so that a stage the call did not run reports "".
 constexpr unsigned kStagesAll = (1u << kProfStages) - 1u;
 constexpr unsigned kStagesHamiltonian =

@@ -364,6 +364,40 @@ class DeviceTRDMs:
                                s_train=self.S.data_ptr())
         return self
 
+    @classmethod
+    def from_padded_rows(cls, one_RDM, two_padded: torch.Tensor, S, layout: int) -> "DeviceTRDMs":
+        """Adopt, WITHOUT copying, an already padded two-body matrix of a pair layout (pack2, pair5 or sym8):
+        ``two_padded`` is a ``(rows, ld)`` device view of unit column stride whose first ``cols`` columns hold the
+        layout's rows and the others zeros (``ld`` a multiple of 16), e.g. the leading rows of a larger matrix
+        (``resident.ResidentTRDMs``).  ``one_RDM (T,T,N,N)`` and ``S (T,T)``: numpy or tensors, copied."""
+        self = cls.__new__(cls)
+        self.device = two_padded.device
+        T, n = int(S.shape[0]), int(one_RDM.shape[-1])
+        self.T, self.n, self.layout = T, n, int(layout)
+        rows, cols = layout_shape(self.layout, T, n)
+        # the matrix is adopted as it is and reaches the library as a pointer with this pitch: refuse, not assert
+        ok = (self.layout in (5, 2, _lib.LAYOUT_SYM8) and two_padded.dtype == F64 and two_padded.dim() == 2
+              and two_padded.device.type == "cuda" and tuple(one_RDM.shape) == (T, T, n, n))
+        ld = int(two_padded.shape[1]) if ok else 0
+        ok = (ok and two_padded.shape[0] == rows and two_padded.stride(1) == 1 and (rows == 1 or two_padded.stride(0) == ld)
+              and ld % 16 == 0 and ld >= cols and two_padded.data_ptr() % 16 == 0)
+        if not ok:
+            raise _lib.EvcontHipError(
+                f"DeviceTRDMs.from_padded_rows: need a float64 device matrix of {rows} rows whose pitch is its width, a "
+                f"multiple of 16 and at least {cols} (layout {self.layout}, T={T}, N={n}), with unit column stride and "
+                f"16-byte aligned; got shape {tuple(two_padded.shape)}, strides {tuple(two_padded.stride())}, "
+                f"{two_padded.dtype} on {two_padded.device}")
+        self.two = two_padded
+        self.rows_total, self.cols, self.ld = rows, cols, ld
+        self.row_offset, self.rows_local = 0, rows
+        as_t = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)))
+        self.one = _pad_even(as_t(one_RDM).to(self.device, F64).reshape(T * T, n * n))
+        self.S = as_t(S).to(self.device, F64).contiguous()
+        self.cstruct = TrdmSet(n=n, ntrain=T, layout=self.layout, reserved=0, rows2=rows, row_offset=0, rows2_total=rows,
+                               cols2=cols, ld2=ld, ld1=self.one.shape[1], two_rdm=self.two.data_ptr(),
+                               one_rdm=self.one.data_ptr(), s_train=self.S.data_ptr())
+        return self
+
     @property
     def nbytes_streamed_per_pass(self) -> int:
         """Algorithmic bytes one pass over the local two-body rows reads."""

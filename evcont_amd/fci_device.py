@@ -5,7 +5,9 @@ GPU (``csrc/fci.hip``): the sigma vector ``H c`` and the transition RDMs.  Same 
     dm1, dm2 = solver.trans_rdm12(cibra, ciket, norb, nelec)       # dm1[p,q] = <q^+ p>, dm2[p,q,r,s] = <p^+ r^+ s q>
 
 plus ``trans_rdm12_rows(bra, kets, norb, nelec)``: one bra against all kets in one pass, which is what
-``FCI_EVCont_obj.append_to_rdms`` needs for a new training state, and ``transform_ci(ci, nelec, u)``
+``FCI_EVCont_obj.append_to_rdms`` needs for a new training state, ``trans_rdm12_rows_packed(..., layout, out_rows)``: the
+same call with its two-body rows written on the device in the evaluator's layout (``csrc/fci_pack.hip``; the training
+set of ``resident.ResidentFCI_EVCont_obj``), and ``transform_ci(ci, nelec, u)``
 (``csrc/fci_rotate.hip``), which rotates a state solved in another orbital basis into the OAO basis.  Opt in with
 ``FCI_EVCont_obj(cisolver=DeviceFCI(), cibasis="OAO")``, or ``cibasis="canonical"`` to solve in the Hartree-Fock basis,
 where the Davidson solver's diagonal preconditioner works best near equilibrium.
@@ -341,6 +343,50 @@ class DeviceFCI:
                                     ovlp.data_ptr(), dm1.data_ptr(), dm2.data_ptr(), self._ws.data_ptr(), grant,
                                     self._stream()), "evc_fci_trdm_rows")
         return ovlp.cpu().numpy(), dm1.cpu().numpy(), dm2.cpu().numpy()
+
+    def trans_rdm12_rows_packed(self, bra, kets, norb, nelec, layout, out_rows: torch.Tensor):
+        """``trans_rdm12_rows`` with the two-body results left on the device, in the layout the evaluator streams
+        (``evc_fci_trdm_rows_packed``): row ``i`` of ``out_rows``, a ``(K, ld)`` float64 device view into the caller's
+        matrix, receives ``<bra|.|kets[i]>`` in ``layout`` ("pack2" / "sym8", or the ``_lib.LAYOUT_*`` integer), its
+        columns beyond the layout's as zeros.  Returns ``(ovlp (K,), dm1 (K,N,N))`` as numpy.  Vectors are uploaded by
+        the rules of ``trans_rdm12_rows``; device tensors are used as they are.  A view whose rows are wider apart than
+        ``ld`` is filled through a contiguous ``(K, ld)`` device buffer, so that nothing between its rows is written."""
+        nelec = _nelec(nelec)
+        kets = list(kets)
+        if not kets:
+            raise EvcontHipError("DeviceFCI.trans_rdm12_rows_packed: no kets")
+        lay = {"pack2": _lib.LAYOUT_PACK2, "sym8": _lib.LAYOUT_SYM8}.get(layout, layout)
+        if lay not in (_lib.LAYOUT_PACK2, _lib.LAYOUT_SYM8):
+            raise EvcontHipError(f"DeviceFCI.trans_rdm12_rows_packed: layout={layout!r}, expected 'pack2' or 'sym8'")
+        lib, dta, dtb, na, nb, grant = self._setup(norb, nelec)
+        dev = self._dev()
+        K = len(kets)
+        on_dev = torch.is_tensor(out_rows) and out_rows.device.type == dev.type and dev.index in (None, out_rows.device.index)
+        if not (on_dev and out_rows.dtype == F64 and out_rows.dim() == 2 and out_rows.shape[0] == K
+                and out_rows.stride(1) == 1):
+            raise EvcontHipError(f"DeviceFCI.trans_rdm12_rows_packed: out_rows must be a ({K}, ld) float64 view with "
+                                 f"unit column stride on {dev}")
+        ld = int(out_rows.shape[1])
+        direct = K == 1 or int(out_rows.stride(0)) == ld
+        target = out_rows if direct else torch.empty((K, ld), dtype=F64, device=dev)
+        # the scratch slot of the packed call on top of what the dense call is granted
+        slot = (lib.evc_fci_rows_packed_workspace_bytes(norb, na, nb, 0) - lib.evc_fci_workspace_bytes(norb, na, nb, 0))
+        if slot <= 0:
+            check(-1, "evc_fci_rows_packed_workspace_bytes")
+        if self._ws.numel() < grant + slot:
+            self._ws = None
+            self._ws = torch.empty(grant + slot, dtype=torch.uint8, device=dev)
+        dbra = self._upload(bra, na, nb, cache=True)
+        dkets = [self._upload(k, na, nb, cache=True) for k in kets]
+        ovlp = torch.empty(K, dtype=F64, device=dev)
+        dm1 = torch.empty((K, norb, norb), dtype=F64, device=dev)
+        ptrs = (C.c_void_p * K)(*[t.data_ptr() for t in dkets])
+        check(lib.evc_fci_trdm_rows_packed(norb, na, nb, dta.data_ptr(), dtb.data_ptr(), dbra.data_ptr(), ptrs, K,
+                                           ovlp.data_ptr(), dm1.data_ptr(), lay, target.data_ptr(), ld,
+                                           self._ws.data_ptr(), grant + slot, self._stream()), "evc_fci_trdm_rows_packed")
+        if not direct:
+            out_rows.copy_(target)
+        return ovlp.cpu().numpy(), dm1.cpu().numpy()
 
     def trans_rdm12(self, cibra, ciket, norb, nelec):
         nelec = _nelec(nelec)

@@ -91,12 +91,23 @@ def _from_padded(one, S, two_padded: torch.Tensor, T: int, n: int) -> DeviceTRDM
 def load_checkpoint(directory: str, device=None, suffix: str = "") -> DeviceTRDMs:
     """``overlap{suffix}.npy / one_rdm{suffix}.npy / two_rdm{suffix}.npy`` -> packed device t-RDMs.  The
     two-body file is memory-mapped; a six-index array is packed on the device one pair block (N^4 doubles)
-    at a time, a ``(P,M)`` array is copied row by row."""
+    at a time, a ``(P,M)`` array is copied row by row.  Where there is no ``two_rdm{suffix}.npy`` but a
+    ``two_rdm_sym8{suffix}.npy`` (the ``(P, cols8)`` rows a sym8 ``resident.ResidentFCI_EVCont_obj`` checkpoints,
+    ``active_learning.converge_EVCont_MD``), the result is the 8-fold compressed set with exactly those rows."""
     dev = _dev(device)
     S = np.load(os.path.join(directory, f"overlap{suffix}.npy"))
     one = np.load(os.path.join(directory, f"one_rdm{suffix}.npy"))
-    two = np.load(os.path.join(directory, f"two_rdm{suffix}.npy"), mmap_mode="r")
     T, n = int(S.shape[0]), int(one.shape[-1])
+    path8 = os.path.join(directory, f"two_rdm_sym8{suffix}.npy")
+    if not os.path.exists(os.path.join(directory, f"two_rdm{suffix}.npy")) and os.path.exists(path8):
+        two8 = np.load(path8, mmap_mode="r")
+        rows8, cols8 = layout_shape(8, T, n)
+        assert two8.shape == (rows8, cols8), f"{path8} has shape {two8.shape}, expected {(rows8, cols8)}"
+        out = torch.zeros((rows8, (cols8 + 15) // 16 * 16), dtype=F64, device=dev)
+        for p in range(rows8):
+            out[p, :cols8].copy_(torch.from_numpy(np.array(two8[p], dtype=np.float64)))
+        return DeviceTRDMs.from_padded_rows(one, out, S, 8)
+    two = np.load(os.path.join(directory, f"two_rdm{suffix}.npy"), mmap_mode="r")
     rows, cols = layout_shape(2, T, n)
     ld = (cols + 15) // 16 * 16
     out = torch.zeros((rows, ld), dtype=F64, device=dev)

@@ -12,6 +12,7 @@ N geometries).  The 1000 evaluations run (a) through the reference-shaped call `
 few and (b) as batched device calls over all of them, which is how a scan should be run on this hardware.
 
     python examples/h10_forces.py [--radius 0.2] [--points 1000] [--exact 3] [--fixture]
+    python examples/h10_forces.py --solver device-davidson --resident    # the training set grown on the device (sym8 rows)
 """
 import argparse
 import os
@@ -47,7 +48,12 @@ p.add_argument("--cibasis", choices=("OAO", "canonical"), default="OAO",
                help="orbital basis the training states are solved in: the Loewdin basis (default), or the Hartree-Fock "
                     "basis (scf_small.rhf; fewer Davidson iterations near equilibrium), from which the solver's "
                     "transform_ci rotates each state into the Loewdin basis")
+p.add_argument("--resident", action="store_true",
+               help="with --solver device[-davidson]: grow the training set on the device (resident.ResidentFCI_EVCont_obj: "
+                    "the 8-fold compressed rows written in place by the row call, no two-body data on the host)")
 a = p.parse_args()
+if a.resident and (a.solver == "host" or a.fixture):
+    p.error("--resident needs --solver device or device-davidson and no --fixture")
 
 
 def make_solver():
@@ -68,7 +74,11 @@ def get_mol(positions, need_grad=True):
     return s_gaussian_mol(np.asarray(positions), exponents=ex, coefficients=co, need_grad=need_grad)
 
 
-continuation_object = FCI_EVCont_obj(cisolver=make_solver(), cibasis=a.cibasis)
+if a.resident:
+    from evcont_amd.resident import ResidentFCI_EVCont_obj
+    continuation_object = ResidentFCI_EVCont_obj(cisolver=make_solver(), cibasis=a.cibasis, layout="sym8", capacity=8)
+else:
+    continuation_object = FCI_EVCont_obj(cisolver=make_solver(), cibasis=a.cibasis)
 if a.fixture:
     with np.load(os.path.join(REPO, "tests", "golden", "h10_fci_t5.npz")) as z:
         continuation_object.overlap, continuation_object.one_rdm = z["overlap"], z["one_rdm"]
@@ -89,13 +99,19 @@ for i in range(n_data_points):
                      a.radius * np.cos(theta)), axis=-1)
     geoms.append(equilibrium_pos + disp)
 
-one, two, S = continuation_object.one_rdm, continuation_object.two_rdm, continuation_object.overlap
-# (a) the reference's call, geometry by geometry
-first = [get_energy_with_grad(get_mol(R), one, two, S) for R in geoms[:3]]
-
-# (b) all geometries in batched device calls against the resident compressed t-RDMs
 from evcont_amd.evaluator import DeviceTRDMs, DeviceAO                             # noqa: E402
-trd = DeviceTRDMs(one, two, S, compress="sym8")
+one, S = continuation_object.one_rdm, continuation_object.overlap
+if a.resident:
+    # (a) the scanner on the container's device rows; (b) the same rows
+    from evcont_amd.MD_utils import get_scanner                                    # noqa: E402
+    trd = continuation_object.device_trdms()
+    first = [get_scanner(get_mol(R), one, None, S, device_trdms=trd)(get_mol(R)) for R in geoms[:3]]
+else:
+    two = continuation_object.two_rdm
+    # (a) the reference's call, geometry by geometry
+    first = [get_energy_with_grad(get_mol(R), one, two, S) for R in geoms[:3]]
+    # (b) all geometries in batched device calls against the resident compressed t-RDMs
+    trd = DeviceTRDMs(one, two, S, compress="sym8")
 G = min(a.batch, n_data_points)
 be = BatchedEvaluator(trd, natm, G)
 en = np.zeros(n_data_points)

@@ -10,6 +10,7 @@ should be run on this hardware.
     python examples/h6_pes.py            # needs a HIP device; writes predicted_surface_*.txt, exact_surface.txt
     python examples/h6_pes.py --solver device     # the FCI training states on the GPU too (fci_device.DeviceFCI)
     python examples/h6_pes.py --solver device-davidson    # ... and their eigensolver iteration, on resident vectors
+    python examples/h6_pes.py --solver device --resident  # ... and the training set grown on the device (resident.py)
 """
 import argparse
 import os
@@ -44,20 +45,31 @@ def main():
     p.add_argument("--cibasis", choices=("OAO", "canonical"), default="OAO",
                    help="orbital basis the FCI is solved in: the Loewdin basis (default), or the Hartree-Fock basis "
                         "(scf_small.rhf), from which the solver's transform_ci rotates each state into the Loewdin basis")
+    p.add_argument("--resident", action="store_true",
+                   help="with --solver device[-davidson]: grow the training set on the device "
+                        "(resident.ResidentFCI_EVCont_obj, pack2 rows written in place; no two-body data on the host)")
     a = p.parse_args()
+    if a.resident and a.solver == "host":
+        p.error("--resident needs --solver device or device-davidson")
     if a.solver != "host":
         from evcont_amd.fci_device import DeviceFCI
         solver = DeviceFCI(eigensolver="davidson" if a.solver == "device-davidson" else "host")
     else:
         solver = SmallFCI()
-    continuation_object = FCI_EVCont_obj(cisolver=solver, cibasis=a.cibasis)
+    if a.resident:
+        from evcont_amd.resident import ResidentFCI_EVCont_obj
+        continuation_object = ResidentFCI_EVCont_obj(cisolver=solver, cibasis=a.cibasis, layout="pack2", capacity=4)
+    else:
+        continuation_object = FCI_EVCont_obj(cisolver=solver, cibasis=a.cibasis)
     test_dists = np.linspace(0.8, 3.0)
     test_mols = [get_mol(d) for d in test_dists]
     for i, trn_dist in enumerate([1.0, 1.8, 2.6]):
         continuation_object.append_to_rdms(get_mol(trn_dist))
-        # (a) the reference's call, one geometry at a time
-        ens = [approximate_ground_state_OAO(mol, continuation_object.one_rdm, continuation_object.two_rdm,
-                                            continuation_object.overlap)[0] for mol in test_mols]
+        # (a) the reference's call, one geometry at a time (a resident container hands out its packed rows, which are
+        # the reference's two-index two_RDM)
+        two = continuation_object.rows_host() if a.resident else continuation_object.two_rdm
+        ens = [approximate_ground_state_OAO(mol, continuation_object.one_rdm, two, continuation_object.overlap)[0]
+               for mol in test_mols]
         # (b) the whole scan as one batched device call against the container's resident packed t-RDMs
         trd = continuation_object.device_trdms()
         be = BatchedEvaluator(trd, n_atoms, len(test_mols))

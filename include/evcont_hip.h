@@ -44,6 +44,8 @@ extern "C" {
                                  stages EVC_PROF_FCI_*; additive: evc_fci_hdiag, evc_fci_dots, evc_fci_combine,
                                  evc_fci_davidson_correction, evc_fci_solve_workspace_bytes, EVC_PROF_FCI_SOLVE;
                                  additive: evc_fci_rotate, evc_fci_rotate_workspace_bytes, EVC_PROF_FCI_ROTATE;
+                                 additive: evc_fci_trdm_rows_packed, evc_fci_rows_packed_workspace_bytes,
+                                 EVC_PROF_FCI_PACK;
                                  evc_trdm_plan_describe */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
@@ -455,6 +457,26 @@ int evc_fci_sigma(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const 
                   const double *h2, const double *c, double *sigma, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * The row call with its two-body results written in place into the (pairs, ld) DEVICE matrix the evaluator streams
+ * (evcont_amd/resident.py): the same product as evc_fci_trdm_rows (same tilings, determinant blocks and order of the
+ * partial sums; ovlp and dm1 as there), then per ket the dense block dm2[p,q,r,s] goes through a scratch slot of the
+ * workspace into row i of `rows` (pitch ld doubles):
+ *   EVC_LAYOUT_PACK2   column R(R+1)/2 + C, R = pN+q >= C = rN+s, holds dm2[p,q,r,s] (multiplier 1);
+ *   EVC_LAYOUT_SYM8    column u(u+1)/2 + v, u = i(i+1)/2+j (i >= j), v = k(k+1)/2+l (k >= l), u >= v, holds
+ *                      0.125 * (((((((d0+d1)+d2)+d3)+d4)+d5)+d6)+d7) with d_m = dm2 at (i,j,k,l), (j,i,k,l), (i,j,l,k),
+ *                      (j,i,l,k), (k,l,i,j), (l,k,i,j), (k,l,j,i), (l,k,j,i): the bits DeviceTRDMs.compress_sym8_ gives
+ *                      for the six-index block.
+ * Columns cols ... ld - 1 of the nkets rows are written as zeros; nothing else of `rows` is touched.  ld: a multiple of
+ * 16, at least cols rounded up to 16, below 2^31.  Any other layout is refused.
+ * evc_fci_rows_packed_workspace_bytes(norb, na, nb, minimal): evc_fci_workspace_bytes(...) plus the slot of norb^4
+ *       doubles (rounded up to 256 bytes); 0 on an argument error.  Every accepted workspace gives the same bits.
+ * --------------------------------------------------------------------------------- */
+size_t evc_fci_rows_packed_workspace_bytes(int norb, int64_t na, int64_t nb, int minimal);
+int evc_fci_trdm_rows_packed(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
+                             const double *bra, const double *const *kets, int nkets, double *ovlp, double *dm1,
+                             int layout, double *rows, int64_t ld, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Vector work of an eigensolver around evc_fci_sigma (evcont_amd/fci_davidson.py: block Davidson with the diagonal of H
  * as preconditioner) on CI vectors that stay on the device.  A set of vectors is a row-major (count, ld) DEVICE array of
  * doubles, ld >= dim = na * nb; at most 256 vectors per set and call.  Every sum over the determinants is formed per
@@ -531,6 +553,8 @@ int evc_fci_rotate(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, con
                                      call and its grouping (not cleared by the other evc_fci_* entry points) */
 #define EVC_PROF_FCI_ROTATE 12    /* evc_fci_rotate: the minor kernel of each spin, whether it took the complementary
                                      minors, the panels of each T, and the product kernel */
+#define EVC_PROF_FCI_PACK 13      /* evc_fci_trdm_rows_packed: the packing kernel, e.g.
+                                     "fci_row_pack_kernel<8> rows=3 cols=231 ld=240" (<1>: PACK2, <8>: SYM8) */
 int evc_profile_begin(int max_samples);
 int evc_profile_end(double *rows_ms, int *rows_n, double *cols_ms, int *cols_n);
 int evc_profile_stage(int stage, double *ms, int *launches);
