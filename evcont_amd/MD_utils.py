@@ -213,7 +213,8 @@ def get_state_scanner(mol, one_rdm, two_rdm, overlap, root, hermitian=True):
 
 
 def get_trajectory(init_mol, overlap, one_rdm, two_rdm, dt=10.0, steps=10, init_veloc=None, hermitian=True,
-                   trajectory_output=None, energy_output=None, compress="default", device_trdms=None):
+                   trajectory_output=None, energy_output=None, compress="default", device_trdms=None,
+                   integrals="host"):
     """NVE trajectory from the continuation (reference :60-125).  Single process: the reference's
     rank-0-computes / Bcast split exists only to coexist with MPI-parallel training code.
 
@@ -221,7 +222,21 @@ def get_trajectory(init_mol, overlap, one_rdm, two_rdm, dt=10.0, steps=10, init_
     that can be rebuilt at new coordinates (``with_coords``, e.g. ``evcont_amd.hchain.HChainMol``) by the
     velocity-Verlet integrator below, with the same conventions (Bohr, atomic time units, frame 0 = the
     initial geometry, ``steps`` frames).  ``device_trdms``: as for ``get_scanner`` (training data already on the
-    device, e.g. ``resident.ResidentFCI_EVCont_obj.device_trdms()``; ``two_rdm`` may then be ``None``)."""
+    device, e.g. ``resident.ResidentFCI_EVCont_obj.device_trdms()``; ``two_rdm`` may then be ``None``).
+    ``integrals="device"`` (s-Gaussian ``with_coords`` molecules, Hermitian branch, host training arrays, no output
+    files): the one-trajectory case of ``state_swarm(..., integrals="device")`` -- the AO integrals of every step are
+    computed on the device from the coordinates."""
+    if integrals == "device":
+        if not (hermitian and device_trdms is None and compress == "default" and trajectory_output is None
+                and energy_output is None):
+            raise ValueError('get_trajectory(integrals="device") takes the Hermitian branch on host training arrays with '
+                             "the default compression and writes no output files")
+        v0 = None if init_veloc is None else np.asarray(init_veloc, dtype=np.float64)[None]
+        frames = state_swarm([init_mol], one_rdm, two_rdm, overlap, 0, dt=dt, steps=steps, init_veloc=v0,
+                             integrals="device")
+        return np.array([f["coord"][0] for f in frames])
+    if integrals != "host":
+        raise ValueError(f"unknown integrals={integrals!r} (known: 'host', 'device')")
     scanner_fun = get_scanner(init_mol, one_rdm, two_rdm, overlap, hermitian=hermitian, compress=compress,
                               device_trdms=device_trdms)
     if hasattr(init_mol, "with_coords"):
@@ -310,26 +325,68 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
                  data_addition=data_addition, **kwargs)
 
 
-def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_veloc=None):
+def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots):
+    """``evaluate(R (G,A,3)) -> (E (G,nroots), grads (G,nroots,A,3))`` for geometries of the s-Gaussian molecule of
+    ``mols``, device-resident from the coordinates on: the training set and the batched evaluator are built once, every
+    call uploads the coordinates, computes the AO integrals there (``hchain_device.DeviceSGaussians``) and runs the
+    batched several-roots call on them."""
+    from .ab_initio_eigenvector_continuation import resolve_compression
+    from .ab_initio_gradients_loewdin import _batched_evaluator
+    from .hchain_device import DeviceSGaussians
+    mol0, G = mols[0], len(mols)
+    if not all(hasattr(mol0, k) for k in ("charges", "exponents", "coefficients")):
+        raise ValueError('integrals="device" needs s-Gaussian molecules (evcont_amd.hchain.HChainMol)')
+    if G * nroots > 4096:
+        raise ValueError(f"{G} trajectories x {nroots} roots exceed the 4096 slots of one call")
+    t = _resident_trdms(one_rdm, two_rdm, overlap,
+                        resolve_compression("default", one_rdm, two_rdm, overlap, ao_arrays(mol0, need_grad=True)))
+    natm = int(np.asarray(mol0.charges).shape[0])
+    ev = _batched_evaluator(t, natm, G)
+    sg = DeviceSGaussians.from_mol(mol0, device=t.device)
+    packed = t.layout == _lib.LAYOUT_SYM8 and t.n <= 64
+
+    def evaluate(R):
+        E, _, grads = ev.multistate_energies_with_grads(sg.integrals(R, packed=packed), nroots)
+        return E, grads
+
+    return evaluate
+
+
+def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_veloc=None, integrals="host"):
     """Velocity-Verlet NVE of G trajectories on the continuation surface ``root`` (0 = ground state), advanced in lock
     step: every step is ONE batched call for all G geometries (``get_multistate_energies_with_grads``, all trajectories'
     roots 0 .. root in one pass).  ``mols``: the G initial geometries of one array-level molecule that can be rebuilt at
     new coordinates (``with_coords``, as ``get_trajectory``'s native path takes); ``init_veloc``: (G,A,3) or None.
     Conventions of ``nve_velocity_verlet`` (Bohr, atomic time units, frame 0 = the initial geometries); returns one
     frame per step with ``coord``/``veloc`` (G,A,3), ``epot``/``ekin`` (G,) and ``time``.  Plain adiabatic dynamics:
-    no surface hopping, and at (near-)degenerate roots the forces follow whichever eigenvector the solver returned."""
+    no surface hopping, and at (near-)degenerate roots the forces follow whichever eigenvector the solver returned.
+    ``integrals``: "host" rebuilds every molecule with ``with_coords`` (numpy) at every step; "device" (s-Gaussian
+    molecules, ``evcont_amd.hchain``) uploads the (G,A,3) coordinates and computes the AO integrals on the device."""
     from .ab_initio_gradients_loewdin import get_multistate_energies_with_grads
     mols = list(mols)
     root = int(root)
     if root < 0:
         raise ValueError(f"root={root} must be >= 0")
+    if integrals not in ("host", "device"):
+        raise ValueError(f"unknown integrals={integrals!r} (known: 'host', 'device')")
     R = np.array([m_.atom_coords() for m_ in mols], dtype=np.float64)
     m = (np.asarray(mols[0].atom_mass_list(), dtype=np.float64) * AMU2AU)[:, None]
     v = np.zeros_like(R) if init_veloc is None else np.array(init_veloc, dtype=np.float64).reshape(R.shape)
 
-    def evaluate(ms):
-        E, grads = get_multistate_energies_with_grads(ms, one_rdm, two_rdm, overlap, root + 1)
-        return E[:, root], grads[:, root]
+    if integrals == "device":
+        surfaces = _device_surfaces(mols, one_rdm, two_rdm, overlap, root + 1)
+
+        def evaluate(ms):
+            E, grads = surfaces(R)
+            return E[:, root], grads[:, root]
+
+        rebuild = lambda ms, R: ms
+    else:
+        def evaluate(ms):
+            E, grads = get_multistate_energies_with_grads(ms, one_rdm, two_rdm, overlap, root + 1)
+            return E[:, root], grads[:, root]
+
+        rebuild = lambda ms, R: [m_.with_coords(r) for m_, r in zip(ms, R)]
 
     e, g = evaluate(mols)
     frames = []
@@ -340,7 +397,7 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
             break
         a = -g / m
         R = _vv_drift(R, v, a, dt)
-        mols = [m_.with_coords(r) for m_, r in zip(mols, R)]
+        mols = rebuild(mols, R)
         e, g = evaluate(mols)
         v = _vv_kick(v, a, g, m, dt)
     return frames

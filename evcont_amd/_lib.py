@@ -55,6 +55,11 @@ class OutputsRoots(C.Structure):
     _fields_ = [("grad", C.c_void_p), ("d_pred", C.c_void_p), ("g_pred", C.c_void_p)]
 
 
+class SgtoOutputs(C.Structure):
+    _fields_ = [("enuc", C.c_void_p), ("S", C.c_void_p), ("hcore", C.c_void_p), ("eri", C.c_void_p),
+                ("ipovlp", C.c_void_p), ("dhcore", C.c_void_p), ("eri_ip1", C.c_void_p), ("gnuc", C.c_void_p)]
+
+
 # symbol -> (restype, argtypes); also the list the CPU test checks against the header
 SIGNATURES = {
     "evc_abi_version": (C.c_int, []),
@@ -147,6 +152,9 @@ SIGNATURES = {
     "evc_fci_rotate_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int]),
     "evc_fci_rotate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_sgto_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "evc_sgto_integrals_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(SgtoOutputs), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_profile_begin": (C.c_int, [C.c_int]),
     "evc_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int)]),

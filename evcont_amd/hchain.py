@@ -18,8 +18,8 @@ electron coordinate is minus the gradient with respect to its centre, which is w
 signs of ``ipovlp`` / ``eri_ip1`` relative to the nuclear derivatives; every derivative here is
 checked against central finite differences in ``tests/test_hchain_physics.py``.
 
-Host code (numpy): these are inputs of the accelerated path, produced once per geometry, exactly
-where the reference calls libcint.
+This module is the host statement (numpy), where the reference calls libcint; ``evcont_amd.hchain_device`` computes the
+same arrays on the device from the coordinates (``csrc/sgto.hip``), term for term.
 """
 from __future__ import annotations
 

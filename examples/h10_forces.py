@@ -13,6 +13,7 @@ few and (b) as batched device calls over all of them, which is how a scan should
 
     python examples/h10_forces.py [--radius 0.2] [--points 1000] [--exact 3] [--fixture]
     python examples/h10_forces.py --solver device-davidson --resident    # the training set grown on the device (sym8 rows)
+    python examples/h10_forces.py --fixture --integrals device           # the AO integrals of the scan on the device
 """
 import argparse
 import os
@@ -51,6 +52,9 @@ p.add_argument("--cibasis", choices=("OAO", "canonical"), default="OAO",
 p.add_argument("--resident", action="store_true",
                help="with --solver device[-davidson]: grow the training set on the device (resident.ResidentFCI_EVCont_obj: "
                     "the 8-fold compressed rows written in place by the row call, no two-body data on the host)")
+p.add_argument("--integrals", choices=("host", "device"), default="host",
+               help="where the AO integrals of the batched scan are computed: numpy on the host, or on the device from the "
+                    "uploaded coordinates (hchain_device.DeviceSGaussians)")
 a = p.parse_args()
 if a.resident and (a.solver == "host" or a.fixture):
     p.error("--resident needs --solver device or device-davidson and no --fixture")
@@ -117,13 +121,22 @@ be = BatchedEvaluator(trd, natm, G)
 en = np.zeros(n_data_points)
 gr = np.zeros((n_data_points, natm, 3))
 t_int = t_dev = 0.0
+if a.integrals == "device":
+    import torch                                                                   # noqa: E402
+    from evcont_amd.hchain_device import DeviceSGaussians                          # noqa: E402
+    sg = DeviceSGaussians(exponents=ex, coefficients=co, device=trd.device)
 for b0 in range(0, n_data_points, G):
     idx = [min(b0 + k, n_data_points - 1) for k in range(G)]          # (the last batch is padded)
     t0 = time.time()
-    mols = [get_mol(geoms[i]) for i in idx]
+    if a.integrals == "device":
+        aob = sg.integrals(np.stack([geoms[i] for i in idx]), packed=True)
+        torch.cuda.synchronize()
+    else:
+        mols = [get_mol(geoms[i]) for i in idx]
     t1 = time.time()
-    E, g = be.energies_with_grads(DeviceAOBatch.stack([DeviceAO.from_arrays(m, trd.device, pack_ip1=True, pack_eri=True)
-                                                       for m in mols]))
+    if a.integrals != "device":
+        aob = DeviceAOBatch.stack([DeviceAO.from_arrays(m, trd.device, pack_ip1=True, pack_eri=True) for m in mols])
+    E, g = be.energies_with_grads(aob)
     t_int, t_dev = t_int + t1 - t0, t_dev + time.time() - t1
     for k, i in enumerate(idx):
         en[i], gr[i] = E[k], g[k]
@@ -147,6 +160,6 @@ with open("H10_continuation_gradients_{}.txt".format(a.radius), "w") as fl:
         for row in gr[i]:
             fl.write("{}  {}  {}  ".format(*row))
         fl.write("\n")
-print(f"{n_data_points} geometries: host integrals {t_int:.2f} s, upload + device + download {t_dev:.2f} s; "
+print(f"{n_data_points} geometries: {a.integrals} integrals {t_int:.2f} s, upload + device + download {t_dev:.2f} s; "
       f"E[0] = {en[0]:.10f}, max |force| = {np.abs(gr).max():.6f}")
 print("OK")

@@ -12,6 +12,7 @@ script shows: per step one host integral evaluation (closed-form s-Gaussians her
 one staged upload (12 MB at H30 with the compressed layout) and one graph launch on the device.
 
     python examples/h30_md.py [--atoms 30] [--train 20] [--steps 5] [--dt 5]
+    python examples/h30_md.py --integrals device     # the AO integrals of every step on the device, from the coordinates
 """
 import argparse
 import os
@@ -33,6 +34,9 @@ p.add_argument("--atoms", type=int, default=30)
 p.add_argument("--train", type=int, default=20)
 p.add_argument("--steps", type=int, default=5)
 p.add_argument("--dt", type=float, default=5.0)
+p.add_argument("--integrals", choices=("host", "device"), default="host",
+               help="where the AO integrals of a step are computed: numpy on the host (with_coords), or on the device "
+                    "from the uploaded coordinates (hchain_device.DeviceSGaussians; the one-trajectory state_swarm)")
 a = p.parse_args()
 norb = nelec = a.atoms
 init_dist = 1.9
@@ -70,27 +74,46 @@ else:
     cont.overlap, cont.one_rdm, cont.two_rdm = S, one, two
     print(f"no overlap.npy here: synthetic stand-in for the DMRG training set ({a.train} states)")
 
-scanner = get_scanner(init_mol, cont.one_rdm, cont.two_rdm, cont.overlap, compress="sym8")
 t_host = [0.0]
-_with = init_mol.with_coords
+if a.integrals == "device":
+    import torch                                                                   # noqa: E402
+    from evcont_amd.MD_utils import state_swarm                                    # noqa: E402
+    from evcont_amd.hchain_device import DeviceSGaussians                          # noqa: E402
+    _integrals = DeviceSGaussians.integrals
 
+    def timed_integrals(self, *args, **kwargs):   # the device call that replaces with_coords, waited for
+        torch.cuda.synchronize()
+        t0 = time.time()
+        aob = _integrals(self, *args, **kwargs)
+        torch.cuda.synchronize()
+        t_host[0] += time.time() - t0
+        return aob
 
-def timed_with_coords(R):                      # where the reference calls libcint
+    DeviceSGaussians.integrals = timed_integrals
     t0 = time.time()
-    m = _with(R)
-    t_host[0] += time.time() - t0
-    return m
+    swarm = state_swarm([init_mol], cont.one_rdm, cont.two_rdm, cont.overlap, 0, dt=a.dt, steps=a.steps,
+                        integrals="device")
+    wall = time.time() - t0
+    frames = [{"coord": f["coord"][0], "epot": f["epot"][0], "ekin": f["ekin"][0]} for f in swarm]
+else:
+    scanner = get_scanner(init_mol, cont.one_rdm, cont.two_rdm, cont.overlap, compress="sym8")
+    _with = init_mol.with_coords
 
+    def timed_with_coords(R):                      # where the reference calls libcint
+        t0 = time.time()
+        m = _with(R)
+        t_host[0] += time.time() - t0
+        return m
 
-init_mol.with_coords = timed_with_coords
-t0 = time.time()
-frames = nve_velocity_verlet(scanner, init_mol, dt=a.dt, steps=a.steps)
-wall = time.time() - t0
+    init_mol.with_coords = timed_with_coords
+    t0 = time.time()
+    frames = nve_velocity_verlet(scanner, init_mol, dt=a.dt, steps=a.steps)
+    wall = time.time() - t0
 traj = np.array([f["coord"] for f in frames])
 np.save("traj_EVCont_0.npy", traj)
 etot = np.array([f["epot"] + f["ekin"] for f in frames])
-print(f"{a.steps} steps of H{a.atoms}: {wall:.2f} s wall, of which host integrals {t_host[0]:.2f} s; "
+print(f"{a.steps} steps of H{a.atoms}: {wall:.2f} s wall, of which {a.integrals} integrals {t_host[0]:.2f} s; "
       f"continuation steps/s excluding them: {a.steps / max(wall - t_host[0], 1e-9):.0f}; "
-      f"total-energy drift {etot[-1] - etot[0]:.2e} Ha")
+      f"total-energy drift {etot[-1] - etot[0]:.2e} Ha; E[0] = {frames[0]['epot']:.10f}, E[-1] = {frames[-1]['epot']:.10f}")
 assert np.all(np.isfinite(traj)) and np.all(np.isfinite(etot))
 print("OK")

@@ -531,6 +531,43 @@ int evc_fci_rotate(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, con
                    size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * AO integrals of s-Gaussian molecules on the device (csrc/sgto.hip; the host statement is evcont_amd/hchain.py
+ * s_gaussian_mol): one contracted s function per centre, the same contraction of nprim primitives on every centre, real
+ * nuclear charges.  One call writes every array of an evc_geometry_batch for `count` geometries, in the layout the
+ * evaluator reads, so a dynamics step stays on the device from coordinates to forces.
+ *   coords        DEVICE (count, natm, 3), Bohr.          charges       DEVICE (natm).
+ *   exponents, coefficients   HOST (nprim): exponents (> 0) and contraction coefficients of NORMALISED primitives; they
+ *                 reach the kernels by value.
+ *   out           every pointer DEVICE and writable, shapes as in evc_geometry_batch (N = natm); ipovlp, dhcore, eri_ip1
+ *                 and gnuc may be NULL with EVC_FLAG_ENERGY_ONLY and are then not written.
+ *   flags         EVC_FLAG_ENERGY_ONLY (S, hcore, eri, enuc only), EVC_FLAG_ERI_S4 (eri is (count, Ms, Ms), Ms = N(N+1)/2),
+ *                 EVC_FLAG_IP1_S2KL (eri_ip1 is (count, 3, N, N, Ms)); the packed forms need natm <= 64.  Any other flag is
+ *                 refused.
+ *   ws            DEVICE workspace (the primitive-pair table), 16-byte aligned, at least evc_sgto_workspace_bytes(...).
+ * Limits: 1 <= natm <= 96, 1 <= nprim <= 8, 1 <= count <= 65535.  A null required pointer, a shape outside the limits, an
+ * unknown flag, a non-positive exponent or a workspace that is too small is refused before anything is launched (rc < 0,
+ * evc_last_error).  Caller's stream, no allocation, no library state; nothing but the output arrays and the workspace
+ * is written.  No sum is split and there are no atomics: the same bits from run to run, for every batch size (geometry g
+ * of a batch = the call on it alone), and the full forms are the unpacked packed forms; eri with EVC_FLAG_ENERGY_ONLY has
+ * the bits of eri without it.  S and hcore are exactly symmetric.  No primitive quartet is screened.
+ * evc_sgto_workspace_bytes: 0 on a shape outside the limits.
+ * --------------------------------------------------------------------------------- */
+typedef struct evc_sgto_outputs {
+    double *enuc;    /* (count) */
+    double *S;       /* (count,N,N) */
+    double *hcore;   /* (count,N,N) */
+    double *eri;     /* (count,N,N,N,N), or (count,Ms,Ms) with EVC_FLAG_ERI_S4 */
+    double *ipovlp;  /* (count,3,N,N) */
+    double *dhcore;  /* (count,A,3,N,N) */
+    double *eri_ip1; /* (count,3,N,N,N,N), or (count,3,N,N,Ms) with EVC_FLAG_IP1_S2KL */
+    double *gnuc;    /* (count,A,3) */
+} evc_sgto_outputs;
+size_t evc_sgto_workspace_bytes(int natm, int nprim, int count);
+int evc_sgto_integrals_batch(int natm, int nprim, int count, const double *coords, const double *charges,
+                             const double *exponents, const double *coefficients, const evc_sgto_outputs *out, int flags,
+                             void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Measurement hook (bench.py): while enabled, the fused pipeline records hipEvents on the launch
  * stream immediately before and after the launches of the stages below, for up to max_samples
  * evaluations.  evc_profile_end synchronises those events, returns the summed durations in
