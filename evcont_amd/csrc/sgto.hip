@@ -104,7 +104,10 @@ __global__ __launch_bounds__(256) void sgto_pair_kernel(SgtoBasis bs, const doub
     const double ax = Ri[0], ay = Ri[1], az = Ri[2], bx = Rj[0], by = Rj[1], bz = Rj[2];
     const double p = a + b, mu = a * b / p;
     const double dx = ax - bx, dy = ay - by, dz = az - bz;
-    const double px = (a * ax + b * bx) / p, py = (a * ay + b * by) / p, pz = (a * az + b * bz) / p;
+    // where A_x = B_x (a pair on one centre) P_x is A_x exactly, not within a rounding of it: P - Q and P - C vanish
+    // exactly where they do mathematically
+    const double px = ax == bx ? ax : (a * ax + b * bx) / p, py = ay == by ? ay : (a * ay + b * by) / p;
+    const double pz = az == bz ? az : (a * az + b * bz) / p;
     const double c = exp(-mu * (dx * dx + dy * dy + dz * dz)) * w;
     double *tg = tab + (int64_t)g * sgto_table_doubles(N, K);
     double *row = tg + sgto_ket_doubles(N, K) + ((int64_t)o * K2 + ab) * kSgtoBra;

@@ -108,7 +108,10 @@ def s_gaussian_mol(coords, charges: Optional[Sequence[float]] = None,
     AB = Rp[:, None, :] - Rp[None, :, :]                    # (Np,Np,3)  A - B
     R2 = np.sum(AB * AB, axis=-1)
     Kab = np.exp(-mu * R2)
-    P = (a[:, None, None] * Rp[:, None, :] + a[None, :, None] * Rp[None, :, :]) / pp[:, :, None]
+    # P = (a A + b B) / p; where A_x = B_x (a pair on one centre) P_x is A_x exactly, not within a rounding of it, so that
+    # P - Q and P - C vanish exactly where they do mathematically
+    P = np.where(AB == 0.0, Rp[:, None, :],
+                 (a[:, None, None] * Rp[:, None, :] + a[None, :, None] * Rp[None, :, :]) / pp[:, :, None])
 
     def contract2(M):                                        # (..., Np, Np) -> (..., n, n)
         return np.einsum("pi,...pq,qj->...ij", Cm, M, Cm, optimize=True)

@@ -3,21 +3,17 @@ csrc/sgto.hip), through ctypes on NaN-poisoned, fenced output buffers and worksp
 within the derived bound of tests/sgto_reference.py: per element 2^-53 (n_terms + 432) sum|terms|.
 
 Largest |device - s_gaussian_mol| in units of 2^-53 sum|terms|, per shape: DESIGN.md section 8.2."""
-import ctypes as C
-
 import numpy as np
 import pytest
-import torch
 
 import sgto_reference as ref
 from evcont_amd import _lib
 from evcont_amd.hchain import (STO3G_H_COEFFICIENTS, STO3G_H_EXPONENTS, STO6G_H_COEFFICIENTS, STO6G_H_EXPONENTS,
                                s_gaussian_mol)
+from sgto_harness import GRAD_FIELDS, MODES, run, unpack
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-FENCE, GUARD = 12345.678, 64          # guard doubles on either side of every buffer
 STO3G = (STO3G_H_EXPONENTS, STO3G_H_COEFFICIENTS)
 STO6G = (STO6G_H_EXPONENTS, STO6G_H_COEFFICIENTS)
 ONE = ((0.4,), (1.0,))
@@ -49,72 +45,6 @@ SHAPES = {
     "A17_K1_G2": (_cluster(17, 2, 5), [1.0] * 17, ONE),
     "H10_K3_G1": (_chain(10, 1.8), [1.0] * 10, STO3G),
 }
-MODES = {"packed": _lib.FLAG_ERI_S4 | _lib.FLAG_IP1_S2KL, "full": 0, "energy": _lib.FLAG_ENERGY_ONLY}
-GRAD_FIELDS = ("ipovlp", "dhcore", "eri_ip1", "gnuc")
-
-
-def _shapes(A, G, packed):
-    n, ms = A, A * (A + 1) // 2
-    return {"enuc": (G,), "S": (G, n, n), "hcore": (G, n, n), "eri": (G, ms, ms) if packed else (G, n, n, n, n),
-            "ipovlp": (G, 3, n, n), "dhcore": (G, A, 3, n, n), "gnuc": (G, A, 3),
-            "eri_ip1": (G, 3, n, n, ms) if packed else (G, 3, n, n, n, n)}
-
-
-class Fenced:
-    """A device buffer of ``count`` doubles filled with NaN between two guards of FENCE."""
-
-    def __init__(self, count):
-        self.count = int(count)
-        self.buf = torch.full((self.count + 2 * GUARD,), float("nan"), dtype=torch.float64, device=DEV)
-        self.buf[:GUARD] = FENCE
-        self.buf[GUARD + self.count:] = FENCE
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + 8 * GUARD
-
-    def fences_intact(self):
-        h = self.buf.cpu().numpy()
-        return bool(np.all(h[:GUARD] == FENCE) and np.all(h[GUARD + self.count:] == FENCE))
-
-    def payload(self, shape=None):
-        h = self.buf.cpu().numpy()[GUARD:GUARD + self.count].copy()
-        return h if shape is None else h.reshape(shape)
-
-
-def run(R, Z, basis, mode, null_grad=False, ws_bytes=None, flags=None, **override):
-    """One call on fresh poisoned buffers -> (rc, {name: host array}, fences intact, raw Fenced buffers)."""
-    lib = _lib.load()
-    R = np.ascontiguousarray(R, dtype=np.float64)
-    G, A, K = R.shape[0], R.shape[1], len(basis[0])
-    shapes = _shapes(A, G, mode == "packed")
-    bufs = {k: Fenced(int(np.prod(s))) for k, s in shapes.items()}
-    need = lib.evc_sgto_workspace_bytes(A, K, G)
-    assert need > 0 and need % 8 == 0
-    ws = Fenced(need // 8)
-    dR = torch.from_numpy(R).to(DEV)
-    dZ = torch.from_numpy(np.ascontiguousarray(Z, dtype=np.float64)).to(DEV)
-    ex, co = (np.ascontiguousarray(b, dtype=np.float64) for b in basis)
-    out = _lib.SgtoOutputs(**{k: (None if (null_grad and k in GRAD_FIELDS) else b.ptr) for k, b in bufs.items()})
-    args = dict(natm=A, nprim=K, count=G, coords=dR.data_ptr(), charges=dZ.data_ptr(), ex=ex.ctypes.data,
-                co=co.ctypes.data, out=C.byref(out), flags=MODES[mode] if flags is None else flags, ws=ws.ptr,
-                ws_bytes=need if ws_bytes is None else ws_bytes)
-    args.update(override)
-    rc = lib.evc_sgto_integrals_batch(args["natm"], args["nprim"], args["count"], args["coords"], args["charges"],
-                                      args["ex"], args["co"], args["out"], args["flags"], args["ws"], args["ws_bytes"],
-                                      torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    arrays = {k: b.payload(shapes[k]) for k, b in bufs.items()}
-    intact = all(b.fences_intact() for b in bufs.values()) and ws.fences_intact()
-    return rc, arrays, intact, bufs
-
-
-def unpack(arrays, A):
-    """The full forms of packed ``eri`` (G,Ms,Ms) and ``eri_ip1`` (G,3,N,N,Ms)."""
-    iu, ju = np.tril_indices(A)
-    P = np.zeros((A, A), dtype=np.int64)
-    P[iu, ju] = P[ju, iu] = np.arange(len(iu))
-    return arrays["eri"][:, P][:, :, :, P], arrays["eri_ip1"][..., P]
 
 
 @pytest.fixture(scope="module", params=sorted(SHAPES))
