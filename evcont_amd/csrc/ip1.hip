@@ -143,7 +143,8 @@ __global__ __launch_bounds__(256) void ip1_dh_kernel(Ip1Args a) {
     const int64_t n2 = (int64_t)n * n, n3 = n2 * n, n4 = n2 * n2;
     const int64_t g = blockIdx.y, gi = geo_of(g, a.geo_period);   // slot, and the geometry whose inputs it reads
     const bool pair_blocks = a.presym && a.fold_cd && a.ip1_s2kl;
-    const int nb1 = kSlots > 1 ? ip1_slots_per_row(n, a.slots, kSlots) : pair_blocks ? n * (n + 1) / 2 : n * nchunk;
+    const int nb1 = kSlots > 1 ? ip1_slots_per_row(n, a.slots, kSlots)
+                               : pair_blocks ? (a.pairs_done ? 0 : n * (n + 1) / 2) : n * nchunk;
     if (kSlots > 1 && (int)blockIdx.x < nb1) {
         ip1_pair_slots<kSlots>(a, nb1);
     } else if (kSlots == 1 && pair_blocks && (int)blockIdx.x < nb1) {
@@ -345,7 +346,7 @@ template <int kSlots>
 static void ip1_launch(const Ip1Args &a, int count, hipStream_t st) {
     const bool pair_blocks = a.presym && a.fold_cd && a.ip1_s2kl;
     const int nb1 = kSlots > 1 ? ip1_slots_per_row(a.n, a.slots, kSlots)
-                               : pair_blocks ? a.n * (a.n + 1) / 2 : a.n * a.nchunk;
+                               : pair_blocks ? (a.pairs_done ? 0 : a.n * (a.n + 1) / 2) : a.n * a.nchunk;
     const int blocks = nb1 + a.natm * 3 + (a.n * a.n + 63) / 64;
     if constexpr (kSlots > 1) {   // (the pair-block form has no per-thread element count: one instance)
         hipLaunchKernelGGL((ip1_dh_kernel<8, kSlots>), dim3(blocks, (unsigned)count), dim3(256), 0, st, a);
@@ -369,7 +370,9 @@ int launch_ip1_dh(const Ip1Args &a, int count, hipStream_t st) {
     }
     EVC_LAUNCH_CHECK("ip1_dh");
     if (ks > 1) note_kernel(EVC_PROF_IP1, "ip1_dh_kernel<8> pairs slots=%d", ks);
-    else note_kernel(EVC_PROF_IP1, "ip1_dh_kernel<%d> %s", ip1_per_thread(), pair_blocks ? "pairs" : "chunks");
+    else
+        note_kernel(EVC_PROF_IP1, "ip1_dh_kernel<%d> %s", ip1_per_thread(),
+                    !pair_blocks ? "chunks" : a.pairs_done ? "pairs (dot in ptd)" : "pairs");
     return 0;
 }
 

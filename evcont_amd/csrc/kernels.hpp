@@ -169,6 +169,14 @@ struct PairTransformArgs {
     int in_ld, out_ld;  // row pitch (doubles) of the dense (pair, pair) operand / result; 0: n(n+1)/2 (the caller's s4 `int2e`);
                         // the pipeline's own intermediates use pair_ld(n): rows start on 128-byte lines
 };
+// launch_pair_transform_dot: the dense step does not write `out` but contracts its result with the packed int2e_ip1 as
+// the pair blocks of ip1_dh_kernel do (Ip1Args below, ip1_s2kl)
+struct PairDotArgs {
+    const double *ip1;  // (3,n,n,n(n+1)/2)  + g*sip1
+    double *t2part;     // (n,3,nchunk)      + g*st2
+    int64_t sip1, st2;
+    int nchunk;
+};
 // (pair_ld(n), the row pitch of the pipeline's dense (pair, pair) intermediates, and kPairTransformMaxN: route.hpp)
 // one packed operand row of the pair kernels in LDS (transform.hip pt_kernel, y2.hip y2_fused_kernel)
 constexpr int kPtRawMax = (kPairTransformMaxN * (kPairTransformMaxN + 1) / 2 + 1 + 127) / 128;   // double2 per lane: 5
@@ -176,6 +184,10 @@ constexpr int kPtRowLen = kPtRawMax * 128 + 4;   // + two zero slots (padding fr
 int launch_pair_transform(const PairTransformArgs &a, int count, hipStream_t st);
 // pair_dma.hip: the fully symmetric dense (pair, pair) -> dense (pair, pair) step, 16 < n <= 30, operand rows by LDS-DMA
 bool pair_transform_dma_applicable(const PairTransformArgs &a, int count);
+// ... with the int2e_ip1 dot in the place of its write-out (`a` as the launch that would write `out`; EVC_IP1_PAIRSTEP=0
+// turns it off, read once per process)
+bool pair_transform_dot_applicable(const PairTransformArgs &a, int count);
+int launch_pair_transform_dot(const PairTransformArgs &a, const PairDotArgs &dt, int count, hipStream_t st);
 int launch_pair_transform_dma(const PairTransformArgs &a, int count, hipStream_t st);
 // ... and the fused Y2 contraction with its two operand rows by LDS-DMA (same slabs as launch_y2_fused)
 bool y2_dma_applicable(int n);
@@ -253,6 +265,8 @@ struct Ip1Args {
     int slots;             // (pair-block route, geo_period > 0) root-pair slots per geometry: the launch has
                            // geo_period * slots slots, and one block reads the int2e_ip1 rows of a geometry once for up
                            // to kIp1MaxSlots of its slots (launch_ip1_dh); 0 or 1: one slot per block
+    int pairs_done;        // (pair-block route, one slot per block) the second gradient-side pair step has written the
+                           // pair blocks' entries of t2part (ptd_kernel<0, 1>): the grid has none
 };
 constexpr int kIp1MaxSlots = 8;
 int launch_ip1_dh(const Ip1Args &a, int count, hipStream_t st);

@@ -40,6 +40,8 @@ constexpr unsigned kPdStage = 4 * kPdRB;          // byte offset of the stage (a
 constexpr unsigned kPdP = 3872;                   // slot pitch of the stage: >= 8 (465 + 16) bytes, = 32 mod 128
 constexpr unsigned kPdTab = kPdStage + 16 * kPdP;   // MODE 1: multiplicity of pair u (1 on the diagonal i == j, else 2), 512 floats
 constexpr unsigned kPdLds = kPdTab, kPdLds1 = kPdTab + 512 * 4;
+// DOT: per tile parity the 48 sums of a tile (8 pairs x 2 orders of the pair x 3 components), behind the stage
+constexpr unsigned kPdRed = kPdTab, kPdRedB = 48 * 8, kPdLdsDot = kPdRed + 2 * kPdRedB;
 // The pair step that also contracts Y2 (y2d_kernel<1>): the M1 rows of the four waves behind their SB rows, the stage
 // behind those, and per wave a 32 x 32 square (pitch 34 doubles: its fragment reads are conflict free) through which
 // H goes from its accumulator form to the A-operand form.  130 KB: one workgroup per CU.
@@ -75,6 +77,8 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) f2 lds_f2;
 __device__ __forceinline__ double lds_ld(unsigned addr) { return *(lds_f64 *)(uintptr_t)addr; }
 __device__ __forceinline__ void lds_st(unsigned addr, double v) { *(lds_f64 *)(uintptr_t)addr = v; }
+typedef __attribute__((address_space(3))) d2 lds_d2;
+__device__ __forceinline__ d2 lds_ld2(unsigned addr) { return *(lds_d2 *)(uintptr_t)addr; }
 // k (0..3) wave-uniform: scalar compares and one wait
 __device__ __forceinline__ void wait_vm_dyn(int k) {
     if (k <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -126,11 +130,29 @@ struct Y2dArgs {
 // N-phase steps and reads the fragments back during the last ones, all at lane-constant addresses.  The M1 row comes
 // by LDS-DMA into a second row of the wave: fragments read during the Y phase, the next row requested behind them.
 // Every counted wait gets the DMA instructions and stores that are younger than the row it waits for.
-template <int MODE, bool Y2>
-__device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dArgs &y) {
+//
+// DOT (MODE 0, the second gradient-side step): the result R_e = row e = tri(hi, lo) of the AO-basis 2-RDM is not written
+// but contracted where it stands in the stage, as the pair blocks of ip1_dh_kernel (ip1.hip) contract it:
+//   t2part[(hi 3 + x) nchunk + lo] = sum_f w(f) R_e[f] ip1[x][hi][lo][f],   and for hi != lo with hi <-> lo,
+// w(f) = 1 on the diagonal pairs f = tri(c, c), else 2.  The write-out has its own thread map here: thread t takes ONE
+// pair of the tile (slot t / 32) and the rows f = 64 k + 2 u, + 1 (u = t % 32) of pass k -- one 16-byte LDS read of the
+// stage, and six 16-byte loads of int2e_ip1 (two orders of the pair x three components) that run along f across the
+// lanes, 512 contiguous bytes per row and wave as in ip1_dh_kernel (8-byte loads of two pairs per thread, in the map of
+// the storing write-out, touch four rows per quad of lanes: 113 us per launch however many were in flight).  The
+// addresses do not depend on the step's result, so the elements are requested one iteration ahead: the four passes of
+// a phase have a register set each, and behind pass k that set is reloaded with pass k + 4 (odd iterations: pass k - 4
+// of the next tile) -- 24 loads of 16 bytes per lane in flight, 98 KB per CU, through an H phase and more.  That costs
+// 96 VGPRs: ONE workgroup per CU (the launch is bound by the int2e_ip1 stream, not by the MFMAs), tiles per workgroup as
+// for the Y2 pair step.  Behind pass 7 of a tile each wave adds the six sums of its two pairs over its lanes (DPP and one
+// shuffle) into LDS behind the stage (one buffer per tile parity); the first 48 threads write the tile's 48 entries
+// behind the next barrier.  The int2e_ip1 loads are buffer loads the compiler counts; the wait for an operand row is
+// vmcnt(0) here.
+template <int MODE, bool Y2, bool DOT = false>
+__device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dArgs &y, const PairDotArgs &dt = PairDotArgs{}) {
     constexpr int KS = 8, NT = 2;
     constexpr unsigned kPdStage = Y2 ? kPdStageY : evc::kPdStage;   // (shadows the namespace constant)
     static_assert(!Y2 || MODE == 0, "the Y2 phase belongs to the dense step");
+    static_assert(!DOT || (MODE == 0 && !Y2), "the int2e_ip1 dot belongs to the dense step alone");
     extern __shared__ __align__(16) char lds[];   // the only LDS of this kernel: it starts at LDS address 0
     const int n = a.n;
     const int npairs = n * (n + 1) / 2;
@@ -251,7 +273,7 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
             frow[k] = (double)*(lds_f32 *)(uintptr_t)(kPdTab + 4u * (unsigned)(u & 511));
         }
     }
-    const int wrows = npairs - 16 * wave;   // pass k valid <=> 64 k < wrows
+    const int wrows = DOT ? npairs : npairs - 16 * wave;   // pass k valid <=> 64 k < wrows (DOT: every wave takes all 64 rows)
     // stores of an N phase that are younger than its DMA (passes c = 1..3 of the phase): what the wait for the next
     // operand row leaves in flight
     int vmask = 0;   // bit k: this wave writes pass k
@@ -264,6 +286,83 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
         cntA += (64 * c < wrows) ? 1 : 0;
         cntB += (64 * (4 + c) < wrows) ? 1 : 0;
     }
+    // DOT: the thread's pair of the tile and its row pair; of the rows 64 k + 2 du, + 1 a bit each for "diagonal pair"
+    // (weight 1, else 2; bits k, 8 + k) and for "a row of the result" (bits 16 + k, 24 + k); the int2e_ip1 blocks of the
+    // three components; the offsets bo of the rows (hi, lo), (lo, hi) of the tile being loaded; the sums; the register
+    // sets of the four passes of a phase
+    [[maybe_unused]] const int dslot = threadIdx.x >> 5, du = threadIdx.x & 31;
+    [[maybe_unused]] const unsigned wod = DOT ? opaque(kPdStage + (unsigned)dslot * kPdP + 16u * (unsigned)du) : 0u, du16 = 16u * (unsigned)du;
+    [[maybe_unused]] double acc[6];
+    [[maybe_unused]] d2 qb[4][6];
+    [[maybe_unused]] unsigned wm = 0, bo[2] = {0, 0};
+    // (buffer loads: a 32-bit lane offset, the component's block as the scalar offset; counted by the compiler)
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t iprs;
+    [[maybe_unused]] unsigned ipx[3] = {0, 0, 0};
+    if constexpr (DOT) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int f = 64 * k + 2 * du + h, fc = f < npairs ? f : 0, r = tri_row_small(fc);
+                wm |= (f < npairs ? 0x10000u << (8 * h + k) : 0u) | (fc == r * (r + 3) / 2 ? 1u << (8 * h + k) : 0u);
+            }
+        const unsigned xb = 8u * (unsigned)(n * n * npairs);
+        iprs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(dt.ip1 + g * dt.sip1), 0, (int)(3u * xb), 0x00020000);
+#pragma unroll
+        for (int x = 0; x < 3; ++x) ipx[x] = __builtin_amdgcn_readfirstlane(xb * (unsigned)x);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) acc[j] = 0.0;
+        if (blockIdx.x == 0 && dt.nchunk > n) {   // the slots behind the n partners, once per geometry
+            double *tp = dt.t2part + g * dt.st2;
+            const int pad = dt.nchunk - n;
+            for (int idx = threadIdx.x; idx < 3 * n * pad; idx += 256) tp[(int64_t)(idx / pad) * dt.nchunk + n + idx % pad] = 0.0;
+        }
+    }
+    // The two halves of a step of the dot: the six sums take register set c with the weighted stage values of pass k
+    // (rows beyond the last pair: zero, whatever the stage holds there); the set takes the loads of pass k of the tile
+    // bo belongs to.  A load stays inside its row: it starts at most at the last pair but one, and the thread whose
+    // first row is the last pair finds that pair in the second element.  The sums of a tile over the lanes of its pair,
+    // into the LDS buffer `par`; the 48 entries of tile jt out of it.
+    [[maybe_unused]] auto dot_fma = [&](int c, int k, d2 stage) {
+        const unsigned wk = opaque(wm) >> k;   // (opaque: the compiler otherwise keeps the weights of all passes in registers)
+        const bool ok0 = wk >> 16 & 1u, ok1 = wk >> 24 & 1u;
+        const double g0 = ok0 ? stage[0] * ((wk & 1u) ? 1.0 : 2.0) : 0.0, g1 = ok1 ? stage[1] * ((wk >> 8 & 1u) ? 1.0 : 2.0) : 0.0;
+        const double ga = (ok0 && !ok1) ? 0.0 : g0, gb = (ok0 && !ok1) ? g0 : g1;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) acc[j] = fma(qb[c][j][1], gb, fma(qb[c][j][0], ga, acc[j]));
+    };
+    [[maybe_unused]] auto dot_load = [&](int c, int k) {
+        const unsigned f8 = opaque(du16) + 512u * (unsigned)k, l8 = 8u * (unsigned)(npairs - 2), fo = f8 < l8 ? f8 : l8;
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+            qb[c][j] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(iprs, (int)(bo[j / 3] + fo), (int)ipx[j % 3], 0));
+    };
+    [[maybe_unused]] auto dot_reduce = [&](unsigned par) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            double v = acc[j];
+            v += dpp_move<0xB1>(v);
+            v += dpp_move<0x4E>(v);
+            v += dpp_move<0x141>(v);
+            v += dpp_move<0x140>(v);
+            v += __shfl_xor(v, 16);
+            if ((lane & 31) == 0) lds_st(kPdRed + par * kPdRedB + 8u * (unsigned)((2 * wave + (lane >> 5)) * 6 + j), v);
+            acc[j] = 0.0;
+        }
+    };
+    [[maybe_unused]] auto dot_flush = [&](int jt, unsigned par) {
+        if (threadIdx.x < 48) {
+            const int t = threadIdx.x, j = t % 6, x = j % 3;
+            const double sum = lds_ld(kPdRed + par * kPdRedB + 8u * (unsigned)t);
+            const int e = 8 * (t_begin + jt) + t / 6;
+            if (e < npairs) {
+                const int hi = tri_row_small(e), lo = e - hi * (hi + 1) / 2;
+                double *tp = dt.t2part + g * dt.st2;
+                if (j < 3) tp[((int64_t)hi * 3 + x) * dt.nchunk + lo] = sum;
+                else if (hi != lo) tp[((int64_t)lo * 3 + x) * dt.nchunk + hi] = sum;
+            }
+        }
+    };
     // the H square of the wave: written as the accumulator holds it (row 4 reg + l4 of a tile, column l15), read as
     // A fragments (row l15, column 4 kk + l4)
     // (a base per 2 KB: the compiler pairs these accesses into ds_write2 / ds_read2, whose offsets reach that far, and
@@ -338,6 +437,9 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
             }
         }
         if (!ODD && i >= 2) lds_barrier();
+        if constexpr (DOT) {   // the sums of tile (i - 4) / 2 were complete before this barrier
+            if (!ODD && i >= 4) dot_flush((i - 4) >> 1, TP);
+        }
         // ---------------------------------------------------------------- N = X^T H  (+ everything else)
         {
             // tile jt (relative to t_begin) is complete after this barrier: written out in the N phases of iterations
@@ -349,8 +451,18 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
 #ifdef EVC_PTD_K0
             const int K = 0;
 #else
-            const int K = (MODE == 0 && i >= 3) ? (ODD ? cntA : cntB) : 0;
+            const int K = (MODE == 0 && !DOT && i >= 3) ? (ODD ? cntA : cntB) : 0;
 #endif
+            if constexpr (DOT) {
+                // the int2e_ip1 rows (hi, lo) and (lo, hi) of the thread's pair of the tile whose passes 0..3 this phase
+                // requests and 4..7 the next one (idle slots: pair 0, not written)
+                if (ODD) {
+                    const int e = 8 * (t_begin + jt + 1) + dslot, ec = e < npairs ? e : 0;
+                    const int hi = tri_row_small(ec), lo = ec - hi * (hi + 1) / 2;
+                    bo[0] = 8u * (unsigned)((hi * n + lo) * npairs);
+                    bo[1] = 8u * (unsigned)((lo * n + hi) * npairs);
+                }
+            }
             d2 dv[4];
             [[maybe_unused]] int kd = 0;       // MODE 1: the pass that holds the diagonal u == v of this tile's columns
             [[maybe_unused]] d2 cf = {1.0, 1.0};   // MODE 1: multiplicities of the thread's two columns
@@ -368,8 +480,12 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
                 if ((kk & 1) == 0) {
                     const int c = kk / 2, k = (ODD ? 4 : 0) + c;
                     if (act >> k & 1) {
-                        dv[c][0] = lds_ld(wo + 512u * k + bimm);
-                        dv[c][1] = lds_ld(wo + 512u * k + bimm + kPdP);
+                        if constexpr (DOT) {
+                            dv[c] = lds_ld2(wod + 512u * k + bimm);
+                        } else {
+                            dv[c][0] = lds_ld(wo + 512u * k + bimm);
+                            dv[c][1] = lds_ld(wo + 512u * k + bimm + kPdP);
+                        }
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -421,7 +537,14 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
                     }
                     if (m == 2 && (kk & 1) == 1) {
                         const int c = kk / 2, k = (ODD ? 4 : 0) + c;
-                        if constexpr (MODE == 0) {
+                        if constexpr (DOT) {
+                            // pass k into the sums; its register set takes pass k + 4 of this tile (odd iterations: pass
+                            // k - 4 of the next tile, if the workgroup has one); behind pass 7 the tile's sums are complete
+                            if (act >> k & 1) dot_fma(c, k, dv[c]);
+                            const int kn = ODD ? c : 4 + c;
+                            if ((vmask >> kn & 1) && (ODD ? jt + 1 < t_end - t_begin : i >= 2)) dot_load(c, kn);
+                            if (c == 3 && ODD && i >= 3) dot_reduce(TP ^ 1u);
+                        } else if constexpr (MODE == 0) {
                             if (act >> k & 1) gstore16(gvo, dv[c], ob + (int64_t)(64 * k) * out_ld * 8);
                         } else if (act >> k & 1) {
                             const int u = ur + 64 * k;
@@ -518,6 +641,12 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
         iteration(F{}, P1{}, i + 1, nnA, nnB);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the rows requested beyond the last matrix)
+    if constexpr (DOT) {
+        // the last tile: no barrier of the loop came behind its sums
+        const int ntl = t_end - t_begin;
+        __syncthreads();
+        dot_flush(ntl - 1, (unsigned)(ntl - 1) & 1u);
+    }
     if constexpr (Y2) {
         // cross-wave sum of Y = Yd + 2 Yo over the rows and the stage, once every wave is done with them
         constexpr int NPAD = 32;
@@ -544,6 +673,11 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void ptd_kernel(PairTransformArgs a) {
     ptd_body<MODE, false>(a, Y2dArgs{});
+}
+// ... and with the int2e_ip1 dot in the place of the write-out (DOT = 1: a second template, the names of the kernels above stay)
+template <int MODE, int DOT>
+__global__ __launch_bounds__(256, 1) void ptd_kernel(PairTransformArgs a, PairDotArgs dt) {
+    ptd_body<MODE, false, DOT != 0>(a, Y2dArgs{}, dt);
 }
 
 // ---------------------------------------------------------------------------------- Y2 with LDS-DMA operand rows
@@ -780,6 +914,12 @@ int launch_y2_pairstep(const PairTransformArgs &a_in, const double *M1, double *
     return 0;
 }
 
+// EVC_IP1_PAIRSTEP=0: the second gradient-side pair step writes the AO-basis 2-RDM and ip1_dh_kernel's pair blocks contract it
+bool pair_transform_dot_applicable(const PairTransformArgs &a, int count) {
+    static const bool on = !(getenv("EVC_IP1_PAIRSTEP") && atoi(getenv("EVC_IP1_PAIRSTEP")) == 0);
+    return on && pair_transform_dma_applicable(a, count) && a.out && !a.packed;
+}
+
 bool pair_transform_dma_applicable(const PairTransformArgs &a, int count) {
     static const bool on = !(getenv("EVC_PT_DMA") && atoi(getenv("EVC_PT_DMA")) == 0);
     const int npairs = a.n * (a.n + 1) / 2;
@@ -787,6 +927,19 @@ bool pair_transform_dma_applicable(const PairTransformArgs &a, int count) {
            !a.k3 && (a.in_ld == 0 || a.in_ld >= npairs) &&
            ((a.out && a.out_pairs && !a.packed && a.out_ld >= 8 * ((npairs + 7) / 8) && a.out_ld % 2 == 0) ||
             (a.packed && a.sym8 && !a.out));
+}
+
+int launch_pair_transform_dot(const PairTransformArgs &a_in, const PairDotArgs &dt, int count, hipStream_t st) {
+    PairTransformArgs a = a_in;
+    const int ntiles = (a.n * (a.n + 1) / 2 + 7) / 8;
+    a.tiles_per_wg = y2_pairstep_tiles(count);   // (one workgroup per CU here as well)
+    const dim3 grid((unsigned)((ntiles + a.tiles_per_wg - 1) / a.tiles_per_wg), (unsigned)count);
+    static LdsAttr attr;
+    if (int rc = allow_dynamic_lds(ptd_kernel<0, 1>, attr, 160 * 1024, "pair_transform_dot")) return rc;
+    hipLaunchKernelGGL((ptd_kernel<0, 1>), grid, dim3(256), kPdLdsDot, st, a, dt);
+    note_kernel(EVC_PROF_PAIR_TRANSFORM, "ptd_kernel<0> +ip1");
+    EVC_LAUNCH_CHECK("pair_transform_dot");
+    return 0;
 }
 
 int launch_pair_transform_dma(const PairTransformArgs &a_in, int count, hipStream_t st) {

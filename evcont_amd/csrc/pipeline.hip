@@ -265,7 +265,10 @@ static int grad_head(const GradCall &x) { return launch_grad_prep(grad_prep_args
 
 // The shared tail: the int2e_ip1 contraction with G^AO in the form (presym, fold_cd, ip1_s2kl: Ip1Args, kernels.hpp) and
 // the sum of `nslab` Y2 slabs, the join of the side stream, the response term.
-static int grad_tail(const GradCall &x, const double *gao, int presym, int fold_cd, int ip1_s2kl, int nslab, bool timed) {
+// ip1_prof: the timing bracket the second pair step opened when it did the pair blocks' dot (ip1_pairs_done): closed
+// behind the residual launch here.
+static int grad_tail(const GradCall &x, const double *gao, int presym, int fold_cd, int ip1_s2kl, int nslab, bool timed,
+                     bool ip1_pairs_done = false, int ip1_prof = -1) {
     const Ws &w = x.c.w;
     const Geo &g = x.g;
     const int n = x.n, cnt = g.count;
@@ -291,7 +294,13 @@ static int grad_tail(const GradCall &x, const double *gao, int presym, int fold_
     ia.nchunk = ip1_chunks(n);
     ia.geo_period = g.geo_period;
     ia.slots = g.geo_period > 0 ? cnt / g.geo_period : 1;
-    EVC_TIMED(timed ? EVC_PROF_IP1 : -1, x.st, launch_ip1_dh(ia, cnt, x.st));
+    ia.pairs_done = ip1_pairs_done ? 1 : 0;
+    if (ip1_pairs_done) {
+        EVC_TRY(launch_ip1_dh(ia, cnt, x.st));
+        prof_stop(ip1_prof, x.st);
+    } else {
+        EVC_TIMED(timed ? EVC_PROF_IP1 : -1, x.st, launch_ip1_dh(ia, cnt, x.st));
+    }
     EVC_TRY(side_join(w.base, x.st));   // U and s may come from the side stream (phase_hamiltonian)
     GradFinalArgs f;
     f.n = n;
@@ -335,13 +344,39 @@ static PairTransformArgs grad_first_step(const Ws &w, int n, int sym) {
 }
 // ... and the second, B2 -> B1
 // (it keeps rs_lower as well: G^AO[m,b,c,d] = G^AO[b,m,c,d], fold_cd reads b <= m; the result is only valid for d <= c)
-static int grad_second_step(PairTransformArgs pa, const Ws &w, int out_pairs, int cnt, hipStream_t st) {
+static PairTransformArgs grad_second_args(PairTransformArgs pa, const Ws &w, int out_pairs) {
     pa.in = w.B2;
     pa.out = w.B1;
     pa.in_pairs = pa.out_pairs;
     pa.out_pairs = out_pairs;
+    return pa;
+}
+static int grad_second_step(PairTransformArgs pa, const Ws &w, int out_pairs, int cnt, hipStream_t st) {
+    pa = grad_second_args(pa, w, out_pairs);
     EVC_TIMED(EVC_PROF_PAIR_TRANSFORM, st, launch_pair_transform(pa, cnt, st));
     return 0;
+}
+// ... with the pair blocks of the packed int2e_ip1 contraction in the place of its write-out (ptd_kernel<0, 1>): nothing
+// but that dot reads B1 behind the step, so B1 stays unwritten.  One slot per geometry (the multi-slot roots form reads
+// the int2e_ip1 rows once for several slots: ip1_dh_kernel keeps it).  The launch belongs to the int2e_ip1 stage's time:
+// *prof is the open bracket, grad_tail closes it behind the residual ip1_dh_kernel launch.
+static bool grad_second_dot_applicable(const GradCall &x, const PairTransformArgs &first, const double *G, bool p64,
+                                       int ip1_s2kl) {
+    const Geo &g = x.g;
+    const bool one_slot = g.geo_period <= 0 || g.count == g.geo_period;
+    return ip1_s2kl && !G && !p64 && one_slot && pair_transform_dot_applicable(grad_second_args(first, x.c.w, 1), g.count);
+}
+static int grad_second_step_dot(const GradCall &x, PairTransformArgs pa, int *prof) {
+    const Ws &w = x.c.w;
+    pa = grad_second_args(pa, w, 1);
+    PairDotArgs dt;
+    dt.ip1 = x.g.eri_ip1;
+    dt.sip1 = x.g.sip1;
+    dt.t2part = w.t2part;
+    dt.st2 = w.stride;
+    dt.nchunk = ip1_chunks(x.n);
+    *prof = prof_start(EVC_PROF_IP1, x.st);
+    return launch_pair_transform_dot(pa, dt, x.g.count, x.st);
 }
 
 // G unpacked, N^4 (layouts 6 / 5 and evc_grad_elec_oao): symmetrise -> Y2 -> rotate G itself -> IP1 symmetrises on the fly
@@ -435,8 +470,14 @@ static int gradient_sym8_pairs(const GradCall &x, const double *packed, int64_t 
     prof_stop(pr, st);
     pa.in_pairs = (!G || p64) ? 1 : 0;
     if (!pairstep) EVC_TIMED(EVC_PROF_PAIR_TRANSFORM, st, launch_pair_transform(pa, cnt, st));
+    const int nslab = pairstep ? y2_pairstep_slabs(n, cnt) : y2_fused_slabs(n, cnt);
+    if (grad_second_dot_applicable(x, pa, G, p64, ip1_s2kl)) {
+        int ip1_prof = -1;
+        EVC_TRY(grad_second_step_dot(x, pa, &ip1_prof));
+        return grad_tail(x, w.B1, 1, 1, ip1_s2kl, nslab, true, true, ip1_prof);
+    }
     EVC_TRY(grad_second_step(pa, w, ip1_s2kl ? 1 : 0, cnt, st));
-    return grad_tail(x, w.B1, 1, 1, ip1_s2kl, pairstep ? y2_pairstep_slabs(n, cnt) : y2_fused_slabs(n, cnt), true);
+    return grad_tail(x, w.B1, 1, 1, ip1_s2kl, nslab, true);
 }
 
 int phase_gradient(const evc_trdm_set *t, const Geo &g_in, const Out &out, int flags, const Call &c, hipStream_t st) {
