@@ -158,7 +158,7 @@ struct PairTransformArgs {
     int64_t sin, sC, sout, spacked, sk3, packed_len;
     double diag_mult;
     int ct, n;
-    int tiles_per_wg;   // set by launch_pair_transform: consecutive 8-wide q tiles per workgroup
+    int tiles_per_wg;   // set by the launchers from the plan (pair_plan.hpp): consecutive 8-wide q tiles per workgroup
     int sym8;           // `packed` is the 8-fold compressed vector (EVC_LAYOUT_SYM8), multiplicities folded in
     int lead_sym;       // in[p][q][..] = in[q][p][..]: only q <= p (whole 8-wide q tiles) is computed and stored
     int in_lower;       // in[p][q][r][s] = in[p][q][s][r] and only r >= s is valid (output of a lead_sym step)
@@ -169,8 +169,7 @@ struct PairTransformArgs {
     int in_ld, out_ld;  // row pitch (doubles) of the dense (pair, pair) operand / result; 0: n(n+1)/2 (the caller's s4 `int2e`);
                         // the pipeline's own intermediates use pair_ld(n): rows start on 128-byte lines
 };
-// launch_pair_transform_dot: the dense step does not write `out` but contracts its result with the packed int2e_ip1 as
-// the pair blocks of ip1_dh_kernel do (Ip1Args below, ip1_s2kl)
+// what ptd_kernel<0, 1> contracts its result with (launch_pair_transform_dot, pair_plan.hpp)
 struct PairDotArgs {
     const double *ip1;  // (3,n,n,n(n+1)/2)  + g*sip1
     double *t2part;     // (n,3,nchunk)      + g*st2
@@ -181,25 +180,7 @@ struct PairDotArgs {
 // one packed operand row of the pair kernels in LDS (transform.hip pt_kernel, y2.hip y2_fused_kernel)
 constexpr int kPtRawMax = (kPairTransformMaxN * (kPairTransformMaxN + 1) / 2 + 1 + 127) / 128;   // double2 per lane: 5
 constexpr int kPtRowLen = kPtRawMax * 128 + 4;   // + two zero slots (padding fragments), 16-byte multiple
-int launch_pair_transform(const PairTransformArgs &a, int count, hipStream_t st);
-// pair_dma.hip: the fully symmetric dense (pair, pair) -> dense (pair, pair) step, 16 < n <= 30, operand rows by LDS-DMA
-bool pair_transform_dma_applicable(const PairTransformArgs &a, int count);
-// ... with the int2e_ip1 dot in the place of its write-out (`a` as the launch that would write `out`; EVC_IP1_PAIRSTEP=0
-// turns it off, read once per process)
-bool pair_transform_dot_applicable(const PairTransformArgs &a, int count);
-int launch_pair_transform_dot(const PairTransformArgs &a, const PairDotArgs &dt, int count, hipStream_t st);
-int launch_pair_transform_dma(const PairTransformArgs &a, int count, hipStream_t st);
-// ... and the fused Y2 contraction with its two operand rows by LDS-DMA (same slabs as launch_y2_fused)
-bool y2_dma_applicable(int n);
-int launch_y2_dma(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial, int64_t sws,
-                  int count, int slabs, int tiles_per_wg, int ppt, hipStream_t st);
-// Y2 inside the first gradient-side pair step (y2d_kernel<1>): the launch `a` describes (dense (pair, pair) SB in, ct = 1,
-// R out as ptd_kernel<0> writes it) and, from the H = SB_v X it forms, Y2 with M1 (pitch a.in_ld, geometry stride sws)
-// into y2_pairstep_slabs(n, count) slabs of `partial`.  EVC_Y2_PAIRSTEP=0 turns it off (read once per process).
-bool y2_pairstep_applicable(const PairTransformArgs &a, const double *M1, int64_t sws, int count);
-int y2_pairstep_slabs(int n, int count);
-int launch_y2_pairstep(const PairTransformArgs &a, const double *M1, double *partial, int64_t sws, int count,
-                       hipStream_t st);
+// (the plans of the pair steps and of Y2, and the launchers that take them: pair_plan.hpp)
 int launch_pack(const double *h2, int64_t sh2, int n, double diag_mult, double *out, int64_t sout, int64_t out_len,
                 int count, hipStream_t st);
 // 8-fold compressed vector of a tensor with the index symmetries of real two-electron integrals:
@@ -224,17 +205,9 @@ int launch_unpack8(const double *packed, int64_t sp, int n, double *SB, int64_t 
                    int lead_half, hipStream_t st);
 // partial[b][i][a] = sum_{k in slab b} SB[i][k] * K3[k][a]: the Y2 contraction with the row-major operand
 int launch_y2_sb(const double *SB, const double *K3, int n, double *partial, int64_t sws, int count, hipStream_t st);
-// Y2 without K3 (symmetric pipeline): the half-transformed integrals are recomputed from the dense (pair, pair)
-// intermediate `M1` of the first pair step (kept by the energy phase) inside the contraction,
-//   Y2[i][a] = sum_v mult(v) sum_j SB[v][tri(i,j)] (M1_v X)[a][j];
-// writes y2_fused_slabs(n, count) partial (n, n) matrices per geometry (slabs as launch_y2's); SB and M1 at the pitch
-// pair_ld(n)
-int launch_y2_fused(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial,
-                    int64_t sws, int count, hipStream_t st);
-int y2_fused_slabs(int n, int count);
 // partial[b][i][a] = sum_{k in slab b} GsT[k][i] * K3[k][a]   (k = jkl)
-int y2_slabs(int n);
-int y2_slab_capacity(int n);   // slabs the pipeline's partial buffer holds (>= y2_slabs)
+constexpr int kY2Slabs = 64;   // K slabs of these two = partial results per geometry
+inline int y2_slabs(int) { return kY2Slabs; }
 int launch_y2(const double *GsT, const double *K3, int n, double *partial, int64_t sws, int count, hipStream_t st);
 // ip1 contraction with on-the-fly AO symmetrisation (gradients_loewdin.py:234-252), dhcore:P_ao dots
 // and the fixed-order sum of the Y2 slabs (three block families of one launch)
@@ -270,14 +243,6 @@ struct Ip1Args {
 };
 constexpr int kIp1MaxSlots = 8;
 int launch_ip1_dh(const Ip1Args &a, int count, hipStream_t st);
-
-// ---- pair64.hip: the symmetric pipeline's pair step and Y2 for 32 < n <= 64 ----------------------------
-bool pair64_applicable(const PairTransformArgs &a);
-int launch_pair_transform64(const PairTransformArgs &a, int count, hipStream_t st);
-bool y2_64_applicable(int n);
-int y2_64_slabs(int n, int count);
-int launch_y2_64(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial, int64_t sws,
-                 int count, hipStream_t st);
 
 // ---- loewdin.hip (loewdin.hpp: the kernel body subspace_small.hip shares) -----------------------------
 struct LoewdinArgs {

@@ -19,10 +19,8 @@
 //     C^T M1_v (four tiles) and of Y (four accumulator tiles for the whole launch), so no wave holds more than eight
 //     tiles and nothing is summed across waves.
 // One workgroup per CU (115 KB of LDS); a workgroup of pt64 takes `tiles_per_wg` consecutive tiles of four pairs.
-#include <stdlib.h>
-
 #include "common.hpp"
-#include "kernels.hpp"
+#include "pair_plan.hpp"
 
 namespace evc {
 
@@ -39,14 +37,7 @@ __device__ __forceinline__ d4 mfma64(double a, double b, d4 c) {
 }
 __device__ __forceinline__ int c64(int row, int col) { return row * 64 + (col ^ ((row & 1) << 4)); }
 
-// doubles of one wave's row / stage buffer: the row, two zero slots behind it (fragments outside the matrix; two because
-// of the 16-byte window below), a length = 8 mod 32 (the four buffers then sit on disjoint quarter-banks for the
-// write-out, which reads slot-fastest)
-__host__ __device__ inline int p64_rowlen(int npairs) {
-    int r = npairs + 4;
-    r += (8 - (r & 31) + 32) & 31;
-    return r;
-}
+// (p64_rowlen, the doubles of one wave's row / stage buffer: pair_plan.hpp)
 
 // C (or its transpose) into LDS, zero padded to 64 x 64; the lane-constant fragment table; zero slots
 __device__ __forceinline__ void p64_setup(const double *__restrict__ C, int n, bool ct, double *Cs, int *ftab, int npairs) {
@@ -210,27 +201,12 @@ __global__ __launch_bounds__(256, 1) void pt64_kernel(PairTransformArgs a) {
     }
 }
 
-bool pair64_applicable(const PairTransformArgs &a) {
-    return a.n > kPairTransformMaxN && a.n <= 64 && a.lead_sym && a.in_lower && a.rs_lower && a.in_pairs &&
-           !a.k3 && ((a.packed && a.sym8 && !a.out) || (a.out && a.out_pairs && !a.packed));
-}
-
-size_t pair64_lds_bytes(int n) {
-    return sizeof(double) * (4096 + 2048 + (size_t)4 * p64_rowlen(n * (n + 1) / 2));
-}
-
-int launch_pair_transform64(const PairTransformArgs &a_in, int count, hipStream_t st) {
-    PairTransformArgs a = a_in;
-    const int npairs = a.n * (a.n + 1) / 2, ntiles = (npairs + 3) / 4;
-    // one resident round of the chip (one workgroup per CU)
-    int tpw = (int)ceil_div((int64_t)ntiles * count, (int64_t)250);
-    if (tpw < 1) tpw = 1;
-    a.tiles_per_wg = tpw;
+// (a: tiles_per_wg filled from the plan, launch_pair_transform)
+int launch_pair_transform64(const PairPlan &p, const PairTransformArgs &a, int count, hipStream_t st) {
     static LdsAttr attr;
     if (int rc = allow_dynamic_lds(pt64_kernel, attr, 160 * 1024, "pt64")) return rc;
-    hipLaunchKernelGGL(pt64_kernel, dim3((unsigned)ceil_div(ntiles, tpw), (unsigned)count), dim3(256),
-                       pair64_lds_bytes(a.n), st, a);
-    note_kernel(EVC_PROF_PAIR_TRANSFORM, "pt64_kernel<%d>", a.packed ? 1 : 0);
+    hipLaunchKernelGGL(pt64_kernel, dim3(p.grid_x, (unsigned)count), dim3(256), p.lds, st, a);
+    note_kernel(EVC_PROF_PAIR_TRANSFORM, "%s", pair_plan_name(p));
     EVC_LAUNCH_CHECK("pt64");
     return 0;
 }
@@ -327,28 +303,12 @@ __global__ __launch_bounds__(256, 1) void y2_64_kernel(const double *__restrict_
         }
 }
 
-bool y2_64_applicable(int n) { return n > kPairTransformMaxN && n <= 64; }
-
-int y2_64_slabs(int n, int count) {
-    // one resident round of the chip, never more slabs than the partial buffer holds
-    const int npairs = n * (n + 1) / 2;
-    int wgs = count >= 250 ? 1 : 250 / count;
-    const int cap = y2_slab_capacity(n);
-    if (wgs > cap) wgs = cap;
-    if (wgs > npairs) wgs = npairs;
-    const int ppw = (npairs + wgs - 1) / wgs;
-    return (npairs + ppw - 1) / ppw;
-}
-
-int launch_y2_64(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial, int64_t sws,
-                 int count, hipStream_t st) {
-    const int npairs = n * (n + 1) / 2, slabs = y2_64_slabs(n, count), ppw = (npairs + slabs - 1) / slabs;
-    const size_t lds = sizeof(double) * (4096 + 2048 + (size_t)4 * p64_rowlen(npairs));
+int launch_y2_64(const Y2Plan &p, const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial,
+                 int64_t sws, int count, hipStream_t st) {
     static LdsAttr attr;
     if (int rc = allow_dynamic_lds(y2_64_kernel, attr, 160 * 1024, "y2_64")) return rc;
-    hipLaunchKernelGGL(y2_64_kernel, dim3((unsigned)slabs, (unsigned)count), dim3(256), lds, st, SB, M1, X, sX, n,
-                       partial, sws, ppw);
-    note_kernel(EVC_PROF_Y2, "y2_64_kernel");
+    hipLaunchKernelGGL(y2_64_kernel, dim3((unsigned)p.slabs, (unsigned)count), dim3(256), p.lds, st, SB, M1, X, sX, n,
+                       partial, sws, p.ppt);
     EVC_LAUNCH_CHECK("y2_64");
     return 0;
 }

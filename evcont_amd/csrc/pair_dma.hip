@@ -21,10 +21,8 @@
 // The pipeline around these pieces is pt_pipe_kernel's: one matrix per iteration, result i-1 staged during the H phase
 // of matrix i, one barrier per tile of eight leading pairs, tile j written out during the N phases of the two
 // iterations behind its barrier, two workgroups per CU.
-#include <stdlib.h>
-
 #include "common.hpp"
-#include "kernels.hpp"
+#include "pair_plan.hpp"
 
 namespace evc {
 
@@ -33,22 +31,7 @@ namespace {
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-constexpr int kPdMaxN = 30;
-constexpr unsigned kPdRaw = 4;                    // 1 KiB pieces per operand row (465 + 1 doubles at most)
-constexpr unsigned kPdRB = kPdRaw * 1024 + 64;    // bytes per wave: the row and a zero slot behind it
-constexpr unsigned kPdStage = 4 * kPdRB;          // byte offset of the stage (a multiple of 256)
-constexpr unsigned kPdP = 3872;                   // slot pitch of the stage: >= 8 (465 + 16) bytes, = 32 mod 128
-constexpr unsigned kPdTab = kPdStage + 16 * kPdP;   // MODE 1: multiplicity of pair u (1 on the diagonal i == j, else 2), 512 floats
-constexpr unsigned kPdLds = kPdTab, kPdLds1 = kPdTab + 512 * 4;
-// DOT: per tile parity the 48 sums of a tile (8 pairs x 2 orders of the pair x 3 components), behind the stage
-constexpr unsigned kPdRed = kPdTab, kPdRedB = 48 * 8, kPdLdsDot = kPdRed + 2 * kPdRedB;
-// The pair step that also contracts Y2 (y2d_kernel<1>): the M1 rows of the four waves behind their SB rows, the stage
-// behind those, and per wave a 32 x 32 square (pitch 34 doubles: its fragment reads are conflict free) through which
-// H goes from its accumulator form to the A-operand form.  130 KB: one workgroup per CU.
-constexpr unsigned kPdStageY = 8 * kPdRB;
-constexpr unsigned kPdSqP = 34, kPdSqB = 32 * kPdSqP * 8;
-constexpr unsigned kPdSq = kPdStageY + 16 * kPdP;
-constexpr unsigned kPdLdsY = kPdSq + 4 * kPdSqB;
+// (kPdMaxN and the LDS layout constants kPd*: pair_plan.hpp, the plans size the launches from them)
 
 __device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
@@ -862,102 +845,52 @@ __global__ __launch_bounds__(256, PS ? 1 : 2) void y2d_kernel(Y2dArgs ya, PairTr
     }
 }
 
-bool y2_dma_applicable(int n) {
-    static const bool on = !(getenv("EVC_PT_DMA") && atoi(getenv("EVC_PT_DMA")) == 0);
-    return on && n > 16 && n <= kPdMaxN;
-}
-
-int launch_y2_dma(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial, int64_t sws,
-                  int count, int slabs, int tiles_per_wg, int ppt, hipStream_t st) {
-    constexpr unsigned ldsb = 8 * kPdRB > 4 * 32 * 33 * 8 ? 8 * kPdRB : 4 * 32 * 33 * 8;
-    Y2dArgs ya{SB, M1, X, partial, sX, sws, n, tiles_per_wg, ppt};
-    hipLaunchKernelGGL((y2d_kernel<0>), dim3((unsigned)slabs, (unsigned)count), dim3(256), ldsb, st, ya, PairTransformArgs{});
-    note_kernel(EVC_PROF_Y2, "y2d_kernel");
+int launch_y2_dma(const Y2Plan &p, const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial,
+                  int64_t sws, int count, hipStream_t st) {
+    Y2dArgs ya{SB, M1, X, partial, sX, sws, n, p.tiles_per_wg, p.ppt};
+    hipLaunchKernelGGL((y2d_kernel<0>), dim3((unsigned)p.slabs, (unsigned)count), dim3(256), p.lds, st, ya, PairTransformArgs{});
     EVC_LAUNCH_CHECK("y2_dma");
     return 0;
 }
 
-// EVC_Y2_PAIRSTEP=0: Y2 and the first gradient-side pair step as two kernels (y2d_kernel<0>, ptd_kernel<0>)
-static bool y2_pairstep_on() {
-    static const bool on = !(getenv("EVC_Y2_PAIRSTEP") && atoi(getenv("EVC_Y2_PAIRSTEP")) == 0);
-    return on;
-}
-// 8-pair tiles per workgroup: one workgroup per CU, so a batch that fills the chip takes 8 (N = 30, 32 geometries: 256
-// workgroups), smaller ones fewer for more workgroups
-static int y2_pairstep_tiles(int count) { return count >= 32 ? 8 : count >= 8 ? 4 : 2; }
-
-int y2_pairstep_slabs(int n, int count) {
-    const int ntiles = (n * (n + 1) / 2 + 7) / 8, t = y2_pairstep_tiles(count);
-    return (ntiles + t - 1) / t;
-}
-
-bool y2_pairstep_applicable(const PairTransformArgs &a, const double *M1, int64_t sws, int count) {
-    const int npairs = a.n * (a.n + 1) / 2;
-    // (both rows of a pair share one DMA window: rows on 16-byte granules, same pitch)
-    const bool aligned = ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(M1)) & 15) == 0 &&
-                         a.in_ld >= npairs && a.in_ld % 2 == 0 && a.sin % 2 == 0 && sws % 2 == 0;
-    return y2_pairstep_on() && y2_dma_applicable(a.n) && pair_transform_dma_applicable(a, count) && a.out && a.ct == 1 &&
-           aligned && a.in != a.out && y2_pairstep_slabs(a.n, count) <= y2_slab_capacity(a.n);
-}
-
-int launch_y2_pairstep(const PairTransformArgs &a_in, const double *M1, double *partial, int64_t sws, int count,
-                       hipStream_t st) {
+int launch_y2_pairstep(const Y2Plan &p, const PairTransformArgs &a_in, const double *M1, double *partial, int64_t sws,
+                       int count, hipStream_t st) {
     PairTransformArgs a = a_in;
-    a.tiles_per_wg = y2_pairstep_tiles(count);
-    Y2dArgs ya{a.in, M1, a.C, partial, a.sC, sws, a.n, a.tiles_per_wg, 8};
+    a.tiles_per_wg = p.tiles_per_wg;
+    Y2dArgs ya{a.in, M1, a.C, partial, a.sC, sws, a.n, p.tiles_per_wg, p.ppt};
     static LdsAttr attr;
     if (int rc = allow_dynamic_lds(y2d_kernel<1>, attr, 160 * 1024, "y2_pairstep")) return rc;
-    hipLaunchKernelGGL((y2d_kernel<1>), dim3((unsigned)y2_pairstep_slabs(a.n, count), (unsigned)count), dim3(256), kPdLdsY,
-                       st, ya, a);
-    note_kernel(EVC_PROF_Y2, "y2d_kernel<1> pairstep");
+    hipLaunchKernelGGL((y2d_kernel<1>), dim3((unsigned)p.slabs, (unsigned)count), dim3(256), p.lds, st, ya, a);
+    note_kernel(EVC_PROF_Y2, "%s", y2_plan_name(p));
     EVC_LAUNCH_CHECK("y2_pairstep");
     return 0;
 }
 
-// EVC_IP1_PAIRSTEP=0: the second gradient-side pair step writes the AO-basis 2-RDM and ip1_dh_kernel's pair blocks contract it
-bool pair_transform_dot_applicable(const PairTransformArgs &a, int count) {
-    static const bool on = !(getenv("EVC_IP1_PAIRSTEP") && atoi(getenv("EVC_IP1_PAIRSTEP")) == 0);
-    return on && pair_transform_dma_applicable(a, count) && a.out && !a.packed;
-}
-
-bool pair_transform_dma_applicable(const PairTransformArgs &a, int count) {
-    static const bool on = !(getenv("EVC_PT_DMA") && atoi(getenv("EVC_PT_DMA")) == 0);
-    const int npairs = a.n * (a.n + 1) / 2;
-    return on && a.n > 16 && a.n <= kPdMaxN && count >= 4 && a.lead_sym && a.in_lower && a.rs_lower && a.in_pairs &&
-           !a.k3 && (a.in_ld == 0 || a.in_ld >= npairs) &&
-           ((a.out && a.out_pairs && !a.packed && a.out_ld >= 8 * ((npairs + 7) / 8) && a.out_ld % 2 == 0) ||
-            (a.packed && a.sym8 && !a.out));
-}
-
-int launch_pair_transform_dot(const PairTransformArgs &a_in, const PairDotArgs &dt, int count, hipStream_t st) {
+int launch_pair_transform_dot(const PairPlan &p, const PairTransformArgs &a_in, const PairDotArgs &dt, int count,
+                              hipStream_t st) {
     PairTransformArgs a = a_in;
-    const int ntiles = (a.n * (a.n + 1) / 2 + 7) / 8;
-    a.tiles_per_wg = y2_pairstep_tiles(count);   // (one workgroup per CU here as well)
-    const dim3 grid((unsigned)((ntiles + a.tiles_per_wg - 1) / a.tiles_per_wg), (unsigned)count);
+    a.tiles_per_wg = p.tiles_per_wg;
     static LdsAttr attr;
     if (int rc = allow_dynamic_lds(ptd_kernel<0, 1>, attr, 160 * 1024, "pair_transform_dot")) return rc;
-    hipLaunchKernelGGL((ptd_kernel<0, 1>), grid, dim3(256), kPdLdsDot, st, a, dt);
-    note_kernel(EVC_PROF_PAIR_TRANSFORM, "ptd_kernel<0> +ip1");
+    hipLaunchKernelGGL((ptd_kernel<0, 1>), dim3(p.grid_x, (unsigned)count), dim3(256), p.lds, st, a, dt);
+    note_kernel(EVC_PROF_PAIR_TRANSFORM, "%s", pair_plan_name(p));
     EVC_LAUNCH_CHECK("pair_transform_dot");
     return 0;
 }
 
-int launch_pair_transform_dma(const PairTransformArgs &a_in, int count, hipStream_t st) {
-    PairTransformArgs a = a_in;
-    const int npairs = a.n * (a.n + 1) / 2, ntiles = (npairs + 7) / 8;
-    if (a.tiles_per_wg < 1) a.tiles_per_wg = 4;
-    const dim3 grid((unsigned)((ntiles + a.tiles_per_wg - 1) / a.tiles_per_wg), (unsigned)count);
-    if (a.packed) {
+// (a: tiles_per_wg filled from the plan, launch_pair_transform)
+int launch_pair_transform_dma(const PairPlan &p, const PairTransformArgs &a, int count, hipStream_t st) {
+    const dim3 grid(p.grid_x, (unsigned)count);
+    if (p.t[0]) {
         static LdsAttr attr1;
         if (int rc = allow_dynamic_lds(ptd_kernel<1>, attr1, 160 * 1024, "pair_transform_dma")) return rc;
-        hipLaunchKernelGGL((ptd_kernel<1>), grid, dim3(256), kPdLds1, st, a);
-        note_kernel(EVC_PROF_PAIR_TRANSFORM, "ptd_kernel<1>");
+        hipLaunchKernelGGL((ptd_kernel<1>), grid, dim3(256), p.lds, st, a);
     } else {
         static LdsAttr attr;
         if (int rc = allow_dynamic_lds(ptd_kernel<0>, attr, 160 * 1024, "pair_transform_dma")) return rc;
-        hipLaunchKernelGGL((ptd_kernel<0>), grid, dim3(256), kPdLds, st, a);
-        note_kernel(EVC_PROF_PAIR_TRANSFORM, "ptd_kernel<0>");
+        hipLaunchKernelGGL((ptd_kernel<0>), grid, dim3(256), p.lds, st, a);
     }
+    note_kernel(EVC_PROF_PAIR_TRANSFORM, "%s", pair_plan_name(p));
     EVC_LAUNCH_CHECK("pair_transform_dma");
     return 0;
 }

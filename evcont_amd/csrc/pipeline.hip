@@ -342,42 +342,7 @@ static PairTransformArgs grad_first_step(const Ws &w, int n, int sym) {
     a.in_ld = a.out_ld = pair_ld(n);   // (pitch of every dense (pair, pair) form of the pipeline)
     return a;
 }
-// ... and the second, B2 -> B1
-// (it keeps rs_lower as well: G^AO[m,b,c,d] = G^AO[b,m,c,d], fold_cd reads b <= m; the result is only valid for d <= c)
-static PairTransformArgs grad_second_args(PairTransformArgs pa, const Ws &w, int out_pairs) {
-    pa.in = w.B2;
-    pa.out = w.B1;
-    pa.in_pairs = pa.out_pairs;
-    pa.out_pairs = out_pairs;
-    return pa;
-}
-static int grad_second_step(PairTransformArgs pa, const Ws &w, int out_pairs, int cnt, hipStream_t st) {
-    pa = grad_second_args(pa, w, out_pairs);
-    EVC_TIMED(EVC_PROF_PAIR_TRANSFORM, st, launch_pair_transform(pa, cnt, st));
-    return 0;
-}
-// ... with the pair blocks of the packed int2e_ip1 contraction in the place of its write-out (ptd_kernel<0, 1>): nothing
-// but that dot reads B1 behind the step, so B1 stays unwritten.  One slot per geometry (the multi-slot roots form reads
-// the int2e_ip1 rows once for several slots: ip1_dh_kernel keeps it).  The launch belongs to the int2e_ip1 stage's time:
-// *prof is the open bracket, grad_tail closes it behind the residual ip1_dh_kernel launch.
-static bool grad_second_dot_applicable(const GradCall &x, const PairTransformArgs &first, const double *G, bool p64,
-                                       int ip1_s2kl) {
-    const Geo &g = x.g;
-    const bool one_slot = g.geo_period <= 0 || g.count == g.geo_period;
-    return ip1_s2kl && !G && !p64 && one_slot && pair_transform_dot_applicable(grad_second_args(first, x.c.w, 1), g.count);
-}
-static int grad_second_step_dot(const GradCall &x, PairTransformArgs pa, int *prof) {
-    const Ws &w = x.c.w;
-    pa = grad_second_args(pa, w, 1);
-    PairDotArgs dt;
-    dt.ip1 = x.g.eri_ip1;
-    dt.sip1 = x.g.sip1;
-    dt.t2part = w.t2part;
-    dt.st2 = w.stride;
-    dt.nchunk = ip1_chunks(x.n);
-    *prof = prof_start(EVC_PROF_IP1, x.st);
-    return launch_pair_transform_dot(pa, dt, x.g.count, x.st);
-}
+// (... and the second, B2 -> B1: grad_second_args, pair_plan.hpp)
 
 // G unpacked, N^4 (layouts 6 / 5 and evc_grad_elec_oao): symmetrise -> Y2 -> rotate G itself -> IP1 symmetrises on the fly
 int gradient_unpacked(const GradCall &x, const double *G, int64_t sG) {
@@ -407,7 +372,7 @@ static int gradient_packed_ref(const GradCall &x, const double *packed, int64_t 
     if (pairs) {
         const PairTransformArgs pa = grad_first_step(w, n, 0);
         EVC_TIMED(EVC_PROF_PAIR_TRANSFORM, x.st, launch_pair_transform(pa, cnt, x.st));
-        EVC_TRY(grad_second_step(pa, w, 0, cnt, x.st));
+        EVC_TIMED(EVC_PROF_PAIR_TRANSFORM, x.st, launch_pair_transform(grad_second_args(pa, w.B1, 0), cnt, x.st));
     } else if (int rc = rotate_four_index(Steps::Quarter, w.B1, sw, w.X, sw, 1, n, w.B2, sw, w.B1, sw, cnt, x.st)) {
         return rc;
     }
@@ -430,7 +395,7 @@ static int gradient_sym8_quarter(const GradCall &x, const double *packed, int64_
 // The symmetric pipeline (compressed layout on pair steps, n <= 32 and the 64-wide form): unpack into the dense
 // (pair, pair) SB -> Y2 from the energy phase's intermediate in the K3 buffer (K3 was written for l <= k only) ->
 // B1 -> B2 -> B1 (AO, dense where int2e_ip1 is packed: the packed-ip1 dot weighs the pairs itself).  The Y2 kernel does
-// the first pair step as well where it can (y2_pairstep_applicable), otherwise that is the first of two pair-transform
+// the first pair step as well where the plan says so (plan_grad_pairs), otherwise that is the first of two pair-transform
 // launches.  With G the first unpack writes the N^4-addressed SB that comes with it:
 //   n <= 32: the first pair step reads that; a second unpack writes the dense form for Y2, to B2, free until the next
 //            step -- or over SB in B1 when the Y2 kernel is the first pair step as well and writes B2;
@@ -455,29 +420,32 @@ static int gradient_sym8_pairs(const GradCall &x, const double *packed, int64_t 
     prof_stop(pr, st);
     pr = prof_start(EVC_PROF_Y2, st);
     PairTransformArgs pa = grad_first_step(w, n, 1);
-    pa.in_pairs = 1;
-    const bool pairstep = y2_pairstep_applicable(pa, w.K3, sw, cnt);
+    pa.in_pairs = 1;   // (the dense form: what Y2 reads; the plan has the form each step is launched with)
+    const Geo &g = x.g;
+    const GradPairPlan plan = plan_grad_pairs(pa, w.B1, w.K3, sw, cnt, G != nullptr, p64, ip1_s2kl,
+                                              g.geo_period <= 0 || cnt == g.geo_period, pair_knobs());
     const double *sbp = w.B1;
     if (G && !p64) {
-        double *dense = pairstep ? w.B1 : w.B2;
+        double *dense = plan.y2_in_first ? w.B1 : w.B2;
         EVC_TRY(launch_unpack8(packed, spacked, n, dense, sw, nullptr, 0, cnt, 2, st));
         sbp = dense;
     }
-    if (pairstep)
-        EVC_TRY(launch_y2_pairstep(pa, w.K3, w.y2part, sw, cnt, st));
+    if (plan.y2_in_first)
+        EVC_TRY(launch_y2_pairstep(plan.y2, pa, w.K3, w.y2part, sw, cnt, st));
     else
-        EVC_TRY(launch_y2_fused(sbp, w.K3, w.X, sw, n, w.y2part, sw, cnt, st));
+        EVC_TRY(launch_y2_fused(plan.y2, sbp, w.K3, w.X, sw, n, w.y2part, sw, cnt, st));
     prof_stop(pr, st);
-    pa.in_pairs = (!G || p64) ? 1 : 0;
-    if (!pairstep) EVC_TIMED(EVC_PROF_PAIR_TRANSFORM, st, launch_pair_transform(pa, cnt, st));
-    const int nslab = pairstep ? y2_pairstep_slabs(n, cnt) : y2_fused_slabs(n, cnt);
-    if (grad_second_dot_applicable(x, pa, G, p64, ip1_s2kl)) {
-        int ip1_prof = -1;
-        EVC_TRY(grad_second_step_dot(x, pa, &ip1_prof));
-        return grad_tail(x, w.B1, 1, 1, ip1_s2kl, nslab, true, true, ip1_prof);
+    if (!plan.y2_in_first)
+        EVC_TIMED(EVC_PROF_PAIR_TRANSFORM, st, launch_pair_transform(plan.first, plan.first_args, cnt, st));
+    if (plan.dot_in_second) {
+        // the launch belongs to the int2e_ip1 stage's time: grad_tail closes the bracket behind the residual ip1_dh_kernel launch
+        const PairDotArgs dt{g.eri_ip1, w.t2part, g.sip1, sw, ip1_chunks(n)};
+        const int ip1_prof = prof_start(EVC_PROF_IP1, st);
+        EVC_TRY(launch_pair_transform_dot(plan.second, plan.second_args, dt, cnt, st));
+        return grad_tail(x, w.B1, 1, 1, ip1_s2kl, plan.nslab(), true, true, ip1_prof);
     }
-    EVC_TRY(grad_second_step(pa, w, ip1_s2kl ? 1 : 0, cnt, st));
-    return grad_tail(x, w.B1, 1, 1, ip1_s2kl, nslab, true);
+    EVC_TIMED(EVC_PROF_PAIR_TRANSFORM, st, launch_pair_transform(plan.second, plan.second_args, cnt, st));
+    return grad_tail(x, w.B1, 1, 1, ip1_s2kl, plan.nslab(), true);
 }
 
 int phase_gradient(const evc_trdm_set *t, const Geo &g_in, const Out &out, int flags, const Call &c, hipStream_t st) {

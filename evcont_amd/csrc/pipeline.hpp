@@ -9,7 +9,7 @@
 #pragma once
 #include <string.h>
 
-#include "kernels.hpp"
+#include "pair_plan.hpp"
 
 namespace evc {
 

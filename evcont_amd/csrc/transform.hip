@@ -5,10 +5,8 @@
 //   pair_dma.hip does not take)
 // The N^4-sized helpers around them: pack.hip (pack / unpack), y2.hip (K13), ip1.hip (K15).
 // blockIdx.y = geometry of the batch (kernels.hpp).
-#include <stdlib.h>
-
 #include "common.hpp"
-#include "kernels.hpp"
+#include "pair_plan.hpp"
 #include <type_traits>
 
 namespace evc {
@@ -1049,89 +1047,52 @@ __global__ __launch_bounds__(256) void pt_pipe4_kernel(PairTransformArgs a) {
     iteration(std::false_type{}, niter);
 }
 
-int launch_pair_transform(const PairTransformArgs &a_in, int count, hipStream_t st) {
-    if (a_in.n > kPairTransformMaxN) {   // 32 < n <= 64: the symmetric step alone exists (pair64.hip)
-        if (pair64_applicable(a_in)) return launch_pair_transform64(a_in, count, st);
-        set_error("pair transform: n=%d beyond %d needs the symmetric dense-pair form", a_in.n, kPairTransformMaxN);
-        return -1;
-    }
-    PairTransformArgs a = a_in;
-    const int n = a.n;
-    const int npad = (n + 15) / 16 * 16;
-    const int ntq = (n + 7) / 8;
-    constexpr int tpw_env = 4;   // (2/3/5/8 tiles per workgroup measured slower, round 2 and again with ptd_kernel in round 4)
-    // few geometries: keep one tile per workgroup so that there are enough workgroups for the chip
-    a.tiles_per_wg = (count < 4 || tpw_env < 1) ? 1 : (tpw_env > ntq ? ntq : tpw_env);
-    const int ntiles = a.lead_sym ? (n * (n + 1) / 2 + 7) / 8 : n * ntq;
-    const dim3 grid((unsigned)((ntiles + a.tiles_per_wg - 1) / a.tiles_per_wg), (unsigned)count);
-    const size_t stage_rows = a.rs_lower ? (size_t)n * (n + 1) / 2 : (size_t)n * n;
-    // fully symmetric step of the compressed layout's pipeline: the software-pipelined kernel, if two of its workgroups
-    // fit a CU's LDS (n <= 30; EVC_PT_PIPE=0: the phase-alternating kernel below)
-    static const bool pipe_on = !(getenv("EVC_PT_PIPE") && atoi(getenv("EVC_PT_PIPE")) == 0);
-    if (pair_transform_dma_applicable(a, count)) return launch_pair_transform_dma(a, count, st);
-    if (pipe_on && a.lead_sym && a.in_lower && a.rs_lower && a.in_pairs && (npad == 16 || npad == 32)) {
-        const int mode = a.k3 ? -1 : (a.out && a.out_pairs && !a.packed) ? 0 : (a.packed && a.sym8 && !a.out) ? 1 : -1;
-        const size_t npairs = (size_t)n * (n + 1) / 2;
-        const size_t lds = sizeof(double) * ((size_t)4 * kPtRowLen + npairs * 16 + 16);
-        constexpr bool pipe4_on = true;
-        if (pipe4_on && mode >= 0 && count < 4 && npairs >= 8) {
-            // a few geometries: tiles of 4 pairs, one per workgroup (twice the workgroups, half the length)
-            a.tiles_per_wg = 1;
-            const size_t lds4 = sizeof(double) * ((size_t)4 * kPtRowLen + npairs * 8 + 8);
-            const dim3 grid4((unsigned)((npairs + 3) / 4), (unsigned)count);
-#define EVC_PT_PIPE4_CASE(NP_, MODE_) hipLaunchKernelGGL((pt_pipe4_kernel<NP_, MODE_>), grid4, dim3(256), lds4, st, a)
-            if (npad == 16 && mode == 0) EVC_PT_PIPE4_CASE(16, 0);
-            else if (npad == 16) EVC_PT_PIPE4_CASE(16, 1);
-            else if (mode == 0) EVC_PT_PIPE4_CASE(32, 0);
-            else EVC_PT_PIPE4_CASE(32, 1);
-#undef EVC_PT_PIPE4_CASE
-            note_kernel(EVC_PROF_PAIR_TRANSFORM, "pt_pipe4_kernel<%d,%d>", npad, mode);
-            EVC_LAUNCH_CHECK("pair_transform_pipe4");
-            return 0;
-        }
-        if (mode >= 0 && lds <= 80 * 1024) {
-            const dim3 gridp((unsigned)(((npairs + 7) / 8 + a.tiles_per_wg - 1) / a.tiles_per_wg), (unsigned)count);
-#define EVC_PT_PIPE_CASE(NP_, MODE_)                                                                            \
-    do {                                                                                                        \
-        static LdsAttr attr;                                                                                    \
-        if (int rc = allow_dynamic_lds(pt_pipe_kernel<NP_, MODE_>, attr, 160 * 1024, "pair_transform")) return rc; \
-        hipLaunchKernelGGL((pt_pipe_kernel<NP_, MODE_>), gridp, dim3(256), lds, st, a);                         \
-    } while (0)
-            if (npad == 16 && mode == 0) EVC_PT_PIPE_CASE(16, 0);
-            else if (npad == 16) EVC_PT_PIPE_CASE(16, 1);
-            else if (mode == 0) EVC_PT_PIPE_CASE(32, 0);
-            else EVC_PT_PIPE_CASE(32, 1);
-#undef EVC_PT_PIPE_CASE
-            note_kernel(EVC_PROF_PAIR_TRANSFORM, "pt_pipe_kernel<%d,%d>", npad, mode);
-            EVC_LAUNCH_CHECK("pair_transform_pipe");
-            return 0;
-        }
-    }
-    // dense (pair, pair) operand: coalesced row fetch through a wave-private LDS row (EVC_PT_ROWBUF=0: gather)
-    constexpr bool rowbuf_on = true;
-    const bool rowbuf = rowbuf_on && a.in_pairs;
-    const size_t rowbuf_doubles = rowbuf ? (size_t)4 * kPtRowLen + 2 : 0;
-    if (npad == 16) {
-        const size_t lds = sizeof(double) * ((size_t)16 * 16 + stage_rows * 9 + rowbuf_doubles);
-        if (rowbuf) hipLaunchKernelGGL((pt_kernel<16, true>), grid, dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((pt_kernel<16, false>), grid, dim3(256), lds, st, a);
-    } else if (npad == 32) {
-        const size_t lds = sizeof(double) * ((size_t)32 * 48 + stage_rows * 9 + rowbuf_doubles);
-        if (rowbuf) {
-            static LdsAttr attr;
-            if (int rc = allow_dynamic_lds(pt_kernel<32, true>, attr, 160 * 1024, "pair_transform")) return rc;
-            hipLaunchKernelGGL((pt_kernel<32, true>), grid, dim3(256), lds, st, a);
-        } else {
-            static LdsAttr attr;
-            if (int rc = allow_dynamic_lds(pt_kernel<32, false>, attr, 160 * 1024, "pair_transform")) return rc;
-            hipLaunchKernelGGL((pt_kernel<32, false>), grid, dim3(256), lds, st, a);
-        }
-    } else {
-        set_error("pair_transform: n=%d not supported (1..32)", n);
-        return -1;
-    }
-    note_kernel(EVC_PROF_PAIR_TRANSFORM, "pt_kernel<%d,%d>", npad, rowbuf ? 1 : 0);
+// One launcher per kernel family of this file, one function (and LdsAttr) per instantiation; pt_kernel<16> and
+// pt_pipe4_kernel stay within the 64 KB of dynamic LDS a kernel gets unasked.
+using PtLauncher = int(const PairPlan &p, const PairTransformArgs &a, dim3 grid, hipStream_t st);
+template <int NPAD, int ROWBUF>
+static int launch_pt(const PairPlan &p, const PairTransformArgs &a, dim3 grid, hipStream_t st) {
+    static LdsAttr attr;
+    if (NPAD == 32)
+        if (int rc = allow_dynamic_lds(pt_kernel<NPAD, ROWBUF != 0>, attr, 160 * 1024, "pair_transform")) return rc;
+    hipLaunchKernelGGL((pt_kernel<NPAD, ROWBUF != 0>), grid, dim3(256), p.lds, st, a);
     EVC_LAUNCH_CHECK("pair_transform");
+    return 0;
+}
+template <int NPAD, int MODE>
+static int launch_pt_pipe(const PairPlan &p, const PairTransformArgs &a, dim3 grid, hipStream_t st) {
+    static LdsAttr attr;
+    if (int rc = allow_dynamic_lds(pt_pipe_kernel<NPAD, MODE>, attr, 160 * 1024, "pair_transform")) return rc;
+    hipLaunchKernelGGL((pt_pipe_kernel<NPAD, MODE>), grid, dim3(256), p.lds, st, a);
+    EVC_LAUNCH_CHECK("pair_transform_pipe");
+    return 0;
+}
+template <int NPAD, int MODE>
+static int launch_pt_pipe4(const PairPlan &p, const PairTransformArgs &a, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL((pt_pipe4_kernel<NPAD, MODE>), grid, dim3(256), p.lds, st, a);
+    EVC_LAUNCH_CHECK("pair_transform_pipe4");
+    return 0;
+}
+
+int launch_pair_transform(const PairPlan &p, PairTransformArgs a, int count, hipStream_t st) {
+#define EVC_PT_FAMILY(launcher_) {{launcher_<16, 0>, launcher_<16, 1>}, {launcher_<32, 0>, launcher_<32, 1>}}
+    static PtLauncher *const launcher[3][2][2] = {EVC_PT_FAMILY(launch_pt), EVC_PT_FAMILY(launch_pt_pipe),
+                                                  EVC_PT_FAMILY(launch_pt_pipe4)};
+#undef EVC_PT_FAMILY
+    a.tiles_per_wg = p.tiles_per_wg;
+    switch (p.kernel) {
+        case kPt: case kPtPipe: case kPtPipe4: break;
+        case kPtd: return launch_pair_transform_dma(p, a, count, st);
+        case kPt64: return launch_pair_transform64(p, a, count, st);
+        default:   // no kernel takes the step (beyond 32 orbitals the symmetric step alone exists: pair64.hip)
+            if (a.n > kPairTransformMaxN)
+                set_error("pair transform: n=%d beyond %d needs the symmetric dense-pair form", a.n, kPairTransformMaxN);
+            else
+                set_error("pair_transform: n=%d not supported (1..32)", a.n);
+            return -1;
+    }
+    EVC_TRY(launcher[p.kernel - kPt][p.t[0] == 32][p.t[1]](p, a, dim3(p.grid_x, (unsigned)count), st));
+    note_kernel(EVC_PROF_PAIR_TRANSFORM, "%s", pair_plan_name(p));
     return 0;
 }
 

@@ -1,10 +1,8 @@
 // K13: Y2 = K3 . Gs contraction of the Loewdin-response gradient (gradients_loewdin.py:210-222), the split-K MFMA
 // kernels for the dense layouts and the fused pair-block kernel of the compressed pipeline (N <= 32; the LDS-DMA
 // variant for 17 <= N <= 30 lives in pair_dma.hip).  blockIdx.y = geometry of the batch (kernels.hpp).
-#include <stdlib.h>
-
 #include "common.hpp"
-#include "kernels.hpp"
+#include "pair_plan.hpp"
 
 namespace evc {
 
@@ -15,17 +13,6 @@ __device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 // Both operands are [k][n] row-major, so each MFMA fragment load is 16 contiguous doubles.
-// number of K slabs = partial results per geometry (fixed for the life of the process: it sizes the workspace)
-static int y2_slab_count() {
-    static const int v = [] {
-        return 64;
-    }();
-    return v;
-}
-int y2_slabs(int) { return y2_slab_count(); }
-// slabs the partial buffer of the pipeline is sized for (the fused kernel below uses up to that many workgroups)
-// (beyond 32 orbitals y2_64_kernel deals the pairs of ONE geometry to a full round of the chip)
-int y2_slab_capacity(int n) { return n > kPairTransformMaxN ? 256 : (y2_slab_count() > 128 ? y2_slab_count() : 128); }
 
 template <int NT>
 __global__ __launch_bounds__(256) void y2_kernel(const double *__restrict__ GsT, const double *__restrict__ K3,
@@ -305,79 +292,56 @@ __global__ __launch_bounds__(256) void y2_fused_kernel(const double *__restrict_
     }
 }
 
-// 8-pair tiles per workgroup: 4 for batches (as the pair transform), 1 for a few geometries (enough workgroups for the
-// chip), never more workgroups than the partial buffer has slabs
-static int y2_fused_ppt(int count) { return count < 4 ? 4 : 8; }   // pairs per tile: 4 (one matrix per wave) for a few geometries
-static int y2_fused_tiles(int n, int count) {
-    const int ppt = y2_fused_ppt(count);
-    const int ntiles = (n * (n + 1) / 2 + ppt - 1) / ppt;
-    int t = count < 4 ? 1 : 4;
-    while ((ntiles + t - 1) / t > y2_slab_capacity(n)) ++t;
-    return t;
-}
-int y2_fused_slabs(int n, int count) {
-    if (y2_64_applicable(n)) return y2_64_slabs(n, count);
-    const int ppt = y2_fused_ppt(count);
-    const int ntiles = (n * (n + 1) / 2 + ppt - 1) / ppt, t = y2_fused_tiles(n, count);
-    return (ntiles + t - 1) / t;
-}
-int launch_y2_fused(const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial,
+int launch_y2_fused(const Y2Plan &p, const double *SB, const double *M1, const double *X, int64_t sX, int n, double *partial,
                     int64_t sws, int count, hipStream_t st) {
-    if (y2_64_applicable(n)) return launch_y2_64(SB, M1, X, sX, n, partial, sws, count, st);
-    if (y2_dma_applicable(n))
-        return launch_y2_dma(SB, M1, X, sX, n, partial, sws, count, y2_fused_slabs(n, count), y2_fused_tiles(n, count),
-                             y2_fused_ppt(count), st);
-    const dim3 grid((unsigned)y2_fused_slabs(n, count), (unsigned)count);
-    const int npad = (n + 15) / 16 * 16;
-    const size_t rows = sizeof(double) * (size_t)8 * kPtRowLen;
-    if (npad == 16) {
-        const size_t redb = sizeof(double) * 4 * 16 * 17;
-        hipLaunchKernelGGL(y2_fused_kernel<16>, grid, dim3(256), rows > redb ? rows : redb, st, SB, M1, X, sX, n, partial,
-                           sws, y2_fused_tiles(n, count), y2_fused_ppt(count));
-    } else if (npad == 32) {
-        const size_t redb = sizeof(double) * 4 * 32 * 33;
-        hipLaunchKernelGGL(y2_fused_kernel<32>, grid, dim3(256), rows > redb ? rows : redb, st, SB, M1, X, sX, n, partial,
-                           sws, y2_fused_tiles(n, count), y2_fused_ppt(count));
-    } else {
-        set_error("y2_fused: n=%d not supported (1..32)", n);
-        return -1;
+    const dim3 grid((unsigned)p.slabs, (unsigned)count);
+    switch (p.kernel) {
+        case kY2Wide: EVC_TRY(launch_y2_64(p, SB, M1, X, sX, n, partial, sws, count, st)); break;
+        case kY2d: EVC_TRY(launch_y2_dma(p, SB, M1, X, sX, n, partial, sws, count, st)); break;
+        case kY2Fused:
+            if (p.t == 16)
+                hipLaunchKernelGGL(y2_fused_kernel<16>, grid, dim3(256), p.lds, st, SB, M1, X, sX, n, partial, sws,
+                                   p.tiles_per_wg, p.ppt);
+            else
+                hipLaunchKernelGGL(y2_fused_kernel<32>, grid, dim3(256), p.lds, st, SB, M1, X, sX, n, partial, sws,
+                                   p.tiles_per_wg, p.ppt);
+            EVC_LAUNCH_CHECK("y2_fused");
+            break;
+        default: set_error("y2_fused: n=%d not supported (1..32)", n); return -1;
     }
-    note_kernel(EVC_PROF_Y2, "y2_fused_kernel<%d>", npad);
-    EVC_LAUNCH_CHECK("y2_fused");
+    note_kernel(EVC_PROF_Y2, "%s", y2_plan_name(p));
     return 0;
 }
 
 int launch_y2_sb(const double *SB, const double *K3, int n, double *partial, int64_t sws, int count, hipStream_t st) {
+    const Y2Plan p = plan_y2(kY2FromSb, n, count, pair_knobs());
     const int64_t ktot = (int64_t)n * n * n;
-    const int nt = (n + 15) / 16;
-    const dim3 grid((unsigned)y2_slab_count(), (unsigned)count, nt > 4 ? 4u : 1u);   // n > 64: four 64 x 64 quadrants
-    switch (nt) {
+    const dim3 grid((unsigned)p.slabs, (unsigned)count, p.grid_z);
+    switch (p.t) {   // (kY2Unsupported: 0)
         case 1: hipLaunchKernelGGL(y2_sb_kernel<1>, grid, dim3(256), 0, st, SB, K3, n, ktot, partial, sws); break;
         case 2: hipLaunchKernelGGL(y2_sb_kernel<2>, grid, dim3(256), 0, st, SB, K3, n, ktot, partial, sws); break;
         case 3: hipLaunchKernelGGL(y2_sb_kernel<3>, grid, dim3(256), 0, st, SB, K3, n, ktot, partial, sws); break;
-        case 4: case 5: case 6: case 7: case 8:
-            hipLaunchKernelGGL(y2_sb_kernel<4>, grid, dim3(256), 0, st, SB, K3, n, ktot, partial, sws); break;
+        case 4: hipLaunchKernelGGL(y2_sb_kernel<4>, grid, dim3(256), 0, st, SB, K3, n, ktot, partial, sws); break;
         default: set_error("y2: n=%d not supported by the gradient path (1..128)", n); return -1;
     }
     EVC_LAUNCH_CHECK("y2_sb");
-    note_kernel(EVC_PROF_Y2, "y2_sb_kernel<%d>", nt > 4 ? 4 : nt);
+    note_kernel(EVC_PROF_Y2, "%s", y2_plan_name(p));
     return 0;
 }
 
 int launch_y2(const double *GsT, const double *K3, int n, double *partial, int64_t sws, int count, hipStream_t st) {
+    const Y2Plan p = plan_y2(kY2FromGsT, n, count, pair_knobs());
     const int64_t ktot = (int64_t)n * n * n;
-    const int nt = (n + 15) / 16;
-    const dim3 grid((unsigned)y2_slab_count(), (unsigned)count, nt > 4 ? 4u : 1u);   // n > 64: four 64 x 64 quadrants
-    switch (nt) {
+    const dim3 grid((unsigned)p.slabs, (unsigned)count, p.grid_z);
+    switch (p.t) {   // (kY2Unsupported: 0)
         case 1: hipLaunchKernelGGL(y2_kernel<1>, grid, dim3(256), 0, st, GsT, K3, n, ktot, partial, sws); break;
         case 2: hipLaunchKernelGGL(y2_kernel<2>, grid, dim3(256), 0, st, GsT, K3, n, ktot, partial, sws); break;
         case 3: hipLaunchKernelGGL(y2_kernel<3>, grid, dim3(256), 0, st, GsT, K3, n, ktot, partial, sws); break;
-        case 4: case 5: case 6: case 7: case 8:
-            hipLaunchKernelGGL(y2_kernel<4>, grid, dim3(256), 0, st, GsT, K3, n, ktot, partial, sws); break;
+        case 4: hipLaunchKernelGGL(y2_kernel<4>, grid, dim3(256), 0, st, GsT, K3, n, ktot, partial, sws); break;
         default: set_error("y2: n=%d not supported by the gradient path (1..128)", n); return -1;
     }
     EVC_LAUNCH_CHECK("y2");
-    note_kernel(EVC_PROF_Y2, "y2_kernel<%d>", nt > 4 ? 4 : nt);
+    note_kernel(EVC_PROF_Y2, "%s", y2_plan_name(p));
     return 0;
 }
 

@@ -38,6 +38,11 @@ L_ONE32 = "loewdin_kernel part=0"
 L_SIDE64 = "loewdin_ns64_kernel part=1; side stream: loewdin_big_kernel part=2"   # 32 < n <= 64, < 12 geometries
 L_BIG = "loewdin_big_kernel part=0"                                     # n > 64, or >= 12 geometries beyond 32 orbitals
 
+# the fused gradient-side route (17 <= n <= 30, packed inputs, >= 4 geometries, one slot per geometry, no 2-RDM output)
+Y2_PAIRSTEP = "y2d_kernel<1> pairstep"   # Y2 inside the first pair step
+PT_DOT = "ptd_kernel<0> +ip1"            # the int2e_ip1 dot inside the second ...
+IP1_REST = "ip1_dh_kernel<8> pairs (dot in ptd)"   # ... and what is left to ip1_dh_kernel
+
 
 def case(id, n, T, A, G, layout, expect, packed=False, energy_only=False, warm=False, nroots=1, api="batch",
          keep=False, env=None, covered_by=None, expect_grad=None, pairs=None):
@@ -93,16 +98,16 @@ CASES = [
                    "ip1_dh_kernel<8> pairs", "y2d_kernel", "unpack8_prep_kernel", L_RIDE,
                    "subspace_loewdin_kernel few=1")),
     case("n17_sym8_packed_G4", 17, 3, 2, 4, "sym8", packed=True,
-         expect=st("gemv_rows_wr_kernel<8,4,2> G=4", "gemv_cols_rs_kernel<4>", "ptd_kernel<0>",
-                   "ip1_dh_kernel<8> pairs", "y2d_kernel", "unpack8_prep_kernel", L_RIDE,
+         expect=st("gemv_rows_wr_kernel<8,4,2> G=4", "gemv_cols_rs_kernel<4>", PT_DOT,
+                   IP1_REST, Y2_PAIRSTEP, "unpack8_prep_kernel", L_RIDE,
                    "subspace_loewdin_kernel few=1")),
     case("n29_sym8_packed_G8", 29, 2, 2, 8, "sym8", packed=True,
-         expect=st("gemv_rows_wr_kernel<4,8,4> G=8", "gemv_cols_rs_kernel<8>", "ptd_kernel<0>",
-                   "ip1_dh_kernel<8> pairs", "y2d_kernel", "unpack8_prep_kernel", L_RIDE,
+         expect=st("gemv_rows_wr_kernel<4,8,4> G=8", "gemv_cols_rs_kernel<8>", PT_DOT,
+                   IP1_REST, Y2_PAIRSTEP, "unpack8_prep_kernel", L_RIDE,
                    "subspace_loewdin_kernel few=1")),
     case("n30_sym8_packed_G9", 30, 2, 2, 9, "sym8", packed=True,
-         expect=st("gemv_rows_kernel<8,1> G=1", "gemv_cols_rs_kernel<1>", "ptd_kernel<0>", "ip1_dh_kernel<8> pairs",
-                   "y2d_kernel", "unpack8_prep_kernel", L_RIDE, "subspace_loewdin_kernel few=1")),
+         expect=st("gemv_rows_kernel<8,1> G=1", "gemv_cols_rs_kernel<1>", PT_DOT, IP1_REST,
+                   Y2_PAIRSTEP, "unpack8_prep_kernel", L_RIDE, "subspace_loewdin_kernel few=1")),
     # (n = 31, 32: the software-pipelined pair step needs more than 80 KB of LDS -> the phase-alternating pt_kernel)
     case("n31_sym8_packed_G4", 31, 2, 2, 4, "sym8", packed=True,
          expect=st("gemv_rows_wr_kernel<8,4,2> G=4", "gemv_cols_rs_kernel<4>", "pt_kernel<32,1>",
@@ -268,13 +273,28 @@ KNOB_CASES = [
                    "unpack8_prep_kernel", L_ONE32, "subspace_kernel few=0")),
     case("knob_rows_mfma_pipe", 30, 20, 2, 32, "sym8", packed=True, env={"EVC_ROWS_LDS": "0"},
          covered_by=_V + "[env7]",
-         expect=st("gemv_rows_mfma_pipe_kernel", "gemv_cols", "ptd_kernel<0>", "ip1_dh_kernel<8> pairs", "y2d_kernel",
+         expect=st("gemv_rows_mfma_pipe_kernel", "gemv_cols", PT_DOT, IP1_REST, Y2_PAIRSTEP,
                    "unpack8_prep_kernel", L_RIDE, "subspace_loewdin_kernel few=1")),
     case("knob_rows_lds_nt", 10, 20, 2, 32, "sym8", packed=True,
          env={"EVC_ROWS_LDS_MINCOLS": "1", "EVC_ROWS_LDS_NT": "7"}, covered_by=_V + "[env11]",
          expect=st("gemv_rows_lds_kernel", "gemv_cols", "pt_pipe_kernel<16,0>", "ip1_dh_kernel<8> pairs",
                    "y2_fused_kernel<16>", "unpack8_prep_kernel", L_RIDE, "subspace_loewdin_kernel few=1")),
     case("knob_cols_mfma", 30, 20, 2, 32, "sym8", packed=True, env={"EVC_COLS_LDS": "0"}, covered_by=_V + "[env14]",
-         expect=st("gemv_rows_lds_kernel", "gemv_cols_mfma", "ptd_kernel<0>", "ip1_dh_kernel<8> pairs", "y2d_kernel",
+         expect=st("gemv_rows_lds_kernel", "gemv_cols_mfma", PT_DOT, IP1_REST, Y2_PAIRSTEP,
+                   "unpack8_prep_kernel", L_RIDE, "subspace_loewdin_kernel few=1")),
+    # one of the two fused steps off: the other stays (n = 17, 4 geometries: the smallest shape on the fused route).  These two
+    # rows hold the WHOLE pair_transform / ip1 / y2 records (a prefix would also match the fused record): the covering
+    # tests compare them with == in their knob-off process (knob_row)
+    case("knob_y2_pairstep_off", 17, 3, 2, 4, "sym8", packed=True, env={"EVC_Y2_PAIRSTEP": "0"},
+         covered_by="tests.test_gpu_y2_pairstep::test_knob_off_agrees",
+         expect=st("gemv_rows_", "gemv_cols", PT_DOT, IP1_REST, "y2d_kernel", "unpack8_prep_kernel", L_RIDE,
+                   "subspace_loewdin_kernel few=1")),
+    case("knob_ip1_pairstep_off", 17, 3, 2, 4, "sym8", packed=True, env={"EVC_IP1_PAIRSTEP": "0"},
+         covered_by="tests.test_gpu_ip1_pairstep::test_batch_against_oracle_and_knob_off",
+         expect=st("gemv_rows_", "gemv_cols", "ptd_kernel<0>", "ip1_dh_kernel<8> pairs", Y2_PAIRSTEP,
                    "unpack8_prep_kernel", L_RIDE, "subspace_loewdin_kernel few=1")),
 ]
+
+
+def knob_row(id):
+    return next(c for c in KNOB_CASES if c["id"] == id)

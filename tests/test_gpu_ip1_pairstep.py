@@ -22,6 +22,7 @@ if __name__ == "__main__":
     sys.path.insert(0, REPO)
 import torch
 
+from dispatch_table import knob_row
 from evcont_amd.synthetic import make_ao_arrays, make_trdms, pack_rows
 from oracle import evcont_oracle as orc
 
@@ -113,8 +114,7 @@ def knob_off_forces(tmp_path_factory):
     which also asserts that its records do not name the fused route; run once."""
     if not _knob_off:
         out = str(tmp_path_factory.mktemp("ip1_pairstep_off"))
-        e = dict(os.environ)
-        e["EVC_IP1_PAIRSTEP"] = "0"
+        e = {**os.environ, "EVC_IP1_PAIRSTEP": "0"}
         r = subprocess.run([sys.executable, os.path.abspath(__file__), out], cwd=REPO, env=e, capture_output=True,
                            text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -191,4 +191,8 @@ if __name__ == "__main__":   # the EVC_IP1_PAIRSTEP=0 leg of test_batch_against_
             assert_fused(False)
             assert record("pair_transform").startswith("ptd_kernel<0>"), record("pair_transform")
             assert record("ip1").startswith("ip1_dh_kernel<8> pairs"), record("ip1")
+            # the whole records of the knob's dispatch-table row: the storing second step, Y2 still in the first
+            want_ = knob_row("knob_ip1_pairstep_off")["expect"]
+            for stage_ in ("pair_transform", "ip1", "y2"):
+                assert record(stage_) == want_[stage_], (stage_, record(stage_))
             np.save(os.path.join(sys.argv[1], f"g_{n_}_{G_}.npy"), g_)

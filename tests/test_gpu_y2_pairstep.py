@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from dispatch_table import knob_row
 from evcont_amd.synthetic import make_ao_arrays, make_trdms, pack_rows
 from oracle import evcont_oracle as orc
 
@@ -95,6 +96,9 @@ def test_batch_against_oracle(n, T, G):
     assert rec.startswith(expected_y2_record()), rec
     if os.environ.get("EVC_Y2_PAIRSTEP") == "0":
         assert not rec.startswith("y2d_kernel<1>"), rec
+        # the whole records of the knob's dispatch-table row: Y2 alone, the int2e_ip1 dot still in the second step
+        want = knob_row("knob_y2_pairstep_off")["expect"]
+        assert (rec, pt_record()) == (want["y2"], want["pair_transform"]), (rec, pt_record())
     assert pt_record().startswith("ptd_kernel<0>"), pt_record()
     check_oracle(n, T, G, E, g)
     out = os.environ.get("EVC_Y2_PAIRSTEP_DUMP")

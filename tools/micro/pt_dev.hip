@@ -11,7 +11,7 @@
 
 #include <vector>
 
-#include "kernels.hpp"
+#include "pair_plan.hpp"
 #ifdef PT_DEV_INLINE_KERNEL   // the kernel under development compiled into the harness (variants by -D flags)
 #include "pair_dma.hip"
 #endif
@@ -82,7 +82,12 @@ int main(int argc, char **argv) {
     pn.out = d_out_new;
     pn.sout = (int64_t)out_new_sz;
     pn.out_ld = ldp;
-    pn.tiles_per_wg = getenv("PT_TILES") ? atoi(getenv("PT_TILES")) : 4;
+    // the plan of the library, or PT_TILES 8-pair tiles per workgroup
+    evc::PairPlan plan = evc::plan_pair_step(pn, G, evc::pair_knobs());
+    if (getenv("PT_TILES")) {
+        plan.tiles_per_wg = atoi(getenv("PT_TILES"));
+        plan.grid_x = (unsigned)((((n * (n + 1) / 2 + 7) / 8) + plan.tiles_per_wg - 1) / plan.tiles_per_wg);
+    }
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
@@ -107,9 +112,9 @@ int main(int argc, char **argv) {
         printf("%-28s best %.2f us   mean %.2f us per launch\n", name, 1e3 * best / reps, 1e3 * sum / 5 / reps);
     };
     time_it([&] { return evc::launch_pair_transform(po, G, 0); }, "pt_pipe_kernel (old)");
-    time_it([&] { return evc::launch_pair_transform_dma(pn, G, 0); }, "ptd_kernel (new)");
+    time_it([&] { return evc::launch_pair_transform(plan, pn, G, 0); }, "ptd_kernel (new)");
     time_it([&] { return evc::launch_pair_transform(po, G, 0); }, "pt_pipe_kernel (old)");
-    time_it([&] { return evc::launch_pair_transform_dma(pn, G, 0); }, "ptd_kernel (new)");
+    time_it([&] { return evc::launch_pair_transform(plan, pn, G, 0); }, "ptd_kernel (new)");
 
     std::vector<double> o_old(G * out_old_sz), o_new(G * out_new_sz);
     CK(hipMemcpy(o_old.data(), d_out_old, sizeof(double) * o_old.size(), hipMemcpyDeviceToHost));
