@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .fci_small import SmallFCI, _strings
+from .fci_small import SmallFCI, _strings, resolve_spin_target, spin_constant
 
 DEPENDENT = 1e-3     # a correction that keeps less than this of its norm through the projections is dropped
 DENOM_FLOOR = 1e-8   # |hdiag - theta| is floored here, keeping its sign
@@ -30,10 +30,13 @@ def occupations(norb: int, nocc: int) -> np.ndarray:
     return ((strs[:, None] >> np.arange(norb)[None, :]) & 1).astype(np.float64)
 
 
-def hdiag_numpy(h1, h2, norb: int, nelec: Tuple[int, int]) -> np.ndarray:
+def hdiag_numpy(h1, h2, norb: int, nelec: Tuple[int, int], spin_penalty: float = 0.0,
+                spin_target: float = 0.0) -> np.ndarray:
     """``<I|H|I>`` of ``H = sum h'_pq E_pq + 1/2 sum (pq|rs) E_pq E_rs`` (``SmallFCI.contract``), ``(na, nb)``; no
     permutation symmetry of ``h2`` assumed:
-    ``sum_p h'_pp n_p + 1/2 sum_pr (pp|rr) n_p n_r + 1/2 sum_{p != q} (pq|qp) sum_spin n_p,spin (1 - n_q,spin)``."""
+    ``sum_p h'_pp n_p + 1/2 sum_pr (pp|rr) n_p n_r + 1/2 sum_{p != q} (pq|qp) sum_spin n_p,spin (1 - n_q,spin)``.
+    A non-zero ``spin_penalty`` adds ``spin_penalty (<I|S^2|I> - spin_target)``, ``<I|S^2|I> = Sz (Sz + 1) + n_beta`` less
+    the doubly occupied orbitals of ``I``: the diagonal of the operator ``SmallFCI(spin_penalty=...)`` contracts."""
     h1 = np.asarray(h1, dtype=np.float64).reshape(norb, norb)
     h2 = np.asarray(h2, dtype=np.float64).reshape(norb, norb, norb, norb)
     hp = np.diag(h1) - 0.5 * np.einsum("prrp->p", h2)
@@ -44,7 +47,10 @@ def hdiag_numpy(h1, h2, norb: int, nelec: Tuple[int, int]) -> np.ndarray:
     out = n @ hp + 0.5 * np.einsum("abp,pr,abr->ab", n, J, n)
     ea = 0.5 * np.einsum("ap,pq,aq->a", oa, K, 1.0 - oa)
     eb = 0.5 * np.einsum("bp,pq,bq->b", ob, K, 1.0 - ob)
-    return out + ea[:, None] + eb[None, :]
+    out = out + ea[:, None] + eb[None, :]
+    if spin_penalty != 0.0:
+        out = out + spin_penalty * ((spin_constant(nelec) - spin_target) - oa @ ob.T)
+    return out
 
 
 # ---- vector operations -----------------------------------------------------------------
@@ -105,7 +111,9 @@ class NumpyOps(DavidsonOps):
     def prepare(self, nroots, max_space):
         self.sets = {"V": np.zeros((max_space, self.dim)), "W": np.zeros((max_space, self.dim)),
                      "S": np.zeros((2 * nroots, self.dim))}
-        self.hdiag = hdiag_numpy(self.h1, self.h2, self.norb, self.nelec).reshape(-1)
+        shift = self.solver.spin_penalty
+        target = resolve_spin_target(self.solver.spin_target, self.nelec) if shift != 0.0 else 0.0
+        self.hdiag = hdiag_numpy(self.h1, self.h2, self.norb, self.nelec, shift, target).reshape(-1)
 
     def lowest(self, n):
         return [int(i) for i in np.argsort(self.hdiag, kind="stable")[:n]]

@@ -12,6 +12,9 @@ set of ``resident.ResidentFCI_EVCont_obj``), and ``transform_ci(ci, nelec, u)``
 ``FCI_EVCont_obj(cisolver=DeviceFCI(), cibasis="OAO")``, or ``cibasis="canonical"`` to solve in the Hartree-Fock basis,
 where the Davidson solver's diagonal preconditioner works best near equilibrium.
 
+``DeviceFCI(spin_penalty=0.2)`` holds the roots to one multiplicity (``H + 0.2 (S^2 - S(S+1))``, PySCF's ``fix_spin_``;
+``csrc/fci_spin.hip``) and ``spin_square(ci, norb, nelec)`` reports ``<S^2>`` of a state.
+
 Limits: ``norb <= 16``, real CI vectors, any ``(n_alpha, n_beta)``.  By default the eigensolver iteration of ``kernel``
 stays on the host (``scipy.sparse.linalg.eigsh``); every matrix-vector product it asks for is a device sigma vector that
 is uploaded and downloaded.  ``DeviceFCI(eigensolver="davidson")`` runs a block Davidson (``fci_davidson.py``) whose
@@ -31,7 +34,7 @@ from scipy.sparse.linalg import LinearOperator, eigsh
 from . import _lib
 from .fci_davidson import DavidsonOps, davidson
 from ._lib import EvcontHipError, check
-from .fci_small import _strings
+from .fci_small import _strings, multiplicity_of, resolve_spin_target, unshift_roots
 from .fci_tables import MAX_ORB, packed_table
 
 F64 = torch.float64
@@ -56,6 +59,7 @@ class _DeviceOps(DavidsonOps):
         self.nsigma = 0
         self.sets = {}
         self.hd = None
+        self.shift, self.target = fci._pen
 
     def prepare(self, nroots, max_space):
         lib, dim = self.lib, self.dim
@@ -86,6 +90,9 @@ class _DeviceOps(DavidsonOps):
         check(lib.evc_fci_hdiag(self.norb, self.na, self.nb, self.dta.data_ptr(), self.dtb.data_ptr(), self.dh1.data_ptr(),
                                 self.dh2.data_ptr(), self.hd.data_ptr(), self.ws.data_ptr(), wsb, self.fci._stream()),
               "evc_fci_hdiag")
+        if self.shift != 0.0:
+            check(lib.evc_fci_spin_diag(self.norb, self.na, self.nb, self.dta.data_ptr(), self.dtb.data_ptr(), self.shift,
+                                        self.target, self.hd.data_ptr(), self.fci._stream()), "evc_fci_spin_diag")
 
     def _row(self, name, row):
         return self.sets[name].data_ptr() + 8 * row * self.dim
@@ -107,6 +114,9 @@ class _DeviceOps(DavidsonOps):
         check(self.lib.evc_fci_sigma(self.norb, self.na, self.nb, self.dta.data_ptr(), self.dtb.data_ptr(),
                                      self.dh1.data_ptr(), self.dh2.data_ptr(), self._row("V", row), self._row("W", row),
                                      self.fci._ws.data_ptr(), self.grant, self.fci._stream()), "evc_fci_sigma")
+        if self.shift != 0.0:
+            self.fci._add_penalty(self.lib, self.dta, self.dtb, self.na, self.nb, self.norb, self.shift, self.target,
+                                  self._row("V", row), self._row("W", row))
 
     def dots(self, x, x0, nx, y, y0, ny):
         check(self.lib.evc_fci_dots(self.dim, self._row(x, x0), self.dim, nx, self._row(y, y0), self.dim, ny,
@@ -145,16 +155,23 @@ class DeviceFCI:
     ``eigsh`` on the host beyond.  ``eigensolver="davidson"``: block Davidson with resident vectors at every size, a root
     converged when its residual 2-norm is at most ``conv_tol``; the basis holds at most ``max_space`` vectors (default
     ``8 nroots + 12``) and ``2 max_space + 2 nroots + 1`` vectors are allocated, once per shape; ``converged`` is False,
-    with a warning, when ``max_cycle`` iterations did not suffice."""
+    with a warning, when ``max_cycle`` iterations did not suffice.
+
+    ``spin_penalty`` / ``spin_target`` as in ``SmallFCI``: with a non-zero penalty every sigma vector, on all three
+    routes, is ``H c + spin_penalty (S^2 c - spin_target c)`` (``evc_fci_spin_apply`` on the row ``evc_fci_sigma`` just
+    wrote, csrc/fci_spin.hip), the Davidson diagonal carries the same penalty, and ``kernel`` returns energies of H with
+    the measured ``<S^2>`` of its roots in ``spin_squares``.  With the default 0 no such kernel is launched."""
 
     def __init__(self, device=None, tol: float = 1e-13, workspace_bytes: Optional[int] = None, dense_limit: int = 1500,
                  eigensolver: str = "host", conv_tol: float = 1e-10, max_space: Optional[int] = None,
-                 max_cycle: int = 300):
+                 max_cycle: int = 300, spin_penalty: float = 0.0, spin_target: Optional[float] = None):
         if eigensolver not in EIGENSOLVERS:
             raise ValueError(f"DeviceFCI: eigensolver={eigensolver!r}, expected one of {EIGENSOLVERS}")
         self.eigensolver = eigensolver
         self.conv_tol, self.max_space, self.max_cycle = conv_tol, max_space, max_cycle
         self.davidson_info = None
+        self.spin_penalty, self.spin_target, self.spin_squares = float(spin_penalty), spin_target, None
+        self._pen = (0.0, 0.0)  # (penalty, S(S+1) target) of the shape last set up
         self._basis = None
         self.tol = tol
         self.dense_limit = dense_limit
@@ -209,6 +226,7 @@ class DeviceFCI:
             dsb = dsa if nelec[1] == nelec[0] else torch.tensor(_strings(norb, nelec[1]), dtype=torch.int32, device=dev)
             self._masks[key] = (dsa, dsb)
         dta, dtb, na, nb, grant = self._tables[key]
+        self._pen = self._penalty(nelec)            # a spin_target that is no S(S+1) is refused here (ValueError)
         if self._ws is None or self._ws.numel() < grant:
             self._ws = None
             self._ws = torch.empty(grant, dtype=torch.uint8, device=self._dev())
@@ -258,7 +276,54 @@ class DeviceFCI:
         check(lib.evc_fci_sigma(norb, na, nb, dta.data_ptr(), dtb.data_ptr(), dh1.data_ptr(), dh2.data_ptr(),
                                 dc.data_ptr(), out.data_ptr(), self._ws.data_ptr(), grant, self._stream()),
               "evc_fci_sigma")
+        shift, target = self._pen
+        if shift != 0.0:
+            self._add_penalty(lib, dta, dtb, na, nb, norb, shift, target, dc.data_ptr(), out.data_ptr())
         return out
+
+    def _penalty(self, nelec) -> Tuple[float, float]:
+        """``(spin_penalty, S(S+1) target)``; the target is resolved, and a wrong one refused, only with a penalty."""
+        shift = float(self.spin_penalty)
+        return (shift, resolve_spin_target(self.spin_target, nelec)) if shift != 0.0 else (0.0, 0.0)
+
+    def _add_penalty(self, lib, dta, dtb, na, nb, norb, shift, target, c_ptr, out_ptr) -> None:
+        """``out += shift (S^2 c - target c)`` on the device."""
+        check(lib.evc_fci_spin_apply(norb, na, nb, dta.data_ptr(), dtb.data_ptr(), c_ptr, shift, target, 1.0, out_ptr,
+                                     self._stream()), "evc_fci_spin_apply")
+
+    def spin_square(self, ci, norb, nelec):
+        """``(<S^2>, multiplicity)`` of a normalised CI vector, a host array or a device tensor
+        (``SmallFCI.spin_square``): one ``evc_fci_spin_apply`` and one ``evc_fci_dots``."""
+        nelec = _nelec(nelec)
+        lib, dta, dtb, na, nb, _ = self._setup(norb, nelec)
+        dc = self._upload(ci, na, nb, cache=False).reshape(-1)
+        dim = na * nb
+        wsb = lib.evc_fci_solve_workspace_bytes(norb, na, nb, 1)
+        if wsb == 0:
+            check(-1, "evc_fci_solve_workspace_bytes")
+        if self._ws.numel() < wsb:
+            self._ws = None
+            self._ws = torch.empty(wsb, dtype=torch.uint8, device=self._dev())
+        s2c = torch.empty(dim, dtype=F64, device=dc.device)
+        one = torch.empty(1, dtype=F64, device=dc.device)
+        check(lib.evc_fci_spin_apply(norb, na, nb, dta.data_ptr(), dtb.data_ptr(), dc.data_ptr(), 1.0, 0.0, 0.0,
+                                     s2c.data_ptr(), self._stream()), "evc_fci_spin_apply")
+        check(lib.evc_fci_dots(dim, dc.data_ptr(), dim, 1, s2c.data_ptr(), dim, 1, one.data_ptr(), self._ws.data_ptr(),
+                               wsb, self._stream()), "evc_fci_dots")
+        ss = float(one.item())
+        return ss, float(multiplicity_of(ss))
+
+    def _finish(self, w, vecs, norb, nelec, nroots):
+        """What ``kernel`` returns: with a penalty, the energies of H from the shifted values and the measured <S^2>."""
+        w = [float(x) for x in w[:nroots]]
+        self.spin_squares = None
+        shift, target = self._penalty(nelec)
+        if shift != 0.0:
+            self.spin_squares = [self.spin_square(x, norb, nelec)[0] for x in vecs]
+            w = unshift_roots(w, self.spin_squares, shift, target)
+        if nroots == 1:
+            return w[0], vecs[0]
+        return w, vecs
 
     def kernel(self, h1, h2, norb, nelec, nroots: int = 1, ci0=None, **_):
         """Lowest ``nroots`` eigenpairs; scalars/array for ``nroots == 1``, lists otherwise; sign convention of
@@ -275,7 +340,7 @@ class DeviceFCI:
         dh2 = torch.from_numpy(np.ascontiguousarray(h2, dtype=np.float64).reshape(norb ** 4)).to(dev)
 
         if self.eigensolver == "davidson":
-            return self._davidson(lib, dta, dtb, na, nb, grant, norb, dh1, dh2, nroots, ci0)
+            return self._davidson(lib, dta, dtb, na, nb, grant, norb, dh1, dh2, nroots, ci0, nelec)
 
         def mv(v):
             dc = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64).reshape(-1)).to(dev)
@@ -302,11 +367,9 @@ class DeviceFCI:
             x = v[:, k].copy()
             x *= np.sign(x[np.argmax(np.abs(x))])
             vecs.append(x.reshape(na, nb))
-        if nroots == 1:
-            return float(w[0]), vecs[0]
-        return [float(x) for x in w[:nroots]], vecs
+        return self._finish(w, vecs, norb, nelec, nroots)
 
-    def _davidson(self, lib, dta, dtb, na, nb, grant, norb, dh1, dh2, nroots, ci0):
+    def _davidson(self, lib, dta, dtb, na, nb, grant, norb, dh1, dh2, nroots, ci0, nelec):
         ops = _DeviceOps(self, lib, dta, dtb, na, nb, grant, norb, dh1, dh2)
         try:
             w, v, self.converged, self.davidson_info = davidson(
@@ -318,9 +381,7 @@ class DeviceFCI:
             x = v[k] / np.linalg.norm(v[k])
             x *= np.sign(x[np.argmax(np.abs(x))])
             vecs.append(x.reshape(na, nb))
-        if nroots == 1:
-            return float(w[0]), vecs[0]
-        return [float(x) for x in w[:nroots]], vecs
+        return self._finish(w, vecs, norb, nelec, nroots)
 
     def trans_rdm12_rows(self, bra, kets, norb, nelec):
         """One bra against all ``kets`` in one pass: ``(ovlp (K,), dm1 (K,N,N), dm2 (K,N,N,N,N))``.  The host arrays are

@@ -10,6 +10,9 @@ over alpha/beta occupation strings ordered by their integer value; ``dm1[p,q] = 
 ``dm2[p,q,r,s] = <p^+ r^+ s q>`` (chemists' order, spin summed), so that
 ``E = h1:dm1 + 1/2 h2:dm2`` with ``h2`` in chemists' notation.
 
+``spin_square_vector(c, norb, nelec)`` is ``S^2 c``; ``SmallFCI(spin_penalty=shift)`` adds ``shift (S^2 - S(S+1))`` to the
+operator the eigensolver sees, so that the lowest roots have the chosen multiplicity (PySCF's ``fix_spin_``).
+
 ``transform_ci(ci, nelec, u)`` rotates a CI vector under an orbital transformation (PySCF's ``fci.addons.transform_ci``),
 so that a state solved in the canonical basis can be stored in the OAO basis.
 
@@ -18,7 +21,9 @@ Host code for up to ~12 orbitals (training-state generation is outside the accel
 from __future__ import annotations
 
 from itertools import combinations
-from typing import List, Tuple
+import warnings
+from functools import lru_cache
+from typing import List, Optional, Tuple
 
 import numpy as np
 import scipy.sparse as sp
@@ -94,12 +99,104 @@ def transform_ci(ci, nelec, u) -> np.ndarray:
     return Ta.T @ c @ Tb
 
 
-class SmallFCI:
-    """Spin-adapted only through Ms: ``nelec = (nalpha, nbeta)``."""
+@lru_cache(maxsize=8)
+def _spin_ops(norb: int, nelec: Tuple[int, int]):
+    ea, na = _excitation_ops(norb, nelec[0])
+    eb, nb = (ea, na) if nelec[1] == nelec[0] else _excitation_ops(norb, nelec[1])
+    return ea, [[eb[p][q].T.tocsr() for q in range(norb)] for p in range(norb)], na, nb
 
-    def __init__(self, tol: float = 1e-13, dense_limit: int = 1500):
+
+def spin_constant(nelec) -> float:
+    """``Sz (Sz + 1) + n_beta``: what ``S^2 = Sz (Sz + 1) + n_beta - sum_pq E^alpha_pq E^beta_qp`` has on its diagonal
+    before the pair term."""
+    na_el, nb_el = _nelec_pair(nelec)
+    sz = 0.5 * (na_el - nb_el)
+    return sz * (sz + 1.0) + nb_el
+
+
+def spin_square_vector(c, norb: int, nelec, _ops=None) -> np.ndarray:
+    """``S^2 c``, ``(na, nb)``: ``k c - sum_pq ea[p][q] @ c @ eb[q][p].T`` with the CSR operators of
+    ``_excitation_ops`` and ``k = Sz (Sz + 1) + n_beta``."""
+    nelec = _nelec_pair(nelec)
+    ea, ebT, na, nb = _ops if _ops is not None else _spin_ops(norb, nelec)
+    c = np.asarray(c, dtype=np.float64).reshape(na, nb)
+    out = spin_constant(nelec) * c
+    for p in range(norb):
+        for q in range(norb):
+            if ea[p][q].nnz and ebT[q][p].nnz:
+                out -= (ea[p][q] @ c) @ ebT[q][p]
+    return out
+
+
+def spin_targets(nelec) -> List[float]:
+    """The values ``S (S + 1)`` that ``nelec`` allows: ``S = |Sz|, |Sz| + 1, ... <= (n_alpha + n_beta) / 2``."""
+    na_el, nb_el = _nelec_pair(nelec)
+    s, top, out = 0.5 * abs(na_el - nb_el), 0.5 * (na_el + nb_el), []
+    while s <= top:
+        out.append(s * (s + 1.0))
+        s += 1.0
+    return out
+
+
+def resolve_spin_target(spin_target: Optional[float], nelec) -> float:
+    """``spin_target`` as a float, ``None`` meaning ``Sz (Sz + 1)``; ``ValueError`` unless it is one of
+    ``spin_targets(nelec)``."""
+    allowed = spin_targets(nelec)
+    if spin_target is None:
+        return allowed[0]
+    hit = [v for v in allowed if abs(v - float(spin_target)) <= 1e-12]
+    if not hit:
+        raise ValueError(f"spin_target={spin_target} is no S(S+1) that nelec={_nelec_pair(nelec)} allows "
+                         f"(expected one of {allowed})")
+    return hit[0]
+
+
+def multiplicity_of(ss: float) -> float:
+    """``2 S + 1`` from ``<S^2> = S (S + 1)`` (PySCF's ``spin_square`` convention)."""
+    return 2.0 * (np.sqrt(ss + 0.25) - 0.5) + 1.0
+
+
+SPIN_WARN = 1e-6     # a returned root whose <S^2> is further than this from the target raises a RuntimeWarning
+
+
+def unshift_roots(theta, spin_squares, shift: float, target: float):
+    """The energies of H from the eigenvalues ``theta`` of ``H + shift (S^2 - target)`` and the measured ``<S^2>`` of
+    their (spin-pure) eigenvectors, in the solver's order; warns about every root of another multiplicity."""
+    out = []
+    for k, (t, ss) in enumerate(zip(theta, spin_squares)):
+        out.append(float(t) - shift * (float(ss) - target))
+        if abs(ss - target) > SPIN_WARN:
+            warnings.warn(f"root {k} has <S^2> = {ss:.6f}, not the target {target:.6f}: another multiplicity lies inside "
+                          f"the window of the {len(theta)} lowest shifted roots; use a larger spin_penalty (now {shift}) "
+                          f"or fewer roots", RuntimeWarning, stacklevel=3)
+    return out
+
+
+def fix_spin_(solver, shift: float = 0.2, ss: Optional[float] = None):
+    """PySCF's ``fci.addons.fix_spin_`` for a ``SmallFCI`` or ``DeviceFCI``: sets ``spin_penalty = shift`` and
+    ``spin_target = ss`` (an ``S (S + 1)`` value, ``None`` for the lowest multiplicity) and returns the solver."""
+    solver.spin_penalty = float(shift)
+    solver.spin_target = ss
+    return solver
+
+
+class SmallFCI:
+    """Spin-adapted through Ms, ``nelec = (nalpha, nbeta)``, and, with ``spin_penalty != 0``, through a penalty on S^2:
+    the eigensolver then sees ``H + spin_penalty (S^2 - spin_target)`` (``contract`` returns that operator's product, as
+    PySCF's ``contract_2e`` does after ``fix_spin_``), while ``kernel`` returns energies of H,
+    ``theta - spin_penalty (<S^2> - spin_target)`` with ``<S^2>`` measured per root and kept in ``spin_squares``.
+    ``spin_target`` is an ``S (S + 1)`` value, ``None`` meaning ``Sz (Sz + 1)``, the lowest multiplicity the electron
+    numbers allow.  A target above ``|Sz|`` pushes the lower multiplicities down instead of up (their penalty is
+    negative), as in PySCF: for such states choose ``nelec`` with ``Ms = S`` and leave ``spin_target`` alone.  With the
+    default ``spin_penalty = 0`` nothing changes and ``spin_squares`` stays ``None``."""
+
+    def __init__(self, tol: float = 1e-13, dense_limit: int = 1500, spin_penalty: float = 0.0,
+                 spin_target: Optional[float] = None):
         self.tol = tol
         self.dense_limit = dense_limit
+        self.spin_penalty = float(spin_penalty)
+        self.spin_target = spin_target
+        self.spin_squares = None
         self._cache = {}
         self.converged = True
 
@@ -134,7 +231,19 @@ class SmallFCI:
             for q in range(norb):
                 g = G[p * norb + q]
                 sigma += 0.5 * (ea[p][q] @ g + (ebT[p][q].T @ g.T).T)
+        if self.spin_penalty != 0.0:
+            nelec = _nelec_pair(nelec)
+            c = np.asarray(c, dtype=np.float64).reshape(na, nb)
+            target = resolve_spin_target(self.spin_target, nelec)
+            sigma += self.spin_penalty * (spin_square_vector(c, norb, nelec, self._ops(norb, nelec)) - target * c)
         return sigma
+
+    def spin_square(self, ci, norb, nelec):
+        """``(<S^2>, multiplicity)`` of a normalised CI vector, ``multiplicity = 2 (sqrt(<S^2> + 1/4) - 1/2) + 1``."""
+        nelec = _nelec_pair(nelec)
+        c = np.asarray(ci, dtype=np.float64).reshape(-1)
+        ss = float(c @ spin_square_vector(c, norb, nelec, self._ops(norb, nelec)).reshape(-1))
+        return ss, multiplicity_of(ss)
 
     def kernel(self, h1, h2, norb, nelec, nroots: int = 1, **_):
         """Lowest ``nroots`` eigenpairs.  Like PySCF: scalars/array for nroots == 1, lists otherwise."""
@@ -143,6 +252,9 @@ class SmallFCI:
         nelec = (int(nelec[0]), int(nelec[1]))
         _, _, na, nb = self._ops(norb, nelec)
         dim = na * nb
+        self.spin_squares = None
+        if self.spin_penalty != 0.0:
+            target = resolve_spin_target(self.spin_target, nelec)      # refused before any work
         mv = lambda v: self.contract(h1, h2, v.reshape(na, nb), norb, nelec).reshape(-1)
         if dim <= self.dense_limit:
             H = np.empty((dim, dim))
@@ -165,6 +277,10 @@ class SmallFCI:
             x = v[:, k].copy()
             x *= np.sign(x[np.argmax(np.abs(x))])     # fixed sign convention
             vecs.append(x.reshape(na, nb))
+        w = w[:nroots]
+        if self.spin_penalty != 0.0:
+            self.spin_squares = [self.spin_square(x, norb, nelec)[0] for x in vecs]
+            w = unshift_roots(w, self.spin_squares, self.spin_penalty, target)
         if nroots == 1:
             return float(w[0]), vecs[0]
         return [float(x) for x in w[:nroots]], vecs

@@ -75,3 +75,30 @@ def excite_through_tables(c, norb: int, nelec: Tuple[int, int]) -> np.ndarray:
         vb = np.where((b != 0)[None, :], np.sign(b)[None, :] * c[:, np.abs(b) - 1], 0.0)
         D[pq] = va + vb
     return D
+
+
+def spin_square_through_tables(c, norb: int, nelec: Tuple[int, int], alpha: float = 1.0, ss: float = 0.0,
+                               beta: float = 0.0, out=None) -> np.ndarray:
+    """What ``evc_fci_spin_apply`` computes, in numpy and in the kernel's order: ``beta out + alpha (S^2 c - ss c)``,
+    ``(na, nb)``.  Per element: ``(k - ss) c`` with ``k = Sz (Sz + 1) + n_beta``, then, ``pq = p norb + q`` ascending,
+    ``- sgn_a sgn_b c[Ja, Jb]`` with ``Ja`` from ``tab_a[Ia][p norb + q]`` and ``Jb`` from ``tab_b[Ib][q norb + p]`` where
+    both entries are non-zero, then ``alpha`` times that sum, then ``+ beta out`` (``beta == 0`` does not read ``out``);
+    every step rounded on its own.  The bit-level reference of the device kernel."""
+    n_a, n_b = int(nelec[0]), int(nelec[1])
+    ta, tb = packed_table(norb, n_a), packed_table(norb, n_b)
+    na, nb = ta.shape[0], tb.shape[0]
+    c = np.asarray(c, dtype=np.float64).reshape(na, nb)
+    sz = 0.5 * (n_a - n_b)
+    t = ((sz * (sz + 1.0) + n_b) - ss) * c
+    for p in range(norb):
+        for q in range(norb):
+            a, b = ta[:, p * norb + q], tb[:, q * norb + p]
+            ra, rb = np.flatnonzero(a), np.flatnonzero(b)
+            if ra.size == 0 or rb.size == 0:
+                continue
+            sgn = (np.sign(a[ra])[:, None] * np.sign(b[rb])[None, :]).astype(np.float64)
+            t[np.ix_(ra, rb)] -= sgn * c[np.ix_(np.abs(a[ra]) - 1, np.abs(b[rb]) - 1)]
+    r = alpha * t
+    if beta != 0.0:
+        r = beta * np.asarray(out, dtype=np.float64).reshape(na, nb) + r
+    return r

@@ -45,7 +45,7 @@ extern "C" {
                                  evc_fci_davidson_correction, evc_fci_solve_workspace_bytes, EVC_PROF_FCI_SOLVE;
                                  additive: evc_fci_rotate, evc_fci_rotate_workspace_bytes, EVC_PROF_FCI_ROTATE;
                                  additive: evc_fci_trdm_rows_packed, evc_fci_rows_packed_workspace_bytes,
-                                 EVC_PROF_FCI_PACK;
+                                 EVC_PROF_FCI_PACK; additive: evc_fci_spin_apply, evc_fci_spin_diag;
                                  evc_trdm_plan_describe */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
@@ -508,6 +508,29 @@ int evc_fci_davidson_correction(int64_t dim, const double *V, int64_t ldv, const
                                 int64_t ldt, double *rnorm2, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * S^2 on CI vectors that stay on the device (csrc/fci_spin.hip; host statements: evcont_amd/fci_small.py
+ * spin_square_vector, evcont_amd/fci_tables.py spin_square_through_tables), for the spin penalty
+ * shift (S^2 - S(S+1)) of DeviceFCI(spin_penalty=...) and for <S^2> of a state.  With Sz = (n_alpha - n_beta) / 2, the
+ * electron numbers read off the first string of each table, and k = Sz (Sz + 1) + n_beta:
+ *       (S^2 c)[Ia, Ib] = k c[Ia, Ib] - sum_pq sgn_a sgn_b c[Ja, Jb],   Ja, sgn_a from tab_a[Ia][p norb + q],
+ *                                                                       Jb, sgn_b from tab_b[Ib][q norb + p],
+ *       <I|S^2|I>       = k - popcount(occ(Ia) & occ(Ib)).
+ * evc_fci_spin_apply: out = beta out + alpha (S^2 c - ss c).  c and out are rows of vector sets as above (8-byte aligned
+ *       DEVICE doubles, na * nb each); beta == 0 does not read out; out must not overlap c (refused).  alpha = 1, ss = 0,
+ *       beta = 0 gives S^2 c; alpha = shift, ss = S(S+1), beta = 1 adds the penalty to the row evc_fci_sigma just wrote;
+ *       <S^2> is this call followed by evc_fci_dots.
+ * evc_fci_spin_diag: hdiag[I] += alpha (<I|S^2|I> - ss), the same penalty on the diagonal evc_fci_hdiag wrote.
+ * Limits as evc_fci_hdiag: 1 <= norb <= 16, 1 <= na, nb <= 12870 (nb = 1: the table of no beta electron).  No workspace.
+ * Every element is one sum in a fixed order ((k - ss) c first, pq ascending, then alpha times the sum, then beta out; no
+ * fused step): the same bits from run to run, and exact on integer data.  Both leave their record on
+ * EVC_PROF_FCI_SOLVE.
+ * --------------------------------------------------------------------------------- */
+int evc_fci_spin_apply(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b, const double *c,
+                       double alpha, double ss, double beta, double *out, void *stream);
+int evc_fci_spin_diag(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b, double alpha,
+                      double ss, double *hdiag, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Rotation of a CI vector under an orbital transformation (PySCF's fci.addons.transform_ci for a square u;
  * evcont_amd/fci_small.py: transform_ci).  With occ(I) the ascending occupied orbitals of string I and k electrons of a
  * spin,
@@ -586,8 +609,10 @@ int evc_sgto_integrals_batch(int natm, int nprim, int count, const double *coord
 #define EVC_PROF_FCI_EXCITE 8     /* evc_fci_*: D = E_pq c (last launch: the layout it wrote) */
 #define EVC_PROF_FCI_TRDM 9       /* evc_fci_trdm_rows: split-K product, with its tiling */
 #define EVC_PROF_FCI_SIGMA 10     /* evc_fci_sigma: G = h2 . D and the gather */
-#define EVC_PROF_FCI_SOLVE 11     /* evc_fci_hdiag / _dots / _combine / _davidson_correction: the kernels of the last such
-                                     call and its grouping (not cleared by the other evc_fci_* entry points) */
+#define EVC_PROF_FCI_SOLVE 11     /* evc_fci_hdiag / _dots / _combine / _davidson_correction / _spin_apply / _spin_diag:
+                                     the kernels of the last such call and its grouping, e.g.
+                                     "fci_spin_apply_kernel beta=1 tiles=870", "fci_spin_diag_kernel" (not cleared by
+                                     the other evc_fci_* entry points) */
 #define EVC_PROF_FCI_ROTATE 12    /* evc_fci_rotate: the minor kernel of each spin, whether it took the complementary
                                      minors, the panels of each T, and the product kernel */
 #define EVC_PROF_FCI_PACK 13      /* evc_fci_trdm_rows_packed: the packing kernel, e.g.
