@@ -89,6 +89,17 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // issued before it keep draining behind the work that follows.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// 16- and 32-byte vectors of doubles: one aligned 16-byte access, the accumulator tile of an FP64 MFMA
+typedef double d2 __attribute__((ext_vector_type(2)));
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+// v_mfma_f64_16x16x4_f64 operand maps (cdna_hip_programming.md §3):
+//   A[i][k]: lane l holds i = l&15, k = l>>4        B[k][j]: k = l>>4, j = l&15
+//   D[i][j]: j = l&15, i = (l>>4) + 4*reg
+__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
+
 // Cross-lane moves on the DPP path (one v_mov_b32_dpp per 32-bit half).  __shfl_xor lowers to ds_bpermute_b32: an
 // LDS-pipeline round trip per half and level, ~10x the latency.  CTRL: quad_perm [1,0,3,2] = 0xB1 (xor 1),
 // [2,3,0,1] = 0x4E (xor 2), row_half_mirror = 0x141, row_mirror = 0x140.

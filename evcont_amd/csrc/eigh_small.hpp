@@ -437,7 +437,7 @@ __device__ __forceinline__ bool oa_refine(int m, int nreal, const double *Ap, do
                 const int i = 16 * ti + l15, j = 16 * tj + l15;
                 const double *pr = Zt + (i < m ? i : 0) * kRp;
                 const double *zr = Zt + (j < m ? j : 0) * kRp, *wr = B1 + (j < m ? j : 0) * kRp;
-                d4s sa = {0.0, 0.0, 0.0, 0.0}, ra = {0.0, 0.0, 0.0, 0.0};
+                d4 sa = {0.0, 0.0, 0.0, 0.0}, ra = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                 for (int kk = 0; kk < 8; ++kk)
                     if (4 * kk < m) {
@@ -445,8 +445,8 @@ __device__ __forceinline__ bool oa_refine(int m, int nreal, const double *Ap, do
                         const bool kv = k < m;
                         const int kc = kv ? k : 0;
                         const double av = kv ? pr[kc] : 0.0;
-                        sa = __builtin_amdgcn_mfma_f64_16x16x4f64(av, kv ? wr[kc] : 0.0, sa, 0, 0, 0);
-                        ra = __builtin_amdgcn_mfma_f64_16x16x4f64(av, kv ? zr[kc] : 0.0, ra, 0, 0, 0);
+                        sa = mfma_f64(av, kv ? wr[kc] : 0.0, sa);
+                        ra = mfma_f64(av, kv ? zr[kc] : 0.0, ra);
                     }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {

@@ -19,12 +19,6 @@
 
 namespace evc {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
 static int fci_npad(int norb) { return (norb * norb + 15) / 16 * 16; }
 // sigma: row tiles per wave for nt = npad / 16 tiles
 static int fci_rt(int nt) { return (int)ceil_div(nt, ceil_div(nt, 4)); }

@@ -20,8 +20,6 @@
 
 namespace evc {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 constexpr int kRotMaxMinor = 8;             // largest instantiated determinant
 constexpr int64_t kRotPanelDoubles = 1 << 19;   // a panel of T holds about this many doubles (4 MiB)
 
@@ -130,10 +128,6 @@ __global__ __launch_bounds__(64) void fci_minor_kernel(RotU w, const int32_t *__
 // MFMA s of a step, lane group g = lane / 16 carries l = l0 + 4 g + s, so that the four operands a lane holds are
 // adjacent in l (a row of an A stored l-contiguous is read in whole 128-byte lines) and a fragment of an operand
 // stored [l][.] is one line.  Elements beyond m, n, k are neither read nor written; they enter as 0.
-__device__ __forceinline__ d4 rot_mfma(double a, double b, d4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(256) void fci_rotate_gemm_kernel(const double *__restrict__ A, int64_t sam, int64_t sak,
                                                               const double *__restrict__ B, int64_t ldb,
                                                               double *__restrict__ C, int64_t ldc, int64_t m, int64_t n,
@@ -172,7 +166,7 @@ __global__ __launch_bounds__(256) void fci_rotate_gemm_kernel(const double *__re
 #pragma unroll
             for (int r = 0; r < 2; ++r)
 #pragma unroll
-                for (int c = 0; c < 2; ++c) acc[r][c] = rot_mfma(af[r][s], bf[c][s], acc[r][c]);
+                for (int c = 0; c < 2; ++c) acc[r][c] = mfma_f64(af[r][s], bf[c][s], acc[r][c]);
     }
 #pragma unroll
     for (int r = 0; r < 2; ++r)

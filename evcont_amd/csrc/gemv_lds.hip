@@ -32,17 +32,10 @@
 
 namespace evc {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2v __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int kLW = kLdsChunkCols;  // columns per wave chunk
 constexpr int kTileBytes = 2048;  // 16 rows x 16 columns
-
-__device__ __forceinline__ d4 mfma64(double a, double b, d4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // LDS-DMA, 16 bytes per lane: LDS address = M0 + 16 * lane.  The compiler neither counts these loads nor knows that
 // they write LDS: every wait below is explicit, and the "memory" clobbers keep its own LDS reads on their side.
@@ -248,9 +241,9 @@ __global__ __launch_bounds__(256, 1) void gemv_rows_lds_kernel(GemvRowsLaunch L,
     {                                                                                           \
         _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                         \
             _Pragma("unroll") for (int gs = 0; gs < GS; ++gs)                                   \
-                acc[gs][T_] = mfma64(AF_[u].x, bf[gs][u].x, acc[gs][T_]);                       \
+                acc[gs][T_] = mfma_f64(AF_[u].x, bf[gs][u].x, acc[gs][T_]);                       \
             _Pragma("unroll") for (int gs = 0; gs < GS; ++gs)                                   \
-                acc[gs][T_] = mfma64(AF_[u].y, bf[gs][u].y, acc[gs][T_]);                       \
+                acc[gs][T_] = mfma_f64(AF_[u].y, bf[gs][u].y, acc[gs][T_]);                       \
         }                                                                                       \
     }
 // One image: chunks at C0_, C0_ + 64, ... of which NV_ are the wave's own; NEXT_: another image follows at CN_ (its slots
@@ -326,7 +319,7 @@ __global__ __launch_bounds__(256, 1) void gemv_rows_lds_kernel(GemvRowsLaunch L,
     // ([tile][copy][half][lane][2 doubles]: 16-byte LDS accesses, lanes 16 bytes apart), the owner adds the four in wave order --
     // (w0 + w1) + (w2 + w3), whoever owns the tile -- and stores the tile straight from its registers.
     wait_vm<0>();
-    d2v *red = reinterpret_cast<d2v *>(lds_img);
+    d2 *red = reinterpret_cast<d2 *>(lds_img);
 #pragma unroll
     for (int gs = 0; gs < GS; ++gs) {
         __syncthreads();
@@ -336,8 +329,8 @@ __global__ __launch_bounds__(256, 1) void gemv_rows_lds_kernel(GemvRowsLaunch L,
             if ((tt & 3) != wave) {
                 const int k = (wave - (tt & 3) - 1) & 3;   // 0..2: wave owner+1+k
                 // (two 16-byte planes: consecutive lanes 16 bytes apart -- a 32-byte lane pitch is a 2-way conflict)
-                red[((tt * 3 + k) * 2 + 0) * 64 + lane] = (d2v){acc[gs][tt][0], acc[gs][tt][1]};
-                red[((tt * 3 + k) * 2 + 1) * 64 + lane] = (d2v){acc[gs][tt][2], acc[gs][tt][3]};
+                red[((tt * 3 + k) * 2 + 0) * 64 + lane] = (d2){acc[gs][tt][0], acc[gs][tt][1]};
+                red[((tt * 3 + k) * 2 + 1) * 64 + lane] = (d2){acc[gs][tt][2], acc[gs][tt][3]};
             }
         }
         if (gs == 0) EVC_K5L_WG(5);
@@ -352,7 +345,7 @@ __global__ __launch_bounds__(256, 1) void gemv_rows_lds_kernel(GemvRowsLaunch L,
                 v[tt & 3] = acc[gs][tt];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    const d2v lo = red[((tt * 3 + k) * 2 + 0) * 64 + lane], hi = red[((tt * 3 + k) * 2 + 1) * 64 + lane];
+                    const d2 lo = red[((tt * 3 + k) * 2 + 0) * 64 + lane], hi = red[((tt * 3 + k) * 2 + 1) * 64 + lane];
                     v[((tt & 3) + 1 + k) & 3] = (d4){lo[0], lo[1], hi[0], hi[1]};
                 }
                 const d4 sum = (v[0] + v[1]) + (v[2] + v[3]);
@@ -566,7 +559,7 @@ __device__ __forceinline__ void cols_lds_body(const ColProblem &P, int g0, int G
     }
 #define EVC_COLS_MMA_K(X_, W_, K_)                                                                           \
     {                                                                                                        \
-        _Pragma("unroll") for (int gs = 0; gs < GS; ++gs) acc[gs] = mfma64(W_[K_][gs], X_[K_], acc[gs]);     \
+        _Pragma("unroll") for (int gs = 0; gs < GS; ++gs) acc[gs] = mfma_f64(W_[K_][gs], X_[K_], acc[gs]);     \
     }
 #define EVC_COLS_MMA(X_, W_)                                                                                 \
     {                                                                                                        \
@@ -745,7 +738,7 @@ __device__ __forceinline__ void cols_lds_slab_body(const ColProblem &P, int g0, 
         __builtin_amdgcn_sched_barrier(0);                                                                   \
         if (MMA_) {                                                                                          \
             _Pragma("unroll") for (int gs = 0; gs < GS; ++gs)                                                \
-                acc[PJ_][gs] = mfma64(wf[PQ_][0][gs], x[PQ_][PJ_][0], acc[PJ_][gs]);                         \
+                acc[PJ_][gs] = mfma_f64(wf[PQ_][0][gs], x[PQ_][PJ_][0], acc[PJ_][gs]);                         \
         }                                                                                                    \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
         wait_lds();                                                                                          \
@@ -753,7 +746,7 @@ __device__ __forceinline__ void cols_lds_slab_body(const ColProblem &P, int g0, 
         __builtin_amdgcn_sched_barrier(0);                                                                   \
         if (MMA_) {                                                                                          \
             _Pragma("unroll") for (int gs = 0; gs < GS; ++gs)                                                \
-                acc[PJ_][gs] = mfma64(wf[PQ_][1][gs], x[PQ_][PJ_][1], acc[PJ_][gs]);                         \
+                acc[PJ_][gs] = mfma_f64(wf[PQ_][1][gs], x[PQ_][PJ_][1], acc[PJ_][gs]);                         \
         }                                                                                                    \
         __builtin_amdgcn_sched_barrier(0);                                                                   \
     }
@@ -802,7 +795,7 @@ __device__ __forceinline__ void cols_lds_slab_body(const ColProblem &P, int g0, 
             for (int k = 0; k < 2; ++k)
 #pragma unroll
                 for (int gs = 0; gs < GS; ++gs)
-                    acc[NTW - 1][gs] = mfma64(wf[1][k][gs], x[1][NTW - 1][k], acc[NTW - 1][gs]);
+                    acc[NTW - 1][gs] = mfma_f64(wf[1][k][gs], x[1][NTW - 1][k], acc[NTW - 1][gs]);
         }
     }
 #pragma unroll

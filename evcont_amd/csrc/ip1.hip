@@ -7,12 +7,6 @@
 
 namespace evc {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 // Remaining blocks: y2[e] = sum_slab y2part[slab][e].
 // elements of the (b,c,d) range per thread (sizes the t2part workspace)
 static int ip1_per_thread() {

@@ -145,7 +145,7 @@ ColsLauncher launch_cols_valu, launch_cols_valu_rs, launch_cols_slab, launch_col
     launch_cols_lds_slab;
 int launch_rows_reduce(const double *partial, int64_t rows, int nspans, double alpha, double *y, hipStream_t st);
 
-// ---- transform.hip, pack.hip, y2.hip, ip1.hip ----------------------------------------
+// ---- quarter.hip, pair_transform.hip, pack.hip, y2.hip, ip1.hip ----------------------
 int launch_quarter_transform(const double *in, int64_t sin, const double *C, int64_t sC, int c_transposed, int n,
                              double *out, int64_t sout, int count, hipStream_t st);
 // Two quarter steps fused (n <= 32): out[r'][s'][p][q] = sum_rs in[p][q][r][s] C[r][r'] C[s][s'].
@@ -177,7 +177,7 @@ struct PairDotArgs {
     int nchunk;
 };
 // (pair_ld(n), the row pitch of the pipeline's dense (pair, pair) intermediates, and kPairTransformMaxN: route.hpp)
-// one packed operand row of the pair kernels in LDS (transform.hip pt_kernel, y2.hip y2_fused_kernel)
+// one packed operand row of the pair kernels in LDS (pair_transform.hip pt_kernel, pair_pipe.hip, y2.hip y2_fused_kernel)
 constexpr int kPtRawMax = (kPairTransformMaxN * (kPairTransformMaxN + 1) / 2 + 1 + 127) / 128;   // double2 per lane: 5
 constexpr int kPtRowLen = kPtRawMax * 128 + 4;   // + two zero slots (padding fragments), 16-byte multiple
 // (the plans of the pair steps and of Y2, and the launchers that take them: pair_plan.hpp)

@@ -20,16 +20,16 @@ constexpr int kNs64Sz = 64 * 64;
 __device__ __forceinline__ int ns64_idx(int row, int col) { return row * 64 + (col ^ ((row & 1) << 4)); }
 
 // strip of A.B for symmetric A: acc[tj] (+)= sum_k A[k][16 w + i] B[k][16 tj + j]
-__device__ __forceinline__ void ns64_strip(const double *A, const double *B, int wave, int l15, int l4, d4s (&acc)[4]) {
+__device__ __forceinline__ void ns64_strip(const double *A, const double *B, int wave, int l15, int l4, d4 (&acc)[4]) {
 #pragma unroll
-    for (int tj = 0; tj < 4; ++tj) acc[tj] = (d4s){0.0, 0.0, 0.0, 0.0};
+    for (int tj = 0; tj < 4; ++tj) acc[tj] = (d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
     for (int kk = 0; kk < 16; ++kk) {
         const int row = 4 * kk + l4;
         const double av = A[ns64_idx(row, 16 * wave + l15)];
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj)
-            acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, B[ns64_idx(row, 16 * tj + l15)], acc[tj], 0, 0, 0);
+            acc[tj] = mfma_f64(av, B[ns64_idx(row, 16 * tj + l15)], acc[tj]);
     }
 }
 
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kThreads) void loewdin_ns64_kernel(LoewdinArgs a) {
     bool ok = false;
     double eprev = 2.0;
     int it = 0;
-    d4s acc[4], acc2[4];
+    d4 acc[4], acc2[4];
 #pragma unroll 1
     for (; it < kNsMaxIter; ++it) {
         ns64_strip(Z, Y, wave, l15, l4, acc);

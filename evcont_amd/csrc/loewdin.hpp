@@ -29,12 +29,12 @@ constexpr int kNsMaxIter = 64;
 constexpr int kNsDoubles = 6 * kNsSz + 8;
 
 // (kmax = 4 for n <= 16: K = 16 covers the matrix, and only the tile (0, 0) is active then)
-__device__ __forceinline__ d4s ns_tile(const double *A, const double *B, int ao, int bo, int kmax) {
-    d4s acc = {0.0, 0.0, 0.0, 0.0};
+__device__ __forceinline__ d4 ns_tile(const double *A, const double *B, int ao, int bo, int kmax) {
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk)
         if (kk < kmax)   // uniform
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[kk * 4 * kNsP + ao], B[kk * 4 * kNsP + bo], acc, 0, 0, 0);
+            acc = mfma_f64(A[kk * 4 * kNsP + ao], B[kk * 4 * kNsP + bo], acc);
     return acc;
 }
 
@@ -85,7 +85,7 @@ __device__ bool loewdin_ns(const double *__restrict__ S, const double *__restric
     for (; it < kNsMaxIter; ++it) {
         double e = 0.0;
         if (act) {
-            const d4s p = ns_tile(Zc, Yc, ao, bo, kmax);
+            const d4 p = ns_tile(Zc, Yc, ao, bo, kmax);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const double dlt = (oi + 4 * r == oj) ? 1.0 : 0.0;
@@ -98,13 +98,13 @@ __device__ bool loewdin_ns(const double *__restrict__ S, const double *__restric
         __syncthreads();
         e = nanmax(nanmax(red[0], red[1]), nanmax(red[2], red[3]));
         if (act) {
-            d4s yn = {0.0, 0.0, 0.0, 0.0}, zn = {0.0, 0.0, 0.0, 0.0};
+            d4 yn = {0.0, 0.0, 0.0, 0.0}, zn = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int kk = 0; kk < 8; ++kk)
                 if (kk < kmax) {
                     const double b = Tm[kk * 4 * kNsP + bo];
-                    yn = __builtin_amdgcn_mfma_f64_16x16x4f64(Yc[kk * 4 * kNsP + ao], b, yn, 0, 0, 0);
-                    zn = __builtin_amdgcn_mfma_f64_16x16x4f64(Zc[kk * 4 * kNsP + ao], b, zn, 0, 0, 0);
+                    yn = mfma_f64(Yc[kk * 4 * kNsP + ao], b, yn);
+                    zn = mfma_f64(Zc[kk * 4 * kNsP + ao], b, zn);
                 }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -140,7 +140,7 @@ __device__ bool loewdin_ns(const double *__restrict__ S, const double *__restric
     }
     __syncthreads();
     if (act) {
-        const d4s wv = ns_tile(S0, Zc, ao, bo, kmax);
+        const d4 wv = ns_tile(S0, Zc, ao, bo, kmax);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Tm[(oi + 4 * r) * kNsP + oj] = wv[r];
     }
@@ -149,7 +149,7 @@ __device__ bool loewdin_ns(const double *__restrict__ S, const double *__restric
     {
         double e = 0.0;
         if (act) {
-            const d4s p = ns_tile(Zc, Tm, ao, bo, kmax);
+            const d4 p = ns_tile(Zc, Tm, ao, bo, kmax);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const double dlt = (oi + 4 * r == oj) ? 1.0 : 0.0;
@@ -165,7 +165,7 @@ __device__ bool loewdin_ns(const double *__restrict__ S, const double *__restric
     EVC_DBGVAL(51, res);
     if (!(res < 1.0e-7)) return false;   // (after the step: ~res^2)
     if (act) {
-        const d4s xv = ns_tile(Zc, Yn, ao, bo, kmax);
+        const d4 xv = ns_tile(Zc, Yn, ao, bo, kmax);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Zn[(oi + 4 * r) * kNsP + oj] = xv[r];
     }
@@ -183,13 +183,13 @@ __device__ bool loewdin_ns(const double *__restrict__ S, const double *__restric
     if (!(h && h1)) return true;
     __syncthreads();
     if (act) {
-        const d4s wv = ns_tile(Tm, Yc, ao, bo, kmax);   // W = h X
+        const d4 wv = ns_tile(Tm, Yc, ao, bo, kmax);   // W = h X
 #pragma unroll
         for (int r = 0; r < 4; ++r) Yn[(oi + 4 * r) * kNsP + oj] = wv[r];
     }
     __syncthreads();
     if (act) {
-        const d4s hv = ns_tile(Yc, Yn, ao, bo, kmax);   // h1 = X W
+        const d4 hv = ns_tile(Yc, Yn, ao, bo, kmax);   // h1 = X W
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             if (oi + 4 * r < n && oj < n) h1[(oi + 4 * r) * n + oj] = hv[r];

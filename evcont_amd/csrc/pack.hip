@@ -9,12 +9,6 @@
 
 namespace evc {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 // ------------------------------------------------------------------ pack / unpack
 __global__ void pack_kernel(const double *__restrict__ h2, int64_t sh2, int n, double mult, double *__restrict__ out,
                             int64_t sout, int64_t M, int64_t out_len) {
@@ -273,6 +267,22 @@ int launch_unpack8(const double *packed, int64_t sp, int n, double *SB, int64_t 
     return 0;
 }
 
-// ------------------------------------------------------------------ Y2 contraction (split-K MFMA GEMM)
-// partial[slab][i][a] = sum_{k in slab} GsT[k][i] * K3[k][a],  k = (j,k,l) flattened, n^3 long.
 }  // namespace evc
+
+// ------------------------------------------------------------------ C ABI
+using namespace evc;
+
+extern "C" int evc_pack_pair_sym(const double *h2, int n, double diag_mult, double *out, int64_t out_len,
+                                 void *stream) {
+    EVC_REQUIRE(h2 && out, "evc_pack_pair_sym: null pointer");
+    EVC_REQUIRE(n >= 1 && n <= 215, "evc_pack_pair_sym: n=%d out of range", n);
+    const int64_t n2 = (int64_t)n * n, M = n2 * (n2 + 1) / 2;
+    EVC_REQUIRE(out_len >= M, "evc_pack_pair_sym: out_len=%lld < M=%lld", (long long)out_len, (long long)M);
+    return launch_pack(h2, 0, n, diag_mult, out, 0, out_len, 1, as_stream(stream));
+}
+
+extern "C" int evc_unpack_pair_sym(const double *packed, int n, double *out, void *stream) {
+    EVC_REQUIRE(packed && out, "evc_unpack_pair_sym: null pointer");
+    EVC_REQUIRE(n >= 1 && n <= 215, "evc_unpack_pair_sym: n=%d out of range", n);
+    return launch_unpack(packed, 0, n, out, 0, 1, as_stream(stream));
+}

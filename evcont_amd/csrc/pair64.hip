@@ -3,7 +3,7 @@
 // (electron_integral_utils.py:136, ab_initio_gradients_loewdin.py:224-232) and the Y2 contraction with the
 // half-transformed integrals recomputed (ab_initio_gradients_loewdin.py:210-222), on 64 x 64 operand matrices.
 //
-// Same mathematics and the same dense (pair, pair) data forms as the n <= 32 kernels (transform.hip, pair_dma.hip, y2.hip):
+// Same mathematics and the same dense (pair, pair) data forms as the n <= 32 kernels (pair_transform.hip, pair_pipe.hip, pair_dma.hip, y2.hip):
 // per leading AO pair v = (p >= q) the symmetric n x n matrix M_v is one row of a dense (pair, pair) matrix,
 //     pt64:  R_v = C^T M_v C   (H = M_v C: 256 MFMAs; R = C^T H, lower-triangle tiles only: 160 MFMAs; the accumulator
 //                               tiles of H are the B operand of the second product)
@@ -21,20 +21,15 @@
 // One workgroup per CU (115 KB of LDS); a workgroup of pt64 takes `tiles_per_wg` consecutive tiles of four pairs.
 #include "common.hpp"
 #include "pair_plan.hpp"
+#include "pair_rows.hpp"
 
 namespace evc {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int kP64MaxPairs = 64 * 65 / 2;
 constexpr int kP64Raw = (kP64MaxPairs + 1 + 127) / 128;   // double2 per lane of one operand row: 17
 
-__device__ __forceinline__ d4 mfma64(double a, double b, d4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ int c64(int row, int col) { return row * 64 + (col ^ ((row & 1) << 4)); }
 
 // (p64_rowlen, the doubles of one wave's row / stage buffer: pair_plan.hpp)
@@ -78,11 +73,6 @@ __device__ __forceinline__ void p64_park(double *buf, int npairs, int lane, cons
         const int j = 128 * u + 2 * lane;
         if (j < npairs + 3) *reinterpret_cast<d2 *>(buf + j) = raw[u];   // (beyond the row: zeros, the zero slots included)
     }
-}
-
-__device__ __forceinline__ bool p64_is_diag(int x) {
-    const int r = tri_row_small(x);
-    return x == r * (r + 3) / 2;
 }
 
 }  // namespace
@@ -133,7 +123,7 @@ __global__ __launch_bounds__(256, 1) void pt64_kernel(PairTransformArgs a) {
 #pragma unroll
                 for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
-                    for (int st = 0; st < 4; ++st) h[rt][st] = mfma64(mf[rt], xf[st], h[rt][st]);
+                    for (int st = 0; st < 4; ++st) h[rt][st] = mfma_f64(mf[rt], xf[st], h[rt][st]);
             }
             // the next row of this wave is requested now: it arrives behind the second product
             const int en = e + 4;
@@ -153,8 +143,8 @@ __global__ __launch_bounds__(256, 1) void pt64_kernel(PairTransformArgs a) {
                     const double xa = Cs[c64(4 * kk + l4, 16 * ia + l15)], xb = Cs[c64(4 * kk + l4, 16 * ib + l15)];
 #pragma unroll
                     for (int st = 0; st < 4; ++st) {
-                        if (st <= ia) na[st] = mfma64(xa, h[kk >> 2][st][kk & 3], na[st]);
-                        if (st <= ib) nb[st] = mfma64(xb, h[kk >> 2][st][kk & 3], nb[st]);
+                        if (st <= ia) na[st] = mfma_f64(xa, h[kk >> 2][st][kk & 3], na[st]);
+                        if (st <= ib) nb[st] = mfma_f64(xb, h[kk >> 2][st][kk & 3], nb[st]);
                     }
                 }
 #pragma unroll
@@ -182,9 +172,9 @@ __global__ __launch_bounds__(256, 1) void pt64_kernel(PairTransformArgs a) {
             if (a.packed) {
                 // 8-fold compressed vector: u >= v, times the multiplicities of both pairs (and diag_mult on u == v)
                 double *pk = a.packed + g * a.spacked;
-                const double mq = p64_is_diag(ev) ? 1.0 : 2.0;
+                const double mq = tri_is_diag(ev) ? 1.0 : 2.0;
                 for (int u = ev + (int)(threadIdx.x >> 2); u < npairs; u += 64) {
-                    const double f = (u == ev ? a.diag_mult : 1.0) * mq * (p64_is_diag(u) ? 1.0 : 2.0);
+                    const double f = (u == ev ? a.diag_mult : 1.0) * mq * (tri_is_diag(u) ? 1.0 : 2.0);
                     pk[(int64_t)u * (u + 1) / 2 + ev] = src[u] * f;
                 }
             } else {
@@ -266,7 +256,7 @@ __global__ __launch_bounds__(256, 1) void y2_64_kernel(const double *__restrict_
             const int b = (e - e_begin) & 1;
             const char *rm = reinterpret_cast<const char *>(rows + (size_t)(2 * b) * rl);
             const char *rt_ = reinterpret_cast<const char *>(rows + (size_t)(2 * b + 1) * rl);
-            const double km = p64_is_diag(e) ? 1.0 : 2.0;
+            const double km = tri_is_diag(e) ? 1.0 : 2.0;
             // the rows of pair e + 1 (in registers since the previous iteration) go to the other buffer: nobody reads it
             // (the barrier at the end of the previous iteration), then the rows of pair e + 2 are requested
             if (e + 1 < e_end) park(b ^ 1);
@@ -280,7 +270,7 @@ __global__ __launch_bounds__(256, 1) void y2_64_kernel(const double *__restrict_
                 // (wave-dependent fragment: table row 16 wave + kk, not an immediate)
                 const double mf = *reinterpret_cast<const double *>(rm + ftab[(wave * 16 + kk) * 64 + lane]);
 #pragma unroll
-                for (int it = 0; it < 4; ++it) hT[it] = mfma64(Cs[c64(4 * kk + l4, 16 * it + l15)], mf, hT[it]);
+                for (int it = 0; it < 4; ++it) hT[it] = mfma_f64(Cs[c64(4 * kk + l4, 16 * it + l15)], mf, hT[it]);
             }
             // Y[:, block] += mult T_v H^T[:, block]
 #pragma unroll
@@ -288,7 +278,7 @@ __global__ __launch_bounds__(256, 1) void y2_64_kernel(const double *__restrict_
 #pragma unroll
                 for (int ti = 0; ti < 4; ++ti) {
                     const double tv = *reinterpret_cast<const double *>(rt_ + ftab[(ti * 16 + kk) * 64 + lane]) * km;
-                    yacc[ti] = mfma64(tv, hT[kk >> 2][kk & 3], yacc[ti]);
+                    yacc[ti] = mfma_f64(tv, hT[kk >> 2][kk & 3], yacc[ti]);
                 }
             __syncthreads();
         }

@@ -4,7 +4,7 @@
 // in its steady state.
 //
 // Why (round 4): an FP64 MFMA and every other vector instruction share one pipe on gfx950 (profiles/
-// mfma_f64_coissue.txt): pt_pipe_kernel (transform.hip) issued ~250 vector instructions per matrix -- address
+// mfma_f64_coissue.txt): pt_pipe_kernel (pair_pipe.hip) issued ~250 vector instructions per matrix -- address
 // arithmetic, predicates, selects, multiplicities -- beside its 56 MFMAs and kept the matrix pipe 49 % busy.  Loads,
 // stores, LDS and scalar instructions DO issue while an MFMA executes.  Here everything per matrix is one of those:
 //   * the operand row (one packed symmetric matrix, n(n+1)/2 doubles) comes by LDS-DMA (global_load_lds_dwordx4,
@@ -23,19 +23,14 @@
 // iterations behind its barrier, two workgroups per CU.
 #include "common.hpp"
 #include "pair_plan.hpp"
+#include "pair_rows.hpp"
 
 namespace evc {
 
 namespace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 // (kPdMaxN and the LDS layout constants kPd*: pair_plan.hpp, the plans size the launches from them)
 
-__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 // LDS-DMA, 16 bytes per lane: LDS address = M0 + 16 * lane.  Invisible to the compiler's wait counting.
 __device__ __forceinline__ void glds16(unsigned voff, const void *sbase, unsigned lds_addr) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
@@ -243,11 +238,8 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
             const int r = tri_row_small(u);
             *(lds_f32 *)(uintptr_t)(kPdTab + 4u * (unsigned)u) = (u == r * (r + 3) / 2) ? 1.0f : 2.0f;
         }
-        if (blockIdx.x == 0) {   // zero the padding [M, packed_len) once per geometry
-            double *pk = a.packed + g * a.spacked;
-            const int64_t M = (int64_t)npairs * (npairs + 1) / 2;
-            for (int64_t m = M + threadIdx.x; m < a.packed_len; m += 256) pk[m] = 0.0;
-        }
+        if (blockIdx.x == 0)   // zero the padding [M, packed_len) once per geometry
+            zero_packed_tail(a.packed + g * a.spacked, (int64_t)npairs * (npairs + 1) / 2, a.packed_len);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 8; ++k) {

@@ -1,7 +1,7 @@
 // Which kernel runs a pair step or the Y2 contraction, and with what launch: the plan is a value --
 // plan_pair_step, plan_y2 and, for the gradient side of the symmetric pipeline, plan_grad_pairs, pure functions of the
 // launch arguments, the batch size and the knobs.  It names ONE kernel instantiation, its tiling, grid and dynamic LDS;
-// the launchers (transform.hip, pair_dma.hip, pair64.hip, y2.hip) launch exactly that and decide nothing.  The plans are
+// the launchers (pair_transform.hip, pair_pipe.hip, pair_dma.hip, pair64.hip, y2.hip) launch exactly that and decide nothing.  The plans are
 // host code; the LDS layout constants kPd* and p64_rowlen below are shared with the kernels of pair_dma.hip and
 // pair64.hip, which lay out the LDS the plans size.
 #pragma once
@@ -242,6 +242,7 @@ int launch_pair_transform(const PairPlan &p, PairTransformArgs a, int count, hip
 inline int launch_pair_transform(const PairTransformArgs &a, int count, hipStream_t st) {
     return launch_pair_transform(plan_pair_step(a, count, pair_knobs()), a, count, st);
 }
+int launch_pair_transform_pipe(const PairPlan &p, const PairTransformArgs &a, dim3 grid, hipStream_t st);   // pair_pipe.hip
 int launch_pair_transform_dma(const PairPlan &p, const PairTransformArgs &a, int count, hipStream_t st);   // pair_dma.hip
 int launch_pair_transform64(const PairPlan &p, const PairTransformArgs &a, int count, hipStream_t st);     // pair64.hip
 // the dense step does not write `out` but contracts its result with the packed int2e_ip1 as the pair blocks of

@@ -15,7 +15,7 @@ inline bool is_packed(int layout) { return layout == EVC_LAYOUT_ELEC3 || layout 
 
 enum class Steps {
     Quarter,   // four quarter steps
-    Pair,      // n <= 32: two fused pair steps (transform.hip / pair_dma.hip)
+    Pair,      // n <= 32: two fused pair steps (pair_transform.hip / pair_pipe.hip / pair_dma.hip)
     Pair64,    // 32 < n <= 64 on the compressed layout with the large array handed over packed (EVC_FLAG_ERI_S4 with the
                // energy phase, EVC_FLAG_IP1_S2KL with the gradient phase): pair steps on 64 x 64 operand matrices
                // (pair64.hip).  (Full arrays take the quarter-step route.)

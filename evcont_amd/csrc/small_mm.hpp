@@ -11,7 +11,6 @@ constexpr int kThreads = 256;
 
 // ------------------------------------------------------------------ small LDS matmul
 // C[i][j] = sum_k a(i,k) * b(k,j),  i,j < n;  thread (tj,tk) owns i = tj+16*, j = tk+16*.
-typedef double d4s __attribute__((ext_vector_type(4)));
 // Small products on the FP64 matrix cores (n <= 64; up to 32: wave w of the workgroup owns the 16 x 16 output tile
 // (w >> 1, w & 1), beyond: sixteen tiles round-robin); operand maps of v_mfma_f64_16x16x4_f64: A[i][k]: lane l holds i = l & 15, k = l >> 4; B[k][j]:
 // k = l >> 4, j = l & 15; D[i][j]: j = l & 15, i = (l >> 4) + 4 reg.  One eighth of the LDS traffic of the 2 x 2
@@ -31,7 +30,7 @@ __device__ __forceinline__ void mm16(int n, FA a, FB b, FC store) {
         if (16 * ti < n && 16 * tj < n) {   // wave-uniform
             const int i = 16 * ti + l15, j = 16 * tj + l15;
             const int ic = i < n ? i : 0, jc = j < n ? j : 0;   // (rows / columns beyond n: computed on row 0, never stored)
-            d4s acc = {0.0, 0.0, 0.0, 0.0};
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int kk = 0; kk < 8; ++kk)
                 if (4 * kk < n) {
@@ -39,7 +38,7 @@ __device__ __forceinline__ void mm16(int n, FA a, FB b, FC store) {
                     const bool kv = k < n;
                     const int kc = kv ? k : 0;
                     const double av = a(ic, kc), bv = b(kc, jc);
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(kv ? av : 0.0, kv ? bv : 0.0, acc, 0, 0, 0);
+                    acc = mfma_f64(kv ? av : 0.0, kv ? bv : 0.0, acc);
                 }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -56,7 +55,7 @@ __device__ __forceinline__ void mm16(int n, FA a, FB b, FC store) {
             const int ti = t / nt, tj = t - ti * nt;
             const int i = 16 * ti + l15, j = 16 * tj + l15;
             const int ic = i < n ? i : 0, jc = j < n ? j : 0;
-            d4s acc = {0.0, 0.0, 0.0, 0.0};
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int kk = 0; kk < 16; ++kk)
                 if (4 * kk < n) {
@@ -64,7 +63,7 @@ __device__ __forceinline__ void mm16(int n, FA a, FB b, FC store) {
                     const bool kv = k < n;
                     const int kc = kv ? k : 0;
                     const double av = a(ic, kc), bv = b(kc, jc);
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(kv ? av : 0.0, kv ? bv : 0.0, acc, 0, 0, 0);
+                    acc = mfma_f64(kv ? av : 0.0, kv ? bv : 0.0, acc);
                 }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -117,14 +116,14 @@ __device__ __forceinline__ void mm_rowrow(int m, const double *__restrict__ P, c
     if (16 * ti >= m || 16 * tj >= m) return;   // wave-uniform
     const int i = 16 * ti + l15, j = 16 * tj + l15;
     const double *pr = P + (i < m ? i : 0) * kRp, *qr = Q + (j < m ? j : 0) * kRp;
-    d4s acc = {0.0, 0.0, 0.0, 0.0};
+    d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk)
         if (4 * kk < m) {
             const int k = 4 * kk + l4;
             const bool kv = k < m;
             const double av = pr[kv ? k : 0], bv = qr[kv ? k : 0];
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(kv ? av : 0.0, kv ? bv : 0.0, acc, 0, 0, 0);
+            acc = mfma_f64(kv ? av : 0.0, kv ? bv : 0.0, acc);
         }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {

@@ -31,7 +31,6 @@ namespace evc {
 
 constexpr int kBT = 1024;   // threads of the workgroup
 constexpr int kBW = kBT / 64;
-typedef double d4b __attribute__((ext_vector_type(4)));
 
 // Phase stamps of workgroup 0 (tools/micro/subspace_time.py --stamps; library built with EVC_DEBUG_STAMPS=1)
 #ifdef EVC_DEBUG_STAMPS
@@ -112,13 +111,13 @@ __device__ __forceinline__ void big_mm_rr(int Tp, const double *__restrict__ P, 
         const int ti = t / nt, tj = t - ti * nt;
         const double *pr = P + (size_t)(16 * ti + l15) * ldp + 2 * l4;
         const double *qr = Q + (size_t)(16 * tj + l15) * ldq + 2 * l4;
-        d4b acc = {0.0, 0.0, 0.0, 0.0};
+        d4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
         for (int k = 0; k < Tp; k += 8) {
             const double2 av = *reinterpret_cast<const double2 *>(pr + k);
             const double2 bv = *reinterpret_cast<const double2 *>(qr + k);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av.x, bv.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av.y, bv.y, acc, 0, 0, 0);
+            acc = mfma_f64(av.x, bv.x, acc);
+            acc = mfma_f64(av.y, bv.y, acc);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) store(16 * ti + l4 + 4 * r, 16 * tj + l15, acc[r]);

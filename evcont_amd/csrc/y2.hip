@@ -3,15 +3,10 @@
 // variant for 17 <= N <= 30 lives in pair_dma.hip).  blockIdx.y = geometry of the batch (kernels.hpp).
 #include "common.hpp"
 #include "pair_plan.hpp"
+#include "pair_rows.hpp"
 
 namespace evc {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 // Both operands are [k][n] row-major, so each MFMA fragment load is 16 contiguous doubles.
 
 template <int NT>
@@ -194,25 +189,9 @@ __global__ __launch_bounds__(256) void y2_fused_kernel(const double *__restrict_
         }
         d2 rawM[RAWN], rawT[RAWN];
         auto fetch = [&](const double *base, int e, d2 (&raw)[RAWN]) -> int {
-            const double *row = base + (int64_t)(e < npairs ? e : 0) * ld;
-            const int d_ = (int)((reinterpret_cast<uintptr_t>(row) >> 3) & 1);
-            const double *w0 = row - d_;
-            const int lim = npairs + d_;
-#pragma unroll
-            for (int u = 0; u < RAWN; ++u) {
-                const int j = 128 * u + 2 * lane;
-                raw[u] = *reinterpret_cast<const d2 *>(w0 + (j < lim ? j : 0));
-            }
-            return d_;
+            return fetch_packed_row(base + (int64_t)(e < npairs ? e : 0) * ld, npairs, lane, raw);
         };
-        auto park = [&](double *row, const d2 (&raw)[RAWN]) {
-#pragma unroll
-            for (int u = 0; u < RAWN; ++u) *reinterpret_cast<d2 *>(row + 128 * u + 2 * lane) = raw[u];
-        };
-        auto is_diag = [&](int x) -> bool {
-            const int r = tri_row_small(x);
-            return x == r * (r + 3) / 2;
-        };
+        auto park = [&](double *row, const d2 (&raw)[RAWN]) { park_packed_row(row, lane, raw); };
         const int e0 = ppt * t_begin + wave;   // this wave's pair of iteration i: e0 + 4 i
         int dM = fetch(M1, e0, rawM), dT = fetch(SB, e0, rawT);
         double xf[KS][NT];
@@ -238,7 +217,7 @@ __global__ __launch_bounds__(256) void y2_fused_kernel(const double *__restrict_
         // requested.  No branches in the body: idle slots of the last tile run on row 0 with multiplicity 0.
         for (int i = 0; i < niter; ++i) {
             const int e = e0 + 4 * i;
-            const double km = e < npairs ? (is_diag(e) ? 1.0 : 2.0) : 0.0;   // multiplicity of the pair (p,q)
+            const double km = e < npairs ? (tri_is_diag(e) ? 1.0 : 2.0) : 0.0;   // multiplicity of the pair (p,q)
             park(rowT, rawT);
 #pragma unroll
             for (int rt = 0; rt < NT; ++rt)

@@ -1,4 +1,4 @@
-// Development harness of the symmetric pair step: pt_pipe_kernel (transform.hip) against ptd_kernel (pair_dma.hip) on
+// Development harness of the symmetric pair step: pt_pipe_kernel (pair_pipe.hip) against ptd_kernel (pair_dma.hip) on
 // the same operands -- results compared element by element and against a host reference, both timed with HIP events.
 //   build:  hipcc --offload-arch=gfx950 -O2 -std=c++17 -Ievcont_amd/csrc tools/micro/pt_dev.hip -Levcont_amd \
 //           -levcont_hip -Wl,-rpath,'$ORIGIN/../evcont_amd' -o build_micro/pt_dev

@@ -22,7 +22,9 @@ for _ in range(5):
 torch.cuda.synchronize()
 lib = _lib.load()
 st = (C.c_longlong * 256)()
-fn = lib.evc_debug_read_pt; fn.restype = C.c_int; fn.argtypes = [C.c_void_p]
+# each kernel family's unit has its own stamps: pair_pipe.hip's by default, pair_transform.hip's pt_kernel with EVC_PT_PIPE=0
+sfx = "" if os.environ.get("EVC_PT_PIPE", "1") != "0" else "_phase"
+fn = getattr(lib, "evc_debug_read_pt" + sfx); fn.restype = C.c_int; fn.argtypes = [C.c_void_p]
 assert fn(st) == 0
 names = {0: "entry", 1: "X staged", 2: "xf+frag0"}
 for k in range(6):
@@ -42,7 +44,7 @@ for i in range(60):
     if all(v == 0 for v in vals): continue
     print("%-18s" % names.get(i, i), "  ".join("%7.2f" % ((v - t0) / 100.0) for v in vals))
 wg = (C.c_longlong * (4096 * 3))()
-fn = lib.evc_debug_read_pt_wg; fn.restype = C.c_int; fn.argtypes = [C.c_void_p]
+fn = getattr(lib, "evc_debug_read_pt_wg" + sfx); fn.restype = C.c_int; fn.argtypes = [C.c_void_p]
 assert fn(wg) == 0
 w = np.array(wg[:]).reshape(4096, 3)
 nwg = 15 * G
