@@ -12,7 +12,7 @@
 //      reflectors with the vector distributed over the lanes (one wave_sum per reflector).
 //   4. Verification in the ORIGINAL matrix: residual and mutual overlap; the caller falls back to the full
 //      eigensolver when it fails (a cluster among the requested roots, an overflow in a recurrence).
-// Same scheme as the large-T kernel's few-roots route (subspace_big.hip: big_few_roots), which runs on 16 waves with
+// Same scheme as the large-T kernel's few-roots route (big_few_roots.hpp), which runs on 16 waves with
 // the matrix in LDS; here nothing waits for a barrier.
 #pragma once
 #include "common.hpp"

@@ -1,6 +1,6 @@
 // Which kernel runs the streaming t-RDM contractions of a call (host code only):
 //   K5  rows GEMV  y[g][r]   = sum_c A[r,c] v[g][c]     kernels in gemv_stream.hip, gemv_mfma.hip, gemv_lds.hip
-//   K8  cols GEMV  out[g][c] = sum_r w[g][r] A[r,c]
+//   K8  cols GEMV  out[g][c] = sum_r w[g][r] A[r,c]   kernels in gemv_stream.hip, gemv_mfma.hip, gemv_cols_lds.hip
 // The plan of a call is a value -- plan_gemv_rows / plan_gemv_cols, pure functions of the two matrix shapes, the batch
 // size, the CU count of the device and the knobs: the span decomposition of K5 and a list of passes, each naming the
 // geometries it takes, the problems it carries and ONE kernel instantiation.  launch_gemv_rows / launch_gemv_cols ask for

@@ -3,7 +3,7 @@
 //   K8/K7  cols GEMV   out[g][c] = sum_r w[g][r] A[r,c]     (predicted RDMs,  gradients_loewdin.py:343-356)
 // A (the t-RDM) is shared by a batch of geometries, so one pass over the 0.68-2.6 GB matrix serves
 // G evaluations: G <= 8 per pass with the VALU kernels of this file, 12..64 with the matrix-core
-// variants of gemv_mfma.hip and gemv_lds.hip (gemv_dispatch.hip plans the passes of a call).
+// variants of gemv_mfma.hip, gemv_lds.hip and gemv_cols_lds.hip (gemv_dispatch.hip plans the passes of a call).
 // Each launch carries TWO problems (the two-body and the one-body t-RDM) so the small one rides
 // along with the big one instead of costing a kernel boundary.
 #include <stdlib.h>

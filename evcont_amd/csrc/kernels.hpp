@@ -34,7 +34,8 @@ int launch_fci_row_pack(int layout, int norb, const double *dm2, double *row, in
 void note_fci_row_pack(int layout, int norb, int nrows, int64_t ld);
 
 // ---- K5 / K8, the streaming t-RDM contractions: kernels in gemv_stream.hip (VALU), gemv_mfma.hip (matrix cores,
-//      fragment-shaped loads), gemv_lds.hip (matrix cores, LDS-staged); gemv_dispatch.hip plans the passes of a call
+//      fragment-shaped loads), gemv_lds.hip / gemv_cols_lds.hip (matrix cores, K5 / K8 LDS-staged); gemv_dispatch.hip
+//      plans the passes of a call
 struct RowProblem {
     const double *A;   // (rows, ld)                       shared by the batch
     const double *v;   // (cols)            + g*vstride
@@ -262,7 +263,7 @@ struct LoewdinArgs {
 };
 int launch_loewdin(const LoewdinArgs &a, int count, hipStream_t st);
 bool loewdin_split_available(int n);
-// subspace_big.hip: 32 < n <= 64 in LDS alone, up to kMaxOrbitals with a.scratch
+// loewdin_big.hip: 32 < n <= 64 in LDS alone, 64 < n <= kMaxOrbitals with a.scratch
 int launch_loewdin_big(const LoewdinArgs &a, int count, hipStream_t st);
 // Host-side knobs, read once per process (loewdin.hip).  EVC_EIGH_F32: 0 = FP64 Jacobi, 1 = FP32 Jacobi + refinement,
 // 2 (default) = FP32 tridiagonal start + refinement.  EVC_SUBSPACE_FEW (default 1): a few lowest roots through the
@@ -270,7 +271,7 @@ int launch_loewdin_big(const LoewdinArgs &a, int count, hipStream_t st);
 int eigh_fast_enabled();
 int subspace_few_enabled();
 
-// ---- subspace_small.hip (T <= kSubspaceSmallT), subspace_big.hip (beyond) ------------------------------
+// ---- subspace_small.hip (T <= kSubspaceSmallT), subspace_big.hip (beyond; big_block.hpp, big_few_roots.hpp) ---
 struct SolveArgs {
     const double *h1part;  // (nsp1, T*T) partial sums of the one-body rows      + g*sh1
     int nsp1;

@@ -1,6 +1,7 @@
 // The Loewdin step's own launches: loewdin_kernel (loewdin.hpp) for n <= 32 and the LDS-only route up to 80,
-// loewdin_ns64_kernel (Newton-Schulz, 32 < n <= 64), launch_loewdin's dispatch between them and subspace_big.hip's
-// loewdin_big_kernel, the two host-side knobs of the small eigensolvers, and evc_loewdin.
+// loewdin_ns64_kernel (Newton-Schulz, 32 < n <= 64), launch_loewdin's dispatch between them and loewdin_big.hip's
+// loewdin_big_kernel (32 < n <= 64 in LDS alone, 64 < n <= kMaxOrbitals with a scratch buffer), the two host-side
+// knobs of the small eigensolvers, and evc_loewdin.
 #include <stdlib.h>
 #include <string.h>
 

@@ -7,7 +7,7 @@
 // mfma_f64_coissue.txt): pt_pipe_kernel (pair_pipe.hip) issued ~250 vector instructions per matrix -- address
 // arithmetic, predicates, selects, multiplicities -- beside its 56 MFMAs and kept the matrix pipe 49 % busy.  Loads,
 // stores, LDS and scalar instructions DO issue while an MFMA executes.  Here everything per matrix is one of those:
-//   * the operand row (one packed symmetric matrix, n(n+1)/2 doubles) comes by LDS-DMA (global_load_lds_dwordx4,
+//   * the operand row (one packed symmetric matrix, n(n+1)/2 doubles) comes by LDS-DMA (glds_s of lds_dma.hpp:
 //     scalar row base + four lane-constant offsets) into the wave's LDS row; the fragments are read from it at sixteen
 //     lane-constant addresses; the wait for the DMA is a counted vmcnt (the stores issued behind it are counted per
 //     wave on the host side of the loop, all conditions wave-uniform);
@@ -22,6 +22,7 @@
 // of matrix i, one barrier per tile of eight leading pairs, tile j written out during the N phases of the two
 // iterations behind its barrier, two workgroups per CU.
 #include "common.hpp"
+#include "lds_dma.hpp"
 #include "pair_plan.hpp"
 #include "pair_rows.hpp"
 
@@ -31,13 +32,8 @@ namespace {
 
 // (kPdMaxN and the LDS layout constants kPd*: pair_plan.hpp, the plans size the launches from them)
 
-// LDS-DMA, 16 bytes per lane: LDS address = M0 + 16 * lane.  Invisible to the compiler's wait counting.
-__device__ __forceinline__ void glds16(unsigned voff, const void *sbase, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                 :
-                 : "v"(voff), "s"(sbase), "s"(lds_addr)
-                 : "memory");
-}
+// (the LDS-DMA load glds_s and the counted waits wait_vm_dyn / wait_vm_dyn8: lds_dma.hpp)
+
 // 16-byte store, scalar base + 32-bit lane offset (the compiler forms a 64-bit vector address for the same C++)
 __device__ __forceinline__ void gstore16(unsigned voff, d2 v, const void *sbase) {
     asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"(voff), "v"(v), "s"(sbase) : "memory");
@@ -57,22 +53,6 @@ __device__ __forceinline__ double lds_ld(unsigned addr) { return *(lds_f64 *)(ui
 __device__ __forceinline__ void lds_st(unsigned addr, double v) { *(lds_f64 *)(uintptr_t)addr = v; }
 typedef __attribute__((address_space(3))) d2 lds_d2;
 __device__ __forceinline__ d2 lds_ld2(unsigned addr) { return *(lds_d2 *)(uintptr_t)addr; }
-// k (0..3) wave-uniform: scalar compares and one wait
-__device__ __forceinline__ void wait_vm_dyn(int k) {
-    if (k <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (k == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if (k == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-}
-// the same for 0..8 (the pair step with Y2 has the DMA of a second row among the younger instructions)
-__device__ __forceinline__ void wait_vm_dyn8(int k) {
-    if (k <= 3) wait_vm_dyn(k);
-    else if (k == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (k == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if (k == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (k == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-}
 
 // (memory, LDS and scalar instructions at a higher priority than the MFMAs: a wave that issues MFMAs back to back
 //  otherwise keeps the issue port from its SIMD mate's loads and stores, profiles/mfma_f64_coissue.txt)
@@ -181,7 +161,7 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
         const char *src = reinterpret_cast<const char *>(in + (int64_t)ec * in_ld) - 8 * dw;
 #pragma unroll
         for (unsigned u = 0; u < kPdRaw; ++u)
-            if ((int)u < npieces) glds16(vo[u], src, rowb + 1024u * u);
+            if ((int)u < npieces) glds_s(vo[u], src, rowb + 1024u * u);
     };
     dma_row(e0);
     // Y2: the M1 row of the same pair (rows on 16-byte granules: the launch checks it, the window is the SB row's)
@@ -192,7 +172,7 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
         const char *src = reinterpret_cast<const char *>(M1 + (int64_t)ec * in_ld);
 #pragma unroll
         for (unsigned u = 0; u < kPdRaw; ++u)
-            if ((int)u < npieces) glds16(vo[u], src, rowb + kRowM + 1024u * u);
+            if ((int)u < npieces) glds_s(vo[u], src, rowb + kRowM + 1024u * u);
     };
     if constexpr (Y2) {
         if (lane < 8) *reinterpret_cast<double *>(lds + rowb + kRowM + kPdRaw * 1024 + 8 * lane) = 0.0;
@@ -723,7 +703,7 @@ __global__ __launch_bounds__(256, PS ? 1 : 2) void y2d_kernel(Y2dArgs ya, PairTr
             const char *src = reinterpret_cast<const char *>(base + (int64_t)(e < npairs ? e : wave) * ld);
 #pragma unroll
             for (unsigned u = 0; u < kPdRaw; ++u)
-                if ((int)u < npieces) glds16(vo[u], src, dst + 1024u * u);
+                if ((int)u < npieces) glds_s(vo[u], src, dst + 1024u * u);
         };
         // "everything but the youngest row has landed": npieces DMA instructions may stay in flight
         auto wait_older = [&]() {

@@ -1,6 +1,6 @@
 """Child process of tests/test_gpu_lds_kernels.py: batched energies and forces of a list of shapes with the streaming
-kernels the environment selects (EVC_ROWS_LDS / EVC_COLS_LDS: the LDS-staged K5 / K8 of csrc/gemv_lds.hip, or the
-fragment-shaped kernels of csrc/gemv_mfma.hip), written to an .npz.  The inputs are generated on the device from seeds,
+kernels the environment selects (EVC_ROWS_LDS / EVC_COLS_LDS: the LDS-staged K5 / K8 of csrc/gemv_lds.hip /
+gemv_cols_lds.hip, or the fragment-shaped kernels of csrc/gemv_mfma.hip), written to an .npz.  The inputs are generated on the device from seeds,
 so two children see identical data."""
 import os
 import sys

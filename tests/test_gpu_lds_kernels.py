@@ -1,6 +1,6 @@
-"""Differential test of the LDS-staged streaming kernels (csrc/gemv_lds.hip: K5 ``gemv_rows_lds_kernel``, K8
-``gemv_cols_lds_kernel``) against the fragment-shaped kernels they replace (csrc/gemv_mfma.hip), on shapes the
-oracle would take minutes for (N up to 32, T up to 23, 12 ... 44 geometries per batch, both layouts): the same seeded
+"""Differential test of the LDS-staged streaming kernels (csrc/gemv_lds.hip: K5 ``gemv_rows_lds_kernel``;
+csrc/gemv_cols_lds.hip: K8 ``gemv_cols_lds_kernel``) against the fragment-shaped kernels they replace
+(csrc/gemv_mfma.hip), on shapes the oracle would take minutes for (N up to 32, T up to 23, 12 ... 44 geometries per batch, both layouts): the same seeded
 device data through two fresh processes, energies and forces compared.  (Both kernel families are held to the CPU
 oracle on the shapes it can afford in test_gpu_bench_config.py / test_gpu_variants.py.)"""
 import os

@@ -1,9 +1,10 @@
-// Microbenchmark 3: the PRODUCT batched rows kernels (csrc/gemv_dispatch.hip and the three kernel files compiled
-// in) on a bare matrix, to bisect what separates them from a plain stream: rows 192/208/210, with and
+// Microbenchmark 3: the PRODUCT batched rows kernels (csrc/gemv_dispatch.hip and the kernel files it plans for
+// compiled in) on a bare matrix, to bisect what separates them from a plain stream: rows 192/208/210, with and
 // without the small second problem, with the V vectors close together or a workspace apart.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../include -I../../evcont_amd/csrc rows_insitu.hip \
 //         ../../evcont_amd/csrc/gemv_dispatch.hip ../../evcont_amd/csrc/gemv_stream.hip \
-//         ../../evcont_amd/csrc/gemv_mfma.hip ../../evcont_amd/csrc/gemv_lds.hip -o /tmp/rows_insitu
+//         ../../evcont_amd/csrc/gemv_mfma.hip ../../evcont_amd/csrc/gemv_lds.hip \
+//         ../../evcont_amd/csrc/gemv_cols_lds.hip -o /tmp/rows_insitu
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
