@@ -8,6 +8,11 @@ overlap / transition-RDM evaluation to a user-supplied ``pair_rdm_fun(casci_bra,
 (ovlp, rdm1, rdm2)`` in the OAO basis (what ``CASCI_EVCont.py:204-335`` computes with pygnme) and
 raises ImportError when neither that nor PySCF is available.  Everything downstream — array growth,
 pruning, the device-resident packed copy — is shared with the other containers.
+
+With a ``cisolver`` (``fci_small.SmallFCI()`` or ``fci_device.DeviceFCI()``) nothing third-party is needed:
+``append_to_rdms(mol)`` runs ``cas_small.casci`` on the molecule's RHF orbitals and reduces each pair of CAS states in
+different orbital sets to a non-orthogonal ``transform_ci`` and an active-space t-RDM (``cas_small``),
+on the device when the solver has ``cas_trans_rdm12_rows``.  Ground state only, as in the reference.
 """
 from __future__ import annotations
 
@@ -17,15 +22,33 @@ from .containers import TRDMContainer
 
 
 class CAS_EVCont_obj(TRDMContainer):
-    def __init__(self, ncas, neleca, casci_solver=None, pair_rdm_fun=None):
+    def __init__(self, ncas, neleca, casci_solver=None, pair_rdm_fun=None, cisolver=None):
         super().__init__()
         self.ncas = ncas
         self.neleca = neleca
         self.cascis = []
+        self.ens = []
         self.casci_solver = casci_solver
         self.pair_rdm_fun = pair_rdm_fun
+        self.cisolver = cisolver
+
+    def _append_own(self, mol):
+        """The built-in route: ``cas_small.casci`` and the pair reduction of ``cas_small`` (host or device)."""
+        from . import cas_small
+        state = cas_small.casci(mol, self.ncas, self.neleca, self.cisolver)
+        kets = self.cascis + [state]
+        # (a pair beyond the conditioning guard raises here: the container is then as it was)
+        if hasattr(self.cisolver, "cas_trans_rdm12_rows"):
+            ovlp, one, two = self.cisolver.cas_trans_rdm12_rows(state, kets)
+        else:
+            ovlp, one, two = cas_small.trans_rdm12_rows(state, kets, self.cisolver)
+        self.cascis.append(state)
+        self.ens.append(state.e_tot)
+        self._append_state(ovlp, one, two)
 
     def append_to_rdms(self, mol):
+        if self.cisolver is not None:
+            return self._append_own(mol)
         if self.casci_solver is None:
             try:
                 from pyscf.mcscf import CASCI
@@ -55,3 +78,5 @@ class CAS_EVCont_obj(TRDMContainer):
         """``CASCI_EVCont.py:345-361``."""
         self._prune_arrays(keep_ids)
         self.cascis = [self.cascis[i] for i in keep_ids]
+        if self.ens:
+            self.ens = [self.ens[i] for i in keep_ids]

@@ -166,6 +166,11 @@ SIGNATURES = {
     "evc_profile_select": (C.c_int, [C.c_uint]),
     "evc_profile_kernel": (C.c_char_p, [C.c_int]),
     "evc_trdm_plan_describe": (C.c_int, [C.POINTER(TrdmSet), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "evc_cas_expand_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "evc_cas_expand_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
+    "evc_cas_expand_describe": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "evc_release_workspace": (C.c_int, [C.c_void_p]),
 }
 # stages of evc_profile_stage (include/evcont_hip.h EVC_PROF_*)

@@ -8,7 +8,9 @@ plus ``trans_rdm12_rows(bra, kets, norb, nelec)``: one bra against all kets in o
 ``FCI_EVCont_obj.append_to_rdms`` needs for a new training state, ``trans_rdm12_rows_packed(..., layout, out_rows)``: the
 same call with its two-body rows written on the device in the evaluator's layout (``csrc/fci_pack.hip``; the training
 set of ``resident.ResidentFCI_EVCont_obj``), and ``transform_ci(ci, nelec, u)``
-(``csrc/fci_rotate.hip``), which rotates a state solved in another orbital basis into the OAO basis.  Opt in with
+(``csrc/fci_rotate.hip``), which rotates a state solved in another orbital basis into the OAO basis, and
+``cas_trans_rdm12_rows(bra, kets)``: the t-RDMs between CAS states in different orbital sets, expanded to all N orbitals
+on the device (``csrc/cas_expand.hip``; ``CAS_EVCont_obj(ncas, neleca, cisolver=DeviceFCI())``).  Opt in with
 ``FCI_EVCont_obj(cisolver=DeviceFCI(), cibasis="OAO")``, or ``cibasis="canonical"`` to solve in the Hartree-Fock basis,
 where the Davidson solver's diagonal preconditioner works best near equilibrium.
 
@@ -182,6 +184,7 @@ class DeviceFCI:
         self._tables = {}
         self._masks = {}    # (norb, nelec) -> occupation masks of the alpha / beta strings on the device (transform_ci)
         self._ws = None
+        self._cas_ws = None  # workspace of evc_cas_expand_rows (cas_trans_rdm12_rows)
         # id(host array) -> (host array, host copy of what was uploaded, device tensor): CI vectors already uploaded
         self._vecs = {}
 
@@ -474,7 +477,11 @@ class DeviceFCI:
         result has the same bits for every accepted value.  Without it the workspace keeps both matrices of minors
         resident where that takes at most ``ROTATE_RESIDENT_BYTES`` (up to about (14, (6, 6))) and is the least one
         beyond (7 MB instead of 2.7 GB at (16, (8, 8)))."""
-        nelec = _nelec(nelec)
+        out, na, nb = self._rotate(ci, _nelec(nelec), u)
+        return out.cpu().numpy().reshape(na, nb)
+
+    def _rotate(self, ci, nelec, u):
+        """``transform_ci`` with the result left on the device: ``(na * nb doubles, na, nb)``."""
         if isinstance(u, (tuple, list)):
             ua, ub = (np.ascontiguousarray(x, dtype=np.float64) for x in u)
         else:
@@ -503,7 +510,72 @@ class DeviceFCI:
         check(lib.evc_fci_rotate(norb, nelec[0], nelec[1], na, nb, dsa.data_ptr(), dsb.data_ptr(), ua.ctypes.data,
                                  ub.ctypes.data, dc.data_ptr(), out.data_ptr(), self._ws.data_ptr(), grant,
                                  self._stream()), "evc_fci_rotate")
-        return out.cpu().numpy().reshape(na, nb)
+        return out, na, nb
+
+    def cas_trans_rdm12_rows(self, bra, kets, layout=None, out_rows: Optional[torch.Tensor] = None):
+        """Overlaps and transition RDMs, in the OAO basis, of one CAS state against ``kets`` whose orbitals differ from
+        its own (``cas_small.CASState``; the statement is ``cas_small.trans_rdm12_rows``): the pair intermediates on the
+        host (m x m and N x m matrices), then per ket one ``evc_fci_rotate`` with ``u = s_eff^T`` scaled by ``fac``, one
+        ``evc_fci_trdm_rows`` call for all kets in the active space, and one ``evc_cas_expand_rows`` call
+        (``csrc/cas_expand.hip``) that expands its results to N orbitals with the core terms.  Nothing but the overlaps,
+        ``dm1`` and, without a layout, ``dm2`` comes back to the host.
+
+        ``layout=None`` returns ``(ovlp (K,), dm1 (K,N,N), dm2 (K,N,N,N,N))`` as numpy.  With ``layout`` ("pack2" /
+        "sym8") the two-body rows go into ``out_rows``, a contiguous ``(K, ld)`` float64 device tensor, in the format of
+        ``trans_rdm12_rows_packed``, and ``(ovlp, dm1)`` is returned.  A pair beyond the conditioning guard raises
+        ``ValueError`` before anything is launched."""
+        from . import cas_small
+        kets = list(kets)
+        if not kets:
+            raise EvcontHipError("DeviceFCI.cas_trans_rdm12_rows: no kets")
+        K, n, ncas, nelec = len(kets), int(bra.U.shape[0]), int(bra.ncas), _nelec(bra.nelecas)
+        lay = {None: _lib.LAYOUT_FULL6, "pack2": _lib.LAYOUT_PACK2, "sym8": _lib.LAYOUT_SYM8}.get(layout, layout)
+        if lay not in (_lib.LAYOUT_FULL6, _lib.LAYOUT_PACK2, _lib.LAYOUT_SYM8):
+            raise EvcontHipError(f"DeviceFCI.cas_trans_rdm12_rows: layout={layout!r}, expected None, 'pack2' or 'sym8'")
+        inter = [cas_small.pair_intermediates(bra, ket, f"(bra, ket {i})") for i, ket in enumerate(kets)]
+        lib, dta, dtb, na, nb, grant = self._setup(ncas, nelec)
+        dev = self._dev()
+        dkets = []
+        for ket, (fac, s_eff, _, _, _) in zip(kets, inter):
+            rotated, _, _ = self._rotate(ket.ci, nelec, np.ascontiguousarray(s_eff.T))
+            dkets.append(rotated.mul_(fac))
+        lib, dta, dtb, na, nb, grant = self._setup(ncas, nelec)      # (the rotation may have replaced the workspace)
+        # (not remembered: a state is a bra once, and as a ket it is uploaded for its rotation anew)
+        dbra = self._upload(bra.ci, na, nb, cache=False)
+        ovlp = torch.empty(K, dtype=F64, device=dev)
+        d1 =torch.empty((K, ncas, ncas), dtype=F64, device=dev)
+        d2 = torch.empty((K, ncas ** 4), dtype=F64, device=dev)
+        ptrs = (C.c_void_p * K)(*[t.data_ptr() for t in dkets])
+        check(lib.evc_fci_trdm_rows(ncas, na, nb, dta.data_ptr(), dtb.data_ptr(), dbra.data_ptr(), ptrs, K,
+                                    ovlp.data_ptr(), d1.data_ptr(), d2.data_ptr(), self._ws.data_ptr(), grant,
+                                    self._stream()), "evc_fci_trdm_rows")
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        A_act = up(np.stack([x[2] for x in inter]))                    # (K, n, ncas): orthogonal to each ket's core
+        B_act = up(np.stack([x[3] for x in inter]))
+        Qc = up(np.stack([x[4] for x in inter])) if bra.ncore else None
+        dm1 = torch.empty((K, n, n), dtype=F64, device=dev)
+        if lay == _lib.LAYOUT_FULL6:
+            rows = torch.empty((K, n ** 4), dtype=F64, device=dev)
+        else:
+            rows = out_rows
+            on_dev = torch.is_tensor(rows) and rows.device.type == dev.type and dev.index in (None, rows.device.index)
+            if not (on_dev and rows.dtype == F64 and rows.dim() == 2 and rows.shape[0] == K and rows.stride(1) == 1
+                    and (K == 1 or rows.stride(0) == rows.shape[1])):
+                raise EvcontHipError(f"DeviceFCI.cas_trans_rdm12_rows: out_rows must be a contiguous ({K}, ld) float64 "
+                                     f"tensor on {dev}")
+        need = lib.evc_cas_expand_workspace_bytes(n, ncas, K)
+        if need == 0:
+            check(-1, "evc_cas_expand_workspace_bytes")
+        if self._cas_ws is None or self._cas_ws.numel() < need:
+            self._cas_ws = None
+            self._cas_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib.evc_cas_expand_rows(n, ncas, K, A_act.data_ptr(), B_act.data_ptr(),
+                                      None if Qc is None else Qc.data_ptr(), ovlp.data_ptr(), d1.data_ptr(),
+                                      d2.data_ptr(), dm1.data_ptr(), lay, rows.data_ptr(), int(rows.shape[1]),
+                                      self._cas_ws.data_ptr(), need, self._stream()), "evc_cas_expand_rows")
+        if lay == _lib.LAYOUT_FULL6:
+            return ovlp.cpu().numpy(), dm1.cpu().numpy(), rows.cpu().numpy().reshape(K, n, n, n, n)
+        return ovlp.cpu().numpy(), dm1.cpu().numpy()
 
     def energy(self, h1, h2, ci, norb, nelec) -> float:
         dm1, dm2 = self.make_rdm12(ci, norb, nelec)

@@ -46,7 +46,8 @@ extern "C" {
                                  additive: evc_fci_rotate, evc_fci_rotate_workspace_bytes, EVC_PROF_FCI_ROTATE;
                                  additive: evc_fci_trdm_rows_packed, evc_fci_rows_packed_workspace_bytes,
                                  EVC_PROF_FCI_PACK; additive: evc_fci_spin_apply, evc_fci_spin_diag;
-                                 evc_trdm_plan_describe */
+                                 evc_trdm_plan_describe; additive: evc_cas_expand_rows,
+                                 evc_cas_expand_workspace_bytes, evc_cas_expand_describe */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -475,6 +476,33 @@ size_t evc_fci_rows_packed_workspace_bytes(int norb, int64_t na, int64_t nb, int
 int evc_fci_trdm_rows_packed(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
                              const double *bra, const double *const *kets, int nkets, double *ovlp, double *dm1,
                              int layout, double *rows, int64_t ld, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Transition RDMs between CAS states in different orbital sets (evcont_amd/cas_small.py states the reduction): the
+ * active-space t-RDMs of one bra against nkets kets, as evc_fci_trdm_rows writes them for the bra's vector and the
+ * rotated, scaled ket vectors, expanded into the OAO basis of n orbitals with the core contributions.  Per ket i, with
+ * A = A_act[i] (n, ncas; the bra's active orbitals made orthogonal to the core of ket i, so one per ket), B = B_act[i]
+ * (n, ncas), Q = Qc[i] (n, n; bra index first), S = ovlp[i]:
+ *   Qa = A d1[i]^T B^T,   dm1[i] = (2 S Q + Qa)^T,
+ *   dm2[p,q,r,s] = sum_tuvw d2[i][t,u,v,w] A[p,t] B[q,u] A[r,v] B[s,w]
+ *                + S (4 Q[p,q] Q[r,s] - 2 Q[p,s] Q[r,q]) + 2 Q[p,q] Qa[r,s] + 2 Qa[p,q] Q[r,s] - Q[p,s] Qa[r,q] - Qa[p,s] Q[r,q]
+ * Qc == NULL: no core orbitals (the Q terms are absent).  `layout`: EVC_LAYOUT_FULL6 writes the dense n^4 block of ket i
+ * at rows + i * ld (ld >= n^4); EVC_LAYOUT_PACK2 / EVC_LAYOUT_SYM8 write row i in the format of evc_fci_trdm_rows_packed
+ * (ld a multiple of 16, at least the layout's columns, the pad columns zero; the bits of the host codecs applied to the
+ * dense block).  Any other layout is refused.  1 <= ncas <= 16, ncas <= n <= 64, 1 <= nkets <= 512, ld < 2^31; every
+ * pointer a DEVICE pointer aligned to 16 bytes (ovlp is read on the device: no host synchronisation); ws_bytes >=
+ * evc_cas_expand_workspace_bytes(n, ncas, nkets) (0 outside the limits).  Everything invalid is refused before any
+ * launch.  The caller's stream, no allocation, no library state, no profile stage; no atomics and no split sums: the same
+ * bits from run to run, and row i of a call equals the single-ket call on ket i.
+ * evc_cas_expand_describe: one line per launch of an evc_cas_expand_rows call of that shape (kernel name with template
+ * arguments, grid; the per-ket launches once), a pure function of its arguments.  Writes at most buf_len - 1 characters
+ * and a NUL; returns the length of the whole text, -1 on an invalid argument.
+ * --------------------------------------------------------------------------------- */
+size_t evc_cas_expand_workspace_bytes(int n, int ncas, int nkets);
+int evc_cas_expand_rows(int n, int ncas, int nkets, const double *A_act, const double *B_act, const double *Qc,
+                        const double *ovlp, const double *d1, const double *d2, double *dm1, int layout, double *rows,
+                        int64_t ld, void *ws, size_t ws_bytes, void *stream);
+int evc_cas_expand_describe(int n, int ncas, int layout, char *buf, size_t buf_len);
 
 /* ---------------------------------------------------------------------------------
  * Vector work of an eigensolver around evc_fci_sigma (evcont_amd/fci_davidson.py: block Davidson with the diagonal of H
