@@ -325,11 +325,12 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
                  data_addition=data_addition, **kwargs)
 
 
-def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots):
+def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=()):
     """``evaluate(R (G,A,3)) -> (E (G,nroots), grads (G,nroots,A,3))`` for geometries of the s-Gaussian molecule of
     ``mols``, device-resident from the coordinates on: the training set and the batched evaluator are built once, every
     call uploads the coordinates, computes the AO integrals there (``hchain_device.DeviceSGaussians``) and runs the
-    batched several-roots call on them."""
+    batched several-roots call on them.  With ``observables``: ``(E, grads (G,1,A,3), props)`` of the highest root alone,
+    forces and observables from one solve (``BatchedEvaluator.multistate_properties``)."""
     from .ab_initio_eigenvector_continuation import resolve_compression
     from .ab_initio_gradients_loewdin import _batched_evaluator
     from .hchain_device import DeviceSGaussians
@@ -346,13 +347,27 @@ def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots):
     packed = t.layout == _lib.LAYOUT_SYM8 and t.n <= 64
 
     def evaluate(R):
-        E, _, grads = ev.multistate_energies_with_grads(sg.integrals(R, packed=packed), nroots)
-        return E, grads
+        aob = sg.integrals(R, packed=packed)
+        if not observables:
+            E, _, grads = ev.multistate_energies_with_grads(aob, nroots)
+            return E, grads
+        # the dipole integrals from the coordinates the call above left on the device: no second upload, and the step's
+        # download grows by the observables of the propagated root alone
+        Rd = sg.staged_coords(G)
+        root = nroots - 1
+        E, _, props, grads = ev.multistate_properties(
+            aob, nroots, [(root, root)], dip=sg.dipole_integrals(Rd) if "dipole" in observables else None,
+            charges=sg.charges, coords=Rd, return_forces=True, observables=observables)
+        return E, grads, props
 
     return evaluate
 
 
-def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_veloc=None, integrals="host"):
+_OBSERVABLES = {"dipole": "dipole", "mulliken": "mulliken_charges", "loewdin": "loewdin_charges"}
+
+
+def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_veloc=None, integrals="host",
+                observables=None):
     """Velocity-Verlet NVE of G trajectories on the continuation surface ``root`` (0 = ground state), advanced in lock
     step: every step is ONE batched call for all G geometries (``get_multistate_energies_with_grads``, all trajectories'
     roots 0 .. root in one pass).  ``mols``: the G initial geometries of one array-level molecule that can be rebuilt at
@@ -361,7 +376,12 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
     frame per step with ``coord``/``veloc`` (G,A,3), ``epot``/``ekin`` (G,) and ``time``.  Plain adiabatic dynamics:
     no surface hopping, and at (near-)degenerate roots the forces follow whichever eigenvector the solver returned.
     ``integrals``: "host" rebuilds every molecule with ``with_coords`` (numpy) at every step; "device" (s-Gaussian
-    molecules, ``evcont_amd.hchain``) uploads the (G,A,3) coordinates and computes the AO integrals on the device."""
+    molecules, ``evcont_amd.hchain``) uploads the (G,A,3) coordinates and computes the AO integrals on the device.
+    ``observables``: None (the frames above, nothing else) or a selection of "dipole", "mulliken", "loewdin": every frame
+    gains ``dipole`` (G,3) (atomic units, origin (0,0,0)) and ``mulliken_charges`` / ``loewdin_charges`` (G,A) of the
+    propagated root (plain Mulliken, not meta-Loewdin), from the solve that gives the forces; with
+    ``integrals="device"`` that adds the observables' G (3 + A) doubles per kind of charge to the step's download and
+    no upload."""
     from .ab_initio_gradients_loewdin import get_multistate_energies_with_grads
     mols = list(mols)
     root = int(root)
@@ -373,31 +393,45 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
     m = (np.asarray(mols[0].atom_mass_list(), dtype=np.float64) * AMU2AU)[:, None]
     v = np.zeros_like(R) if init_veloc is None else np.array(init_veloc, dtype=np.float64).reshape(R.shape)
 
+    observables = tuple(observables or ())
+    if set(observables) - set(_OBSERVABLES):
+        raise ValueError(f"unknown observables {observables!r} (known: {sorted(_OBSERVABLES)})")
+    # frame key -> (G, ...) array of the propagated root
+    observed = lambda props: {_OBSERVABLES[k]: props[_OBSERVABLES[k]][:, 0] for k in observables}
+
     if integrals == "device":
-        surfaces = _device_surfaces(mols, one_rdm, two_rdm, overlap, root + 1)
+        surfaces = _device_surfaces(mols, one_rdm, two_rdm, overlap, root + 1, observables)
 
         def evaluate(ms):
+            if observables:
+                E, grads, props = surfaces(R)
+                return E[:, root], grads[:, 0], observed(props)
             E, grads = surfaces(R)
-            return E[:, root], grads[:, root]
+            return E[:, root], grads[:, root], {}
 
         rebuild = lambda ms, R: ms
     else:
         def evaluate(ms):
+            if observables:
+                from .ab_initio_eigenvector_continuation import get_multistate_properties
+                E, props = get_multistate_properties(ms, one_rdm, two_rdm, overlap, root + 1, [(root, root)],
+                                                     return_forces=True)
+                return E[:, root], props["grads"][:, 0], observed(props)
             E, grads = get_multistate_energies_with_grads(ms, one_rdm, two_rdm, overlap, root + 1)
-            return E[:, root], grads[:, root]
+            return E[:, root], grads[:, root], {}
 
         rebuild = lambda ms, R: [m_.with_coords(r) for m_, r in zip(ms, R)]
 
-    e, g = evaluate(mols)
+    e, g, obs = evaluate(mols)
     frames = []
     for k in range(steps):
         frames.append({"coord": R.copy(), "veloc": v.copy(), "epot": e.copy(),
-                       "ekin": 0.5 * np.sum(m * v * v, axis=(1, 2)), "time": k * dt})
+                       "ekin": 0.5 * np.sum(m * v * v, axis=(1, 2)), "time": k * dt, **obs})
         if k == steps - 1:
             break
         a = -g / m
         R = _vv_drift(R, v, a, dt)
         mols = rebuild(mols, R)
-        e, g = evaluate(mols)
+        e, g, obs = evaluate(mols)
         v = _vv_kick(v, a, g, m, dt)
     return frames

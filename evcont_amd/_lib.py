@@ -60,6 +60,16 @@ class SgtoOutputs(C.Structure):
                 ("ipovlp", C.c_void_p), ("dhcore", C.c_void_p), ("eri_ip1", C.c_void_p), ("gnuc", C.c_void_p)]
 
 
+class PropertyInputs(C.Structure):
+    _fields_ = [("natm", C.c_int32), ("count", C.c_int32), ("S", C.c_void_p), ("dip", C.c_void_p),
+                ("aoslices", C.c_void_p), ("charges", C.c_void_p), ("coords", C.c_void_p), ("origin", C.c_double * 3)]
+
+
+class PropertyOutputs(C.Structure):
+    _fields_ = [("d_oao", C.c_void_p), ("d_ao", C.c_void_p), ("dipole", C.c_void_p), ("mulliken", C.c_void_p),
+                ("loewdin", C.c_void_p)]
+
+
 # symbol -> (restype, argtypes); also the list the CPU test checks against the header
 SIGNATURES = {
     "evc_abi_version": (C.c_int, []),
@@ -159,6 +169,12 @@ SIGNATURES = {
     "evc_sgto_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "evc_sgto_integrals_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(SgtoOutputs), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_sgto_dipole_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "evc_properties_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "evc_properties_roots_batch": (C.c_int, [C.POINTER(TrdmSet), C.POINTER(PropertyInputs), C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_int, C.POINTER(PropertyOutputs), C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_profile_begin": (C.c_int, [C.c_int]),
     "evc_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int)]),

@@ -236,3 +236,90 @@ def approximate_ground_state_OAO(mol, one_RDM, two_RDM, S, hermitian=True):
 def approximate_multistate_OAO(mol, one_RDM, two_RDM, S, nroots=1, hermitian=True):
     """Reference :214-250."""
     return _oao(mol, one_RDM, two_RDM, S, int(nroots), hermitian=bool(hermitian))
+
+
+def _dipole_inputs(mol, origin):
+    """``(dip (3,N,N), charges (A,), coords (A,3))`` of one molecule for the origin: an array-level molecule computes its
+    own dipole integrals (``dipole_integrals(origin)``, e.g. ``hchain.HChainMol``), a PySCF ``Mole`` gives
+    ``int1e_r`` under ``with_common_orig``."""
+    if is_array_mol(mol):
+        if not hasattr(mol, "dipole_integrals"):
+            raise ValueError("array-level molecule without dipole_integrals(origin): no AO dipole integrals")
+        return (np.asarray(mol.dipole_integrals(origin), dtype=np.float64), np.asarray(mol.charges, dtype=np.float64),
+                np.asarray(mol.coords, dtype=np.float64).reshape(-1, 3))
+    with mol.with_common_orig(origin):
+        dip = np.asarray(mol.intor("int1e_r", comp=3), dtype=np.float64)
+    return dip, np.asarray(mol.atom_charges(), dtype=np.float64), np.asarray(mol.atom_coords(), dtype=np.float64)
+
+
+def get_multistate_properties(mols, one_rdm, two_rdm, overlap, nroots=1, pairs=None, origin=None, hermitian=True,
+                              return_forces=False):
+    """Dipole moments, transition dipole moments and atomic charges of the lowest ``nroots`` continuation states at
+    every geometry of ``mols`` (geometries of ONE molecule), on the device in batches
+    (``BatchedEvaluator.multistate_properties``): what the reference computes per geometry on the host at the end of
+    its workflow (``scripts/MD/H2O-H3O+/evaluate_dipole_moment_charges_continuation.py:72-90``), for every root pair.
+
+    ``pairs``: (P,2) root pairs k <= l < nroots, default the diagonal; ``origin``: of the dipole operator, default
+    (0,0,0) (the dipole of a neutral molecule and every transition dipole between orthogonal states do not depend on
+    it).  Returns ``E (G,nroots)`` and a dict of ``dipole (G,P,3)`` in atomic units (diagonal slots: total dipole;
+    slot (k,l): the electronic transition dipole), ``mulliken_charges`` and ``loewdin_charges (G,P,A)``, ``C
+    (G,nroots,T)``; with ``return_forces`` also ``grads (G,P,A,3)`` of the same slots from the same solve.
+
+    The populations are PLAIN Mulliken (PySCF's ``mulliken_pop``) and Loewdin; the reference script's
+    ``mulliken_meta`` (meta-Loewdin, orthogonalised against PySCF's tabulated atomic reference orbitals) is not
+    provided.  For array-level molecules the dipole integrals come from the molecule (``dipole_integrals(origin)``);
+    for a PySCF ``Mole`` from ``mol.intor("int1e_r")`` under ``with_common_orig`` -- that branch is written against
+    PySCF's documented interface and has NOT been run: PySCF was not available where this was developed."""
+    from .ab_initio_gradients_loewdin import BATCH_WORKSPACE_BUDGET, _batched_evaluator
+    from .evaluator import DeviceAOBatch
+    import ctypes as C
+    from . import _lib
+    mols = list(mols)
+    if not mols:
+        raise ValueError("no geometries")
+    nroots = int(nroots)
+    origin = (0.0, 0.0, 0.0) if origin is None else tuple(float(x) for x in origin)
+    need_grad = bool(return_forces)
+    aos = [ao_arrays(m, need_grad=need_grad) for m in mols]
+    natm = int(np.asarray(aos[0].aoslices).shape[0])
+    if any(int(np.asarray(a.aoslices).shape[0]) != natm or a.S.shape != aos[0].S.shape for a in aos):
+        raise ValueError("get_multistate_properties: the geometries must be of one molecule")
+    t = _resident_trdms(one_rdm, two_rdm, overlap,
+                        resolve_compression("default", one_rdm, two_rdm, overlap,
+                                            mols[0] if not is_array_mol(mols[0]) else aos[0], hermitian=hermitian,
+                                            need_grad=need_grad))
+    if pairs is None:
+        pairs = [(k, k) for k in range(nroots)]
+    pairs = [tuple(int(x) for x in p) for p in np.asarray(pairs).reshape(-1, 2)]
+    npairs = len(pairs)
+    lib = _lib.load()
+    per_slot = (lib.evc_workspace_bytes_roots_batch(C.byref(t.cstruct), natm, 1, 1) if need_grad
+                else lib.evc_workspace_bytes_batch(C.byref(t.cstruct), natm, 1))
+    if per_slot == 0:
+        raise _lib.EvcontHipError("workspace size: " + lib.evc_last_error().decode())
+    per_geo = per_slot * (npairs if need_grad else 1)
+    chunk = max(1, min(len(mols), 4096 // npairs, BATCH_WORKSPACE_BUDGET // per_geo))
+    if chunk * npairs > 4096:
+        raise ValueError(f"{npairs} root pairs exceed the 4096 slots of one call")
+    slices = torch.from_numpy(np.ascontiguousarray(aos[0].aoslices, dtype=np.int64)).to(t.device)
+    E, Cs, grads, props = [], [], [], {}
+    for c0 in range(0, len(mols), chunk):
+        part = aos[c0: c0 + chunk]
+        ev = _batched_evaluator(t, natm, len(part))
+        aob = DeviceAOBatch.from_arrays(part, t.device, energy_only=not need_grad)
+        aob.aoslices = slices
+        dz = [_dipole_inputs(m, origin) for m in mols[c0: c0 + chunk]]
+        res = ev.multistate_properties(aob, nroots, pairs, dip=np.stack([d[0] for d in dz]), charges=dz[0][1],
+                                       coords=np.stack([d[2] for d in dz]), origin=origin, hermitian=hermitian,
+                                       return_forces=need_grad)
+        E.append(res[0])
+        Cs.append(res[1])
+        for k, v in res[2].items():
+            props.setdefault(k, []).append(v)
+        if need_grad:
+            grads.append(res[3])
+    out = {k: np.concatenate(v) for k, v in props.items()}
+    out["C"] = np.concatenate(Cs)
+    if need_grad:
+        out["grads"] = np.concatenate(grads)
+    return np.concatenate(E), out

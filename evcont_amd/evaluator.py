@@ -745,6 +745,110 @@ class _EvaluatorBase:
         return e, c, grads, D, Gm
 
 
+    # -- observables of several roots (evc_properties_roots_batch; one geometry: count = 1) ------------------------
+    def _properties_device(self, ao, coeffs: torch.Tensor, nvec: int, P: np.ndarray, dip, charges, coords, origin,
+                           want=("dipole", "mulliken", "loewdin")) -> dict:
+        """Enqueue ``evc_properties_roots_batch`` on the workspace as the energy call left it (phases A+B of ``ao``),
+        for the rows 0 .. nvec-1 of ``coeffs`` and the root pairs ``P`` (npairs,2) int32.  ``want``: among "d_oao",
+        "d_ao", "dipole", "mulliken", "loewdin".  Returns the device tensors, leading shape ``(npairs,) + _lead``,
+        populations not charges; no synchronisation."""
+        t, d = self.t, self.t.device
+        if self.natm < 1:
+            raise _lib.EvcontHipError("properties need an evaluator built with natm >= 1")
+        count = int(np.prod(self._lead, dtype=np.int64)) if self._lead else 1
+        npairs, n, A = int(P.shape[0]), t.n, self.natm
+        dev = lambda x, shape: (None if x is None else
+                                (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)))
+                                .to(device=d, dtype=F64).reshape(shape).contiguous())
+        need_dip = "dipole" in want
+        dip_d = dev(dip, self._lead + (3, n, n)) if need_dip else None
+        z_d = dev(charges, (A,)) if need_dip else None
+        r_d = dev(coords, self._lead + (A, 3)) if need_dip else None
+        if need_dip and (dip_d is None or z_d is None or r_d is None):
+            raise ValueError("the dipole needs dip, charges and coords")
+        need_slices = "mulliken" in want or "loewdin" in want
+        if need_slices and ao.aoslices is None:
+            raise ValueError("populations need the geometry's aoslices")
+        nbytes = self.lib.evc_properties_workspace_bytes(n, t.T, A, count, npairs)
+        if nbytes == 0:
+            raise _lib.EvcontHipError("evc_properties_workspace_bytes: " + self.lib.evc_last_error().decode())
+        scratch = getattr(self, "_prop_scratch", None)
+        if scratch is None or scratch.numel() < nbytes:
+            scratch = self._prop_scratch = torch.empty(nbytes, dtype=torch.uint8, device=d)
+        lead = (npairs,) + self._lead
+        shapes = {"d_oao": (n, n), "d_ao": (n, n), "dipole": (3,), "mulliken": (A,), "loewdin": (A,)}
+        res = {k: torch.zeros(lead + shapes[k], dtype=F64, device=d) for k in shapes if k in want}
+        p = lambda x: (x.data_ptr() if x is not None else None)
+        pin = _lib.PropertyInputs(natm=A, count=count, S=p(ao.S), dip=p(dip_d), aoslices=p(ao.aoslices), charges=p(z_d),
+                                  coords=p(r_d), origin=(C.c_double * 3)(*[float(x) for x in origin]))
+        pout = _lib.PropertyOutputs(**{k: p(res.get(k)) for k in shapes})
+        P = np.ascontiguousarray(P, dtype=np.int32)
+        check(self.lib.evc_properties_roots_batch(C.byref(t.cstruct), C.byref(pin), coeffs.data_ptr(), int(nvec),
+                                                  P.ctypes.data, npairs, C.byref(pout), self.ws.data_ptr(), self.ws_bytes,
+                                                  scratch.data_ptr(), int(scratch.numel()), self._sp()),
+              "evc_properties_roots_batch")
+        res["_keep"] = (dip_d, z_d, r_d, coeffs)     # inputs live until the caller synchronises
+        return res
+
+    def _multistate_properties(self, ao, nroots: int, pairs, dip, charges, coords, origin, hermitian: bool,
+                               return_dm_ao: bool, return_forces: bool, observables):
+        """What ``multistate_properties`` of both evaluators does; geometry axis (if any) still behind the pair axis."""
+        T = self.t.T
+        nroots = int(nroots)
+        if not 1 <= nroots <= T:
+            raise ValueError(f"nroots={nroots} out of range 1..{T}")
+        if pairs is None:
+            pairs = [(k, k) for k in range(nroots)]
+        P = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        grads = None
+        if return_forces:
+            # one solve: the gradient call and the properties call read the same phases A+B
+            e, c, grads, _, _ = self._gradient_roots(ao, nroots, P, False, False, hermitian)
+            if hermitian:
+                coeffs = self.coeffs
+            else:
+                blocks = np.zeros(self._lead + (T, T))
+                blocks[..., :nroots, :] = c
+                coeffs = torch.from_numpy(blocks).to(self.t.device)
+        elif hermitian:
+            self.enqueue(ao, nroots, energy_only=True)
+            coeffs = self.coeffs
+        else:
+            e, c, coeffs = self._host_coeffs(ao, nroots)
+            if coeffs.shape[-2] != T:                       # (one geometry: (nroots, T) rows)
+                blocks = torch.zeros((T, T), dtype=F64, device=self.t.device)
+                blocks[:nroots] = coeffs
+                coeffs = blocks
+        unknown = set(observables) - {"dipole", "mulliken", "loewdin"}
+        if unknown:
+            raise ValueError(f"unknown observables {sorted(unknown)} (known: 'dipole', 'mulliken', 'loewdin')")
+        want = tuple(observables) + (("d_ao",) if return_dm_ao else ())
+        res = self._properties_device(ao, coeffs, nroots, P, dip, charges, coords, origin, want)
+        self.synchronize()
+        if hermitian and not return_forces:
+            e = self.energy[..., :nroots].cpu().numpy().copy()
+            self._raise_if_nan(e[..., 0])
+            c = self.coeffs[..., :nroots, :].cpu().numpy().copy()
+        res.pop("_keep")
+        return e, c, P, {k: v.cpu().numpy() for k, v in res.items()}, grads
+
+    @staticmethod
+    def _property_dict(host: dict, P: np.ndarray, charges, move) -> dict:
+        """Populations -> charges (``Z - pop`` on diagonal slots, ``-pop`` on transition slots); ``move``: puts the
+        geometry axis in front of the pair axis."""
+        from .properties import charges_from_populations
+        Z = np.asarray(charges.cpu().numpy() if torch.is_tensor(charges) else charges, dtype=np.float64).reshape(-1)
+        out = {}
+        if "dipole" in host:
+            out["dipole"] = move(host["dipole"])
+        for k in ("mulliken", "loewdin"):
+            if k in host:
+                out[k + "_charges"] = charges_from_populations(move(host[k]), Z, P)
+        if "d_ao" in host:
+            out["dm_ao"] = move(host["d_ao"])
+        return out
+
+
 class BatchedEvaluator(_EvaluatorBase):
     """``count`` independent geometries per call (``evc_energy_with_grad_batch``): every launch covers
     the whole batch and the t-RDM is streamed once per up to 32 geometries.  Results stay on the device in
@@ -858,6 +962,31 @@ class BatchedEvaluator(_EvaluatorBase):
             res += (D.transpose(0, 1).cpu().numpy().copy(),
                     Gm.transpose(0, 1).cpu().numpy().copy().reshape(self.count, Gm.shape[0], -1))
         return res
+
+
+    def multistate_properties(self, aob: DeviceAOBatch, nroots: int, pairs=None, dip=None, charges=None, coords=None,
+                              origin=(0.0, 0.0, 0.0), hermitian: bool = True, return_dm_ao: bool = False,
+                              return_forces: bool = False, observables=("dipole", "mulliken", "loewdin")):
+        """Dipole moments, transition dipole moments and atomic charges of the lowest ``nroots`` roots of every geometry
+        of the batch, on the device from what the energy call left there (``evc_energy_with_grad_batch`` energy-only +
+        ``evc_properties_roots_batch``; numpy statement: ``evcont_amd.properties``).  ``pairs``: the same (P,2) list
+        k <= l < nroots for every geometry (default: the diagonal); slot (k,k) is state k, slot (k,l) the transition
+        with the weighting (c_k c_l^T + c_l c_k^T) / 2.  ``dip`` (G,3,N,N) = <mu| r - origin |nu>, ``charges`` (A,),
+        ``coords`` (G,A,3) Bohr: numpy or device tensors.  Returns ``E (G,nroots)``, ``C (G,nroots,T)`` and a dict of
+        ``dipole (G,P,3)`` (atomic units; diagonal slots: total, nuclei included; transition slots: -tr(P r)),
+        ``mulliken_charges`` and ``loewdin_charges (G,P,A)`` (``Z - pop`` on diagonal slots, ``-pop`` on transition
+        slots; plain Mulliken, not the reference script's meta-Loewdin ``mulliken_meta``) and, with ``return_dm_ao``,
+        ``dm_ao (G,P,N,N)``.  ``return_forces``: also ``grads (G,P,A,3)`` of the same slots as
+        ``multistate_energies_with_grads`` returns them, from the same energy phase (one solve per step).
+        ``observables``: which of "dipole", "mulliken", "loewdin" to compute and download.
+        ``hermitian=False``: the host eig selection (not on sym8).  G * P <= 4096."""
+        assert aob.count == self.count, "batch size is fixed at construction"
+        e, c, P, host, grads = self._multistate_properties(aob, nroots, pairs, dip, charges, coords, origin, hermitian,
+                                                           return_dm_ao, return_forces, observables)
+        props = self._property_dict(host, P, charges, lambda x: np.ascontiguousarray(np.swapaxes(x, 0, 1)))
+        if return_forces:
+            return e, c, props, grads[:, :, : self.natm].transpose(0, 1).cpu().numpy().copy()
+        return e, c, props
 
 
 class PipelinedBatchedEvaluator:
@@ -1048,3 +1177,18 @@ class ContinuationEvaluator(_EvaluatorBase):
         if return_density_matrices:
             return e, c, gr, D.cpu().numpy(), G.cpu().numpy()
         return e, c, gr
+
+
+    def multistate_properties(self, ao: DeviceAO, nroots: int, pairs=None, dip=None, charges=None, coords=None,
+                              origin=(0.0, 0.0, 0.0), hermitian: bool = True, return_dm_ao: bool = False,
+                              return_forces: bool = False, observables=("dipole", "mulliken", "loewdin")):
+        """``BatchedEvaluator.multistate_properties`` for one geometry (``evc_properties_roots_batch`` with count = 1 on
+        this evaluator's workspace): ``E (nroots,)``, ``C (nroots,T)`` and the dict of ``dipole (P,3)``,
+        ``mulliken_charges`` / ``loewdin_charges (P,A)`` and, on request, ``dm_ao (P,N,N)``; ``return_forces``: also
+        ``grads (P,A,3)``.  ``dip`` (3,N,N), ``charges`` (A,), ``coords`` (A,3)."""
+        e, c, P, host, grads = self._multistate_properties(ao, nroots, pairs, dip, charges, coords, origin, hermitian,
+                                                           return_dm_ao, return_forces, observables)
+        props = self._property_dict(host, P, charges, lambda x: x)
+        if return_forces:
+            return e, c, props, grads[:, : self.natm].cpu().numpy().copy()
+        return e, c, props

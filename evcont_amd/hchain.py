@@ -78,6 +78,29 @@ class HChainMol(AOArrays):
         """Atomic masses in amu (hydrogen-like centres: 1.008 per unit charge is only right for H)."""
         return np.full(self.natm, 1.008)
 
+    def dipole_integrals(self, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """AO dipole integrals ``<mu| r - origin |nu>`` (3,N,N) (PySCF: ``int1e_r`` under ``with_common_orig``), computed
+        on demand from ``coords``, ``exponents`` and ``coefficients``: per primitive pair ``(P - origin) S_prim`` with the
+        pair centre ``P`` of ``s_gaussian_mol`` (on coincident coordinates the centre exactly)."""
+        R = np.asarray(self.coords, dtype=np.float64).reshape(-1, 3)
+        A = R.shape[0]
+        ex = np.asarray(self.exponents, dtype=np.float64)
+        K = len(ex)
+        a = np.tile(ex, A)
+        owner = np.repeat(np.arange(A), K)
+        Rp = R[owner]
+        cn = np.tile(np.asarray(self.coefficients, dtype=np.float64), A) * (2.0 * a / np.pi) ** 0.75
+        Cm = np.zeros((A * K, A))
+        Cm[np.arange(A * K), owner] = cn
+        pp = a[:, None] + a[None, :]
+        AB = Rp[:, None, :] - Rp[None, :, :]
+        Sp = (np.pi / pp) ** 1.5 * np.exp(-a[:, None] * a[None, :] / pp * np.sum(AB * AB, axis=-1))
+        P = np.where(AB == 0.0, Rp[:, None, :],
+                     (a[:, None, None] * Rp[:, None, :] + a[None, :, None] * Rp[None, :, :]) / pp[:, :, None])
+        Dp = np.moveaxis(P - np.asarray(origin, dtype=np.float64), -1, 0) * Sp[None]
+        dip = np.einsum("pi,xpq,qj->xij", Cm, Dp, Cm, optimize=True)
+        return 0.5 * (dip + dip.transpose(0, 2, 1))
+
     def with_coords(self, coords, need_grad: bool = True) -> "HChainMol":
         """The same molecule (basis, charges, electrons) at new nuclear positions (Bohr)."""
         return s_gaussian_mol(coords, self.charges, self.exponents, self.coefficients, need_grad, self.nelec)

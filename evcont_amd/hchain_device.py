@@ -43,6 +43,7 @@ class DeviceSGaussians:
         self._aoslices = None      # device (A,2) int64, built once
         self._buffers = {}         # (G, need_grad, packed) -> dict of output tensors
         self._coords = {}          # G -> device (G,A,3) staging of host coordinates
+        self._dip = {}             # G -> device (G,3,N,N) dipole integrals
         self._ws = None
 
     @classmethod
@@ -74,6 +75,51 @@ class DeviceSGaussians:
             out.update(ipovlp=z(G, 3, n, n), dhcore=z(G, A, 3, n, n), gnuc=z(G, A, 3),
                        eri_ip1=z(G, 3, n, n, ms) if packed else z(G, 3, n, n, n, n))
         return out
+
+    def _device_coords(self, coords) -> torch.Tensor:
+        """``coords`` ((G,A,3) or (A,3); numpy or a device tensor) as a contiguous device (G,A,3) tensor; host
+        coordinates go through the staging tensor kept per G."""
+        if torch.is_tensor(coords):
+            R = coords.to(device=self.device, dtype=F64).reshape((-1,) + tuple(coords.shape[-2:])).contiguous()
+            self._setup(int(R.shape[1]))
+        else:
+            host = np.ascontiguousarray(coords, dtype=np.float64)
+            host = host.reshape((-1,) + host.shape[-2:])
+            G, A = host.shape[0], host.shape[1]
+            self._setup(A)
+            R = self._coords.get(G)
+            if R is None:
+                R = self._coords[G] = torch.empty((G, A, 3), dtype=F64, device=self.device)
+            R.copy_(torch.from_numpy(host))
+        if R.shape[-1] != 3:
+            raise ValueError("coords must be (G,A,3) or (A,3)")
+        return R
+
+    def staged_coords(self, G: int) -> torch.Tensor:
+        """The device (G,A,3) copy of the HOST coordinates the last ``integrals`` / ``dipole_integrals`` call of ``G``
+        geometries uploaded: what a following device call on the same geometries reads without a second upload."""
+        return self._coords[int(G)]
+
+    @property
+    def charges(self) -> torch.Tensor:
+        """Nuclear charges, device (A,)."""
+        return self._charges
+
+    def dipole_integrals(self, coords, origin=(0.0, 0.0, 0.0)) -> torch.Tensor:
+        """AO dipole integrals ``<mu| r - origin |nu>`` at ``coords`` as a device (G,3,N,N) tensor
+        (``evc_sgto_dipole_batch``; host statement: ``HChainMol.dipole_integrals``), enqueued on the current stream.  The
+        tensor is kept per G: a later call of the same G overwrites it."""
+        R = self._device_coords(coords)
+        G, A = int(R.shape[0]), int(R.shape[1])
+        dip = self._dip.get(G)
+        if dip is None:
+            dip = self._dip[G] = torch.zeros((G, 3, A, A), dtype=F64, device=self.device)
+        o = (C.c_double * 3)(*[float(x) for x in origin])
+        _lib.check(self.lib.evc_sgto_dipole_batch(
+            A, int(self.exponents.shape[0]), G, R.data_ptr(), self.exponents.ctypes.data, self.coefficients.ctypes.data,
+            C.cast(o, C.c_void_p), dip.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
+            "evc_sgto_dipole_batch")
+        return dip
 
     def integrals(self, coords, need_grad: bool = True, packed: bool = False, out: Optional[dict] = None) -> DeviceAOBatch:
         """The integrals at ``coords`` ((G,A,3) or (A,3), Bohr; numpy or a device tensor), enqueued on the current

@@ -13,6 +13,7 @@ one staged upload (12 MB at H30 with the compressed layout) and one graph launch
 
     python examples/h30_md.py [--atoms 30] [--train 20] [--steps 5] [--dt 5]
     python examples/h30_md.py --integrals device     # the AO integrals of every step on the device, from the coordinates
+    python examples/h30_md.py --integrals device --observables    # ... and dipole / Loewdin charges of every frame
 """
 import argparse
 import os
@@ -37,7 +38,12 @@ p.add_argument("--dt", type=float, default=5.0)
 p.add_argument("--integrals", choices=("host", "device"), default="host",
                help="where the AO integrals of a step are computed: numpy on the host (with_coords), or on the device "
                     "from the uploaded coordinates (hchain_device.DeviceSGaussians; the one-trajectory state_swarm)")
+p.add_argument("--observables", action="store_true",
+               help="with --integrals device: dipole moment and Loewdin charges of every frame from the step's own solve "
+                    "(state_swarm(..., observables=...)), written to dipole_EVCont_0.npy / charges_EVCont_0.npy")
 a = p.parse_args()
+if a.observables and a.integrals != "device":
+    p.error("--observables needs --integrals device (the swarm route)")
 norb = nelec = a.atoms
 init_dist = 1.9
 
@@ -92,9 +98,14 @@ if a.integrals == "device":
     DeviceSGaussians.integrals = timed_integrals
     t0 = time.time()
     swarm = state_swarm([init_mol], cont.one_rdm, cont.two_rdm, cont.overlap, 0, dt=a.dt, steps=a.steps,
-                        integrals="device")
+                        integrals="device", observables=("dipole", "loewdin") if a.observables else None)
     wall = time.time() - t0
     frames = [{"coord": f["coord"][0], "epot": f["epot"][0], "ekin": f["ekin"][0]} for f in swarm]
+    if a.observables:
+        np.save("dipole_EVCont_0.npy", np.array([f["dipole"][0] for f in swarm]))
+        np.save("charges_EVCont_0.npy", np.array([f["loewdin_charges"][0] for f in swarm]))
+        print(f"dipole of the last frame: {swarm[-1]['dipole'][0]} e Bohr; largest |Loewdin charge|: "
+              f"{np.abs(swarm[-1]['loewdin_charges'][0]).max():.4f}")
 else:
     scanner = get_scanner(init_mol, cont.one_rdm, cont.two_rdm, cont.overlap, compress="sym8")
     _with = init_mol.with_coords

@@ -9,6 +9,7 @@ solver with singlet symmetry would give them.  ``--spin-penalty 0`` shows the mi
 
     python examples/h6_excited_pes.py                              # needs a HIP device for the continuation itself
     python examples/h6_excited_pes.py --solver device-davidson     # the FCI and its eigensolver on the GPU as well
+    python examples/h6_excited_pes.py --oscillator                 # f_0k of the predicted states along the scan
 """
 import argparse
 import os
@@ -19,7 +20,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from evcont_amd.FCI_EVCont import FCI_EVCont_obj                                       # noqa: E402
-from evcont_amd.ab_initio_eigenvector_continuation import approximate_multistate_OAO   # noqa: E402
+from evcont_amd.ab_initio_eigenvector_continuation import approximate_multistate_OAO, \
+    get_multistate_properties                                                          # noqa: E402
+from evcont_amd.properties import oscillator_strength                                  # noqa: E402
 from evcont_amd.electron_integral_utils import get_basis, get_integrals               # noqa: E402
 from evcont_amd.fci_small import SmallFCI                                              # noqa: E402
 from evcont_amd.hchain import hydrogen_chain                                           # noqa: E402
@@ -43,6 +46,9 @@ def main():
                    help="shift of H + shift (S^2 - S(S+1)) in the FCI of the training states; 0: no penalty, and the "
                         "excited training states are triplets")
     p.add_argument("--points", type=int, default=25, help="geometries of the scan between 0.9 and 2.8 Bohr")
+    p.add_argument("--oscillator", action="store_true",
+                   help="also the oscillator strengths f_0k = 2/3 (E_k - E_0) |mu_0k|^2 of the predicted states along the "
+                        "scan (get_multistate_properties), written to oscillator_strengths_roots_*.txt")
     a = p.parse_args()
     solver = make_solver(a.solver, a.spin_penalty)
     test_dists = np.linspace(0.9, 2.8, a.points)
@@ -71,6 +77,14 @@ def main():
         err = np.abs(pred - exact[:, :nstates]).max(axis=0)
         print(f"roots_train={roots}: {cont.ntrain} states, max |error| of the {nstates} lowest surfaces: "
               + ", ".join(f"{x:.2e}" for x in err) + " Ha")
+        if a.oscillator and nstates > 1:
+            # f_0k along the scan: the transition dipoles of every geometry in one batched device call
+            pairs = [(0, k) for k in range(1, nstates)]
+            E, props = get_multistate_properties(test_mols, cont.one_rdm, cont.two_rdm, cont.overlap, nstates, pairs)
+            f = np.stack([oscillator_strength(E[:, 0], E[:, k], props["dipole"][:, p]) for p, (_, k) in enumerate(pairs)],
+                         axis=1)
+            np.savetxt(f"oscillator_strengths_roots_{tag}.txt", np.column_stack([test_dists, f]))
+            print(f"roots_train={roots}: f_0k along the scan between {f.min():.3e} and {f.max():.3e}")
 
 
 if __name__ == "__main__":

@@ -47,7 +47,8 @@ extern "C" {
                                  additive: evc_fci_trdm_rows_packed, evc_fci_rows_packed_workspace_bytes,
                                  EVC_PROF_FCI_PACK; additive: evc_fci_spin_apply, evc_fci_spin_diag;
                                  evc_trdm_plan_describe; additive: evc_cas_expand_rows,
-                                 evc_cas_expand_workspace_bytes, evc_cas_expand_describe */
+                                 evc_cas_expand_workspace_bytes, evc_cas_expand_describe; additive:
+                                 evc_properties_roots_batch, evc_properties_workspace_bytes, evc_sgto_dipole_batch */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -617,6 +618,65 @@ size_t evc_sgto_workspace_bytes(int natm, int nprim, int count);
 int evc_sgto_integrals_batch(int natm, int nprim, int count, const double *coords, const double *charges,
                              const double *exponents, const double *coefficients, const evc_sgto_outputs *out, int flags,
                              void *ws, size_t ws_bytes, void *stream);
+/* The AO dipole integrals of the same molecules, the one integral the call above does not produce (csrc/properties.hip;
+ * host statement: HChainMol.dipole_integrals): dip (count,3,N,N) = <mu| r - origin |nu>; per primitive pair
+ * (P - origin) S_prim with P as in s_gaussian_mol (on coincident coordinates the centre exactly).  coords DEVICE
+ * (count,natm,3); ex, co, origin HOST; limits and refusals of evc_sgto_integrals_batch (natm <= 96, nprim <= 8, positive
+ * exponents).  One sum per element over the primitive pairs in ascending order, mirrored: exactly symmetric, the same
+ * bits from run to run and for every batch size. */
+int evc_sgto_dipole_batch(int natm, int nprim, int count, const double *coords, const double *ex, const double *co,
+                          const double origin[3], double *dip, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Observables of continuation states (csrc/properties.hip; host statement: evcont_amd/properties.py; the reference's
+ * scripts/MD/H2O-H3O+/evaluate_dipole_moment_charges_continuation.py:72-90 per geometry on the host): for every root pair
+ * (k, l) of `pairs` and every geometry of a batch the predicted (transition) 1-RDM of the symmetric weighting
+ * W = (c_k c_l^T + c_l c_k^T) / 2 -- the quantity evc_outputs_roots.d_pred holds --, its back-rotation P = X D X^T to the AO
+ * basis, the dipole moment and the atomic populations.
+ *   ws       an evaluation workspace whose geometries 0 .. count-1 hold phases A+B of THESE geometries (the contract of
+ *            evc_phase_gradient_roots_batch; count = 1: the single-geometry entry points), ws_bytes >= count x the bytes
+ *            of one geometry (evc_workspace_bytes(t, in->natm)).  Only X of each geometry is read and nothing is written,
+ *            so a gradient call may follow or precede on the same workspace.
+ *   coeffs   DEVICE (count,T,T), rows 0 .. nvec-1 of each block used.
+ *   pairs    HOST (npairs,2), 0 <= k <= l < nvec, 1 <= count * npairs <= 4096.  Slots s = p * count + g; every output is
+ *            ROOT-PAIR-MAJOR.  Degeneracy warning: evc_phase_gradient_roots.
+ *   scratch  DEVICE, 16-byte aligned, at least evc_properties_workspace_bytes(n, ntrain, natm, count, npairs) bytes (0 on a
+ *            shape outside the limits): the row-chunk partial sums of D.  T^2 rows are cut into chunks that depend on T
+ *            alone and the chunks are added in ascending order: the same bits from run to run.
+ * Inputs, all DEVICE: S (count,N,N) (for mulliken), dip (count,3,N,N) = <mu| r - origin |nu>, charges (A), coords
+ * (count,A,3) (for dipole), aoslices (A,2) int64 shared by the batch (for mulliken / loewdin); origin by value.
+ * Outputs, each may be NULL:
+ *   d_oao    (npairs,count,N,N)   D
+ *   d_ao     (npairs,count,N,N)   P = X D X^T
+ *   dipole   (npairs,count,3)     atomic units; k == l: sum_A Z_A (R_A - origin) - tr(P r); k != l: -tr(P r)
+ *   mulliken (npairs,count,A)     populations sum_{mu in A} (P S)_mu,mu   (plain Mulliken, PySCF's mulliken_pop; not the
+ *                                 meta-Loewdin analysis of mulliken_meta)
+ *   loewdin  (npairs,count,A)     populations sum_{mu in A} D_mu,mu       (the OAO basis is the Loewdin basis)
+ * Populations, not charges.  Refused on the host before any launch (rc < 0): a null pointer (of an input only when an
+ * output that needs it is asked for), n > 96, T > 512, pairs out of order, count * npairs out of range, misaligned
+ * pointers, short scratch, short ws.  Caller's stream, no allocation, no profile stage.
+ * --------------------------------------------------------------------------------- */
+typedef struct evc_property_inputs {
+    int32_t natm;
+    int32_t count;
+    const double *S;         /* (count,N,N) */
+    const double *dip;       /* (count,3,N,N) */
+    const int64_t *aoslices; /* (A,2) [start,stop) */
+    const double *charges;   /* (A) */
+    const double *coords;    /* (count,A,3) Bohr */
+    double origin[3];
+} evc_property_inputs;
+typedef struct evc_property_outputs {
+    double *d_oao;
+    double *d_ao;
+    double *dipole;
+    double *mulliken;
+    double *loewdin;
+} evc_property_outputs;
+size_t evc_properties_workspace_bytes(int n, int ntrain, int natm, int count, int npairs);
+int evc_properties_roots_batch(const evc_trdm_set *t, const evc_property_inputs *in, const double *coeffs, int nvec,
+                               const int32_t *pairs, int npairs, const evc_property_outputs *out, const void *ws,
+                               size_t ws_bytes, void *scratch, size_t scratch_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Measurement hook (bench.py): while enabled, the fused pipeline records hipEvents on the launch

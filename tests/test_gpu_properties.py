@@ -1,0 +1,324 @@
+"""Observables of continuation states on the device (csrc/properties.hip: evc_properties_roots_batch,
+evc_sgto_dipole_batch) against the numpy statement evcont_amd/properties.py, at the project's parity bar of 1e-10
+absolute in atomic units (coordinates within 10 Bohr), through the C ABI at every shape at which a mechanism of the
+kernels can fail, through both evaluators, and end to end."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+BAR = 1e-10
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUTPUTS = ("d_oao", "d_ao", "dipole", "mulliken", "loewdin")
+
+
+def rows_min():
+    """Rows of one_rdm above which the row sum is split over blocks, read from the code under test."""
+    with open(os.path.join(REPO, "evcont_amd", "csrc", "properties.hip")) as f:
+        return int(re.search(r"constexpr int kPropRowsMin = (\d+);", f.read()).group(1))
+
+
+def slices_of(sizes):
+    stops = np.cumsum(sizes)
+    return np.stack([stops - np.array(sizes), stops], axis=1).astype(np.int64)
+
+
+class Problem:
+    """Random inputs of one evc_properties_roots_batch call and a hand-made evaluation workspace that holds X of every
+    geometry where carve() puts it (the head of a geometry's slot).  The kernels do not know physics: X is the Loewdin
+    transformation of a random overlap matrix, dip and S are random symmetric matrices."""
+
+    def __init__(self, n, T, G, pairs, sizes, seed):
+        from evcont_amd import _lib
+        from oracle import evcont_oracle as orc
+        self.lib = _lib.load()
+        rng = np.random.default_rng(seed)
+        self.n, self.T, self.G, self.A = n, T, G, len(sizes)
+        self.pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        self.nvec = int(self.pairs.max()) + 1
+        assert sum(sizes) == n and self.nvec <= T
+        self.aoslices = slices_of(sizes)
+        sym = lambda a: a + np.swapaxes(a, -1, -2)
+        B = rng.standard_normal((G, n, n))
+        self.S = B @ np.swapaxes(B, -1, -2) / n + np.eye(n)
+        self.X = np.stack([orc.loewdin_trafo(s) for s in self.S])
+        self.dip = sym(rng.standard_normal((G, 3, n, n)))
+        one = rng.standard_normal((T, T, n, n)) / n
+        self.one = 0.5 * (one + one.transpose(1, 0, 3, 2))
+        self.coeffs = rng.standard_normal((G, T, T)) / np.sqrt(T)
+        self.charges = rng.uniform(0.5, 3.0, self.A)
+        self.coords = rng.uniform(-5.0, 5.0, (G, self.A, 3))       # within 10 Bohr
+        self.origin = (0.4, -0.3, 1.2)
+        n2 = n * n
+        ld1 = n2 + (n2 & 1)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+        one_d = torch.zeros((T * T, ld1), dtype=torch.float64, device=DEV)
+        one_d[:, :n2] = up(self.one.reshape(T * T, n2))
+        self.dev = dict(one=one_d, S=up(self.S), dip=up(self.dip), coeffs=up(self.coeffs), charges=up(self.charges),
+                        coords=up(self.coords), aoslices=up(self.aoslices), dummy=torch.zeros(64, dtype=torch.float64, device=DEV))
+        P, M = T * (T + 1) // 2, n2 * (n2 + 1) // 2
+        self.t = _lib.TrdmSet(n=n, ntrain=T, layout=2, rows2=P, row_offset=0, rows2_total=P, cols2=M,
+                              ld2=(M + 15) // 16 * 16, ld1=ld1, two_rdm=self.dev["dummy"].data_ptr(),
+                              one_rdm=one_d.data_ptr(), s_train=self.dev["dummy"].data_ptr())
+        self.per_geo = self.lib.evc_workspace_bytes(C.byref(self.t), self.A)
+        assert self.per_geo >= n2 * 8
+        # nothing but X is read from it
+        self.ws = torch.empty(self.per_geo * G, dtype=torch.uint8, device=DEV)
+        for g in range(G):
+            self.ws[g * self.per_geo: g * self.per_geo + n2 * 8].view(torch.float64).copy_(up(self.X[g]).reshape(-1))
+        nbytes = self.lib.evc_properties_workspace_bytes(n, T, self.A, G, len(self.pairs))
+        assert nbytes > 0
+        self.scratch = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+
+    def call(self, want=OUTPUTS):
+        from evcont_amd import _lib
+        n, A, G, npairs = self.n, self.A, self.G, len(self.pairs)
+        shapes = {"d_oao": (n, n), "d_ao": (n, n), "dipole": (3,), "mulliken": (A,), "loewdin": (A,)}
+        # NaN-filled: an element the call leaves out shows
+        out = {k: torch.full((npairs, G) + shapes[k], float("nan"), dtype=torch.float64, device=DEV) for k in want}
+        d = self.dev
+        pin = _lib.PropertyInputs(natm=A, count=G, S=d["S"].data_ptr(), dip=d["dip"].data_ptr(),
+                                  aoslices=d["aoslices"].data_ptr(), charges=d["charges"].data_ptr(),
+                                  coords=d["coords"].data_ptr(), origin=(C.c_double * 3)(*self.origin))
+        pout = _lib.PropertyOutputs(**{k: (out[k].data_ptr() if k in out else None) for k in OUTPUTS})
+        rc = self.lib.evc_properties_roots_batch(C.byref(self.t), C.byref(pin), d["coeffs"].data_ptr(), self.nvec,
+                                                 self.pairs.ctypes.data, npairs, C.byref(pout), self.ws.data_ptr(),
+                                                 int(self.ws.numel()), self.scratch.data_ptr(), int(self.scratch.numel()),
+                                                 torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, self.lib.evc_last_error()
+        torch.cuda.synchronize()
+        return out
+
+    def reference(self):
+        from evcont_amd import properties as pr
+        per_geo = [pr.properties_host(self.one, self.X[g], self.coeffs[g], self.pairs, self.S[g], self.dip[g],
+                                      self.aoslices, self.charges, self.coords[g], self.origin) for g in range(self.G)]
+        return {k: np.stack([r[k] for r in per_geo], axis=1) for k in OUTPUTS}      # root-pair-major
+
+
+def compare(got, want, what):
+    worst = {}
+    for k in got:
+        a = got[k].cpu().numpy() if torch.is_tensor(got[k]) else got[k]
+        assert np.all(np.isfinite(a)), (what, k)
+        worst[k] = float(np.abs(a - want[k]).max())
+    print(what, " ".join(f"{k}={v:.2e}" for k, v in worst.items()))
+    assert max(worst.values()) < BAR, (what, worst)
+
+
+DIAG3 = [(0, 0), (0, 1), (1, 1)]
+# n, T, G, pairs, AO counts per atom: every N that is no multiple of a tile, both sides of N = 32 | 33 and 64 | 65 (the
+# three tilings of prop_ao_kernel), the limit 96; 1, 6 and 33 slots (33 crosses a 32-slot group); atoms with unequal AO
+# counts and an atom with one AO
+SHAPES = [
+    (5, 2, 1, [(0, 0)], (4, 1)),
+    (6, 3, 2, DIAG3, (1, 2, 3)),
+    (17, 5, 11, DIAG3, (1, 7, 9)),
+    (33, 3, 2, DIAG3, (16, 1, 16)),
+    (64, 2, 1, [(0, 1)], (30, 33, 1)),
+    (65, 2, 2, DIAG3, (1, 31, 33)),
+    (96, 2, 1, [(0, 0), (0, 1)], (1, 47, 48)),
+]
+
+
+@pytest.mark.parametrize("n,T,G,pairs,sizes", SHAPES, ids=[f"n{s[0]}t{s[1]}g{s[2]}p{len(s[3])}" for s in SHAPES])
+def test_abi_parity_and_bitwise_repeat(n, T, G, pairs, sizes):
+    pb = Problem(n, T, G, pairs, sizes, seed=100 + n)
+    first = pb.call()
+    compare(first, pb.reference(), f"n={n} T={T} G={G} P={len(pairs)}:")
+    second = pb.call()
+    for k in OUTPUTS:                 # fixed-order reductions: the same bits from run to run
+        assert torch.equal(first[k], second[k]), k
+
+
+@pytest.mark.parametrize("T", [17, 24])
+def test_split_row_sum(T):
+    """T^2 above the threshold read from the code: the rows of one_rdm are split over blocks and added in order."""
+    assert T * T > rows_min() >= 16 * 16
+    pb = Problem(5, T, 2, [(0, 0), (3, T - 1), (T - 1, T - 1)], (2, 3), seed=7 + T)
+    first = pb.call()
+    compare(first, pb.reference(), f"split T={T}:")
+    second = pb.call()
+    assert all(torch.equal(first[k], second[k]) for k in OUTPUTS)
+
+
+def test_every_output_may_be_null():
+    pb = Problem(6, 3, 2, DIAG3, (1, 2, 3), seed=11)
+    full = pb.call()
+    for skip in OUTPUTS:
+        part = pb.call(tuple(k for k in OUTPUTS if k != skip))
+        assert skip not in part
+        for k in part:
+            assert torch.equal(part[k], full[k]), (skip, k)
+    for only in OUTPUTS:
+        one = pb.call((only,))
+        assert torch.equal(one[only], full[only]), only
+
+
+def host_reference(one, C_rows, pairs, aos, dip, charges, coords, origin):
+    """properties_host per geometry with the oracle's Loewdin transformation; geometry-major (G,P,...)."""
+    from evcont_amd import properties as pr
+    from oracle import evcont_oracle as orc
+    res = [pr.properties_host(one, orc.loewdin_trafo(ao.S), C_rows[g], pairs, ao.S, dip[g], ao.aoslices, charges,
+                              coords[g], origin) for g, ao in enumerate(aos)]
+    return {k: np.stack([r[k] for r in res]) for k in OUTPUTS}
+
+
+def check_props(props, ref, pairs, charges, what):
+    from evcont_amd import properties as pr
+    want = {"dipole": ref["dipole"], "mulliken_charges": pr.charges_from_populations(ref["mulliken"], charges, pairs),
+            "loewdin_charges": pr.charges_from_populations(ref["loewdin"], charges, pairs), "dm_ao": ref["d_ao"]}
+    compare({k: props[k] for k in props}, want, what)
+
+
+@pytest.mark.parametrize("n,T", [(5, 2), (6, 3), (5, 5)])
+def test_batched_evaluator_against_host_and_the_roots_call(n, T):
+    """multistate_properties on the workspace the energy call left, with the eigenvectors it solved for; d_oao is the
+    d_pred of evc_phase_gradient_roots_batch; and the properties call writes nothing into the workspace: a gradient
+    call after it returns the forces it returns without it."""
+    from evcont_amd import _lib
+    from evcont_amd.evaluator import BatchedEvaluator, DeviceAOBatch, DeviceTRDMs
+    from evcont_amd.synthetic import make_ao_arrays, make_trdms, pack_rows
+    G, A, nroots = 2, 2, 2
+    rng = np.random.default_rng(n * 10 + T)
+    S, one, two = make_trdms(n, T, 300 + n + T)
+    aos = [make_ao_arrays(n, A, 310 + k, ao_sizes=(n - 1, 1)) for k in range(G)]
+    dip = rng.standard_normal((G, 3, n, n))
+    dip = dip + dip.transpose(0, 1, 3, 2)
+    charges, coords, origin = np.array([2.0, 1.0]), rng.uniform(-4, 4, (G, A, 3)), (0.1, 0.2, -0.3)
+    ev = BatchedEvaluator(DeviceTRDMs(one, pack_rows(two, True, True), S, DEV), A, G)
+    aob = DeviceAOBatch.from_arrays(aos, DEV)
+    E, Cs, props = ev.multistate_properties(aob, nroots, DIAG3, dip=dip, charges=charges, coords=coords, origin=origin,
+                                            return_dm_ao=True)
+    assert props["dipole"].shape == (G, 3, 3) and props["mulliken_charges"].shape == (G, 3, A)
+    check_props(props, host_reference(one, Cs, DIAG3, aos, dip, charges, coords, origin), DIAG3, charges,
+                f"batched n={n} T={T}:")
+    # the forces of the same slots without a properties call
+    E0, C0, g0, D0, _ = ev.multistate_energies_with_grads(aob, nroots, DIAG3, return_density_matrices=True)
+    assert np.abs(E - E0).max() < BAR
+    # energy phase, properties, then the gradient phase on the same workspace
+    P = np.ascontiguousarray(np.asarray(DIAG3, dtype=np.int32))
+    ev.enqueue(aob, nroots, energy_only=True)
+    res = ev._properties_device(aob, ev.coeffs, nroots, P, None, None, None, origin, want=("d_oao",))
+    grads = torch.zeros((3, G, A, 3), dtype=torch.float64, device=DEV)
+    out = _lib.OutputsRoots(grad=grads.data_ptr(), d_pred=None, g_pred=None)
+    g = aob.cstruct()
+    ev._call("evc_phase_gradient_roots", C.byref(g), ev.coeffs.data_ptr(), nroots, P.ctypes.data, 3, C.byref(out), 0)
+    ev.synchronize()
+    d_oao = res["d_oao"].transpose(0, 1).cpu().numpy()
+    g1 = grads.transpose(0, 1).cpu().numpy()
+    print(f"n={n} T={T}: max |d_oao - d_pred| = {np.abs(d_oao - D0).max():.2e}, max |dgrad| = {np.abs(g1 - g0).max():.2e}")
+    assert np.abs(d_oao - D0).max() < BAR
+    assert np.abs(g1 - g0).max() < BAR
+    # forces and observables from one solve
+    E2, C2, props2, g2 = ev.multistate_properties(aob, nroots, DIAG3, dip=dip, charges=charges, coords=coords,
+                                                  origin=origin, return_forces=True)
+    assert np.abs(g2 - g0).max() < BAR and np.abs(props2["dipole"] - props["dipole"]).max() < BAR
+
+
+def test_single_geometry_evaluator_and_the_large_T_golden():
+    """count = 1 through ContinuationEvaluator, on the T = 40 golden case (large-T subspace kernel; 1600 rows of
+    one_rdm: the split row sum)."""
+    from conftest import ao_from_golden
+    from evcont_amd.evaluator import ContinuationEvaluator, DeviceAO, DeviceTRDMs
+    with np.load(os.path.join(REPO, "tests", "golden", "largeT_n3t40a2.npz")) as z:
+        g = {k: z[k] for k in z.files}
+    assert 40 * 40 > rows_min()
+    ao = ao_from_golden(g)
+    rng = np.random.default_rng(40)
+    dip = rng.standard_normal((3, 3, 3))
+    dip = dip + dip.transpose(0, 2, 1)
+    charges, coords, origin = np.array([1.0, 2.0]), rng.uniform(-3, 3, (2, 3)), (0.0, 0.5, 0.0)
+    pairs = [(0, 0), (0, 2), (1, 1), (1, 2), (2, 2)]
+    ev = ContinuationEvaluator(DeviceTRDMs(g["one_RDM"], g["two_RDM_pack2"], g["S_train"], DEV), 2)
+    E, Cs, props = ev.multistate_properties(DeviceAO.from_arrays(ao, DEV), 3, pairs, dip=dip, charges=charges,
+                                            coords=coords, origin=origin, return_dm_ao=True)
+    assert E.shape == (3,) and props["dipole"].shape == (5, 3)
+    ref = host_reference(g["one_RDM"], Cs[None], pairs, [ao], dip[None], charges, coords[None], origin)
+    check_props(props, {k: v[0] for k, v in ref.items()}, pairs, charges, "single, T=40:")
+
+
+def h_molecules():
+    from evcont_amd.hchain import hydrogen_chain, s_gaussian_mol
+    from test_properties_host import H4_CHARGES, H4_COORDS
+    return {"H2": hydrogen_chain(2, 1.4, need_grad=False), "H10": hydrogen_chain(10, 1.8, need_grad=False),
+            "H4": s_gaussian_mol(H4_COORDS, H4_CHARGES, need_grad=False)}
+
+
+@pytest.mark.parametrize("name", ["H2", "H10", "H4"])
+@pytest.mark.parametrize("G", [1, 3])
+@pytest.mark.parametrize("origin", [(0.0, 0.0, 0.0), (0.7, -1.3, 2.1)])
+def test_sgto_dipole_integrals(name, G, origin):
+    from evcont_amd.hchain_device import DeviceSGaussians
+    mol = h_molecules()[name]
+    rng = np.random.default_rng(G)
+    R = np.stack([mol.coords + (0.05 * rng.standard_normal(mol.coords.shape) if k else 0.0) for k in range(G)])
+    sg = DeviceSGaussians.from_mol(mol, device=DEV)
+    got = sg.dipole_integrals(R, origin).clone()
+    again = sg.dipole_integrals(torch.from_numpy(R).to(DEV), origin)      # (a device tensor of coordinates)
+    torch.cuda.synchronize()
+    want = np.stack([mol.with_coords(r, need_grad=False).dipole_integrals(origin) for r in R])
+    a = got.cpu().numpy()
+    print(f"{name} G={G} origin={origin}: max |d dip| = {np.abs(a - want).max():.2e}")
+    assert a.shape == (G, 3, mol.natm, mol.natm) and np.abs(a - want).max() < BAR
+    assert torch.equal(got, again) and np.array_equal(a, a.transpose(0, 1, 3, 2))
+
+
+def test_hellmann_feynman_through_the_device_energy_path():
+    """The check of tests/test_properties_host.py with the energies of get_multistate_energies_with_grads at hcore +- F
+    r_x and the dipole of get_multistate_properties, field and tolerance as derived there."""
+    from evcont_amd.ab_initio_eigenvector_continuation import get_multistate_properties
+    from evcont_amd.ab_initio_gradients_loewdin import get_multistate_energies_with_grads
+    from test_properties_host import HF_FIELD, HF_TOL, h4_problem, in_field
+    mol, S_train, one, two = h4_problem()
+    E, _ = get_multistate_energies_with_grads([in_field(mol, HF_FIELD), in_field(mol, -HF_FIELD)], one, two, S_train, 2)
+    E0, props = get_multistate_properties([mol], one, two, S_train, 2)
+    nuc = np.asarray(mol.charges) @ mol.coords
+    tr_pr = nuc[0] - props["dipole"][0, :, 0]             # diagonal slots: dipole = nuclei - tr(P r)
+    fd = (E[0] - E[1]) / (2.0 * HF_FIELD)
+    print("central difference", fd, "tr(P r_x)", tr_pr, "gap %.3e" % np.abs(fd - tr_pr).max())
+    assert np.abs(tr_pr).min() > 1e-2
+    assert np.abs(fd - tr_pr).max() < HF_TOL
+
+
+def test_swarm_observables_match_a_host_recomputation():
+    """Three steps of state_swarm(integrals="device", observables=...): every frame's dipole and Loewdin charges are those
+    of a host evaluation at the frame's coordinates, and without observables the frames are what they were."""
+    from evcont_amd.FCI_EVCont import FCI_EVCont_obj
+    from evcont_amd.MD_utils import state_swarm
+    from evcont_amd.fci_small import SmallFCI
+    from evcont_amd.hchain import hydrogen_chain, s_gaussian_mol
+    from evcont_amd import properties as pr
+    from oracle import evcont_oracle as orc
+    cont = FCI_EVCont_obj(cisolver=SmallFCI(), cibasis="OAO")
+    for d in (1.5, 2.0, 2.6):
+        cont.append_to_rdms(hydrogen_chain(4, d, need_grad=False))
+    S, one, two = cont.overlap, cont.one_rdm, cont.two_rdm
+    base = np.zeros((4, 3))
+    base[:, 0] = 1.9 * np.arange(4)
+    mols = [s_gaussian_mol(base + 0.08 * np.random.default_rng(s).standard_normal((4, 3))) for s in (5, 6)]
+    plain = state_swarm(mols, one, two, S, root=1, dt=4.0, steps=3, integrals="device")
+    frames = state_swarm(mols, one, two, S, root=1, dt=4.0, steps=3, integrals="device",
+                         observables=("dipole", "loewdin"))
+    assert len(frames) == 3 and set(frames[0]) == set(plain[0]) | {"dipole", "loewdin_charges"}
+    worst = 0.0
+    for f, f0 in zip(frames, plain):
+        assert np.abs(f["coord"] - f0["coord"]).max() < BAR and np.abs(f["epot"] - f0["epot"]).max() < BAR
+        assert f["dipole"].shape == (2, 3) and f["loewdin_charges"].shape == (2, 4)
+        for g, R in enumerate(f["coord"]):
+            mol = s_gaussian_mol(R, need_grad=False)
+            b = orc.AOBundle(mol.S, mol.hcore, mol.eri, mol.ipovlp, mol.dhcore, mol.eri_ip1, mol.aoslices, mol.enuc,
+                             mol.gnuc)
+            _, Cr = orc.approximate_multistate_OAO(b, one, two, S, 2)
+            ref = pr.properties_host(one, orc.loewdin_trafo(mol.S), Cr, [(1, 1)], mol.S, mol.dipole_integrals(),
+                                     mol.aoslices, mol.charges, R)
+            worst = max(worst, np.abs(f["dipole"][g] - ref["dipole"][0]).max(),
+                        np.abs(f["loewdin_charges"][g] - (mol.charges - ref["loewdin"][0])).max())
+    print("swarm observables: max deviation from the host recomputation = %.2e" % worst)
+    assert worst < BAR
