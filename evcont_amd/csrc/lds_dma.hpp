@@ -1,5 +1,5 @@
 // LDS-DMA (global_load_lds_dwordx4: global memory straight into LDS, no VGPRs in between) and its waits.  The only place
-// that spells the instruction: K5 (gemv_lds.hip), K8 (gemv_cols_lds.hip) and the pair steps of pair_dma.hip include it.
+// that spells the instruction: K5 (gemv_lds.hip), K8 (gemv_cols_lds.hip) and the pair steps of pair_dma.hip (through pair_dma.hpp) include it.
 #pragma once
 #include "common.hpp"
 

@@ -21,48 +21,9 @@
 // The pipeline around these pieces is pt_pipe_kernel's: one matrix per iteration, result i-1 staged during the H phase
 // of matrix i, one barrier per tile of eight leading pairs, tile j written out during the N phases of the two
 // iterations behind its barrier, two workgroups per CU.
-#include "common.hpp"
-#include "lds_dma.hpp"
-#include "pair_plan.hpp"
-#include "pair_rows.hpp"
+#include "pair_dma.hpp"
 
 namespace evc {
-
-namespace {
-
-// (kPdMaxN and the LDS layout constants kPd*: pair_plan.hpp, the plans size the launches from them)
-
-// (the LDS-DMA load glds_s and the counted waits wait_vm_dyn / wait_vm_dyn8: lds_dma.hpp)
-
-// 16-byte store, scalar base + 32-bit lane offset (the compiler forms a 64-bit vector address for the same C++)
-__device__ __forceinline__ void gstore16(unsigned voff, d2 v, const void *sbase) {
-    asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-// an address the compiler shall not take apart (it folds constants out of it and leaves `v_add_u32 v, 0, v` behind)
-__device__ __forceinline__ unsigned opaque(unsigned x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-// LDS accesses at integer byte addresses (through the `lds` array the compiler adds the array's base -- the literal 0 --
-// with a vector instruction per access in some of the unrolled phases)
-typedef __attribute__((address_space(3))) double lds_f64;
-typedef __attribute__((address_space(3))) float lds_f32;
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) f2 lds_f2;
-__device__ __forceinline__ double lds_ld(unsigned addr) { return *(lds_f64 *)(uintptr_t)addr; }
-__device__ __forceinline__ void lds_st(unsigned addr, double v) { *(lds_f64 *)(uintptr_t)addr = v; }
-typedef __attribute__((address_space(3))) d2 lds_d2;
-__device__ __forceinline__ d2 lds_ld2(unsigned addr) { return *(lds_d2 *)(uintptr_t)addr; }
-
-// (memory, LDS and scalar instructions at a higher priority than the MFMAs: a wave that issues MFMAs back to back
-//  otherwise keeps the issue port from its SIMD mate's loads and stores, profiles/mfma_f64_coissue.txt)
-#ifdef EVC_PTD_NO_SETPRIO
-#define EVC_PTD_PRIO(x_) do { } while (0)
-#else
-#define EVC_PTD_PRIO(x_) __builtin_amdgcn_s_setprio(x_)
-#endif
-
-}  // namespace
 
 // arguments of y2d_kernel: the Y2 contraction alone, or what it adds to the first gradient-side pair step
 struct Y2dArgs {
@@ -76,8 +37,7 @@ struct Y2dArgs {
 // MODE 1: the 8-fold compressed packed vector packed[tri(u, v)], u = tri(r',s') >= v = tri(p,q), times the
 //         multiplicities of both pairs (and diag_mult on u == v): the write-out walks the rows u = ur + 64 k from 0 with
 //         lane-constant offsets tri(u) and skips the passes above the diagonal (k < v / 64, wave-uniform); the pass that
-//         holds the diagonal takes a slower, predicated body, once per tile.  Its stores vary from tile to tile, so here
-//         the wait for an operand row is vmcnt(0) (the stores behind it are a phase old by then).
+//         holds the diagonal takes a slower, predicated body, once per tile (store_pass).
 //
 // Y2 (MODE 0, the first gradient-side step, ct = 1): the H = M_e X this step forms is T_e X^T of the Y2 contraction
 //   Y2 = sum_e mult(e) T_e X^T M1_e   (ab_initio_gradients_loewdin.py:210-232),
@@ -87,7 +47,6 @@ struct Y2dArgs {
 // B operand; H M1_e wants it as the A operand (rows on lanes): the wave writes it into its LDS square during the first
 // N-phase steps and reads the fragments back during the last ones, all at lane-constant addresses.  The M1 row comes
 // by LDS-DMA into a second row of the wave: fragments read during the Y phase, the next row requested behind them.
-// Every counted wait gets the DMA instructions and stores that are younger than the row it waits for.
 //
 // DOT (MODE 0, the second gradient-side step): the result R_e = row e = tri(hi, lo) of the AO-basis 2-RDM is not written
 // but contracted where it stands in the stage, as the pair blocks of ip1_dh_kernel (ip1.hip) contract it:
@@ -103,8 +62,7 @@ struct Y2dArgs {
 // 96 VGPRs: ONE workgroup per CU (the launch is bound by the int2e_ip1 stream, not by the MFMAs), tiles per workgroup as
 // for the Y2 pair step.  Behind pass 7 of a tile each wave adds the six sums of its two pairs over its lanes (DPP and one
 // shuffle) into LDS behind the stage (one buffer per tile parity); the first 48 threads write the tile's 48 entries
-// behind the next barrier.  The int2e_ip1 loads are buffer loads the compiler counts; the wait for an operand row is
-// vmcnt(0) here.
+// behind the next barrier.
 template <int MODE, bool Y2, bool DOT = false>
 __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dArgs &y, const PairDotArgs &dt = PairDotArgs{}) {
     constexpr int KS = 8, NT = 2;
@@ -148,20 +106,11 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
             fa[rt][kk] = (r < n && s < n) ? rowb + 8u * (unsigned)(dw + hi * (hi + 1) / 2 + lo) : rowb + kPdRaw * 1024;
         }
     if (lane < 8) *reinterpret_cast<double *>(lds + rowb + kPdRaw * 1024 + 8 * lane) = 0.0;
-    const unsigned wbytes = (unsigned)(((npairs + dw) * 8 + 15) & ~15);   // bytes of the window
-    unsigned vo[kPdRaw];   // lanes past the end re-read the first granule
-#pragma unroll
-    for (unsigned u = 0; u < kPdRaw; ++u) {
-        const unsigned o = 1024u * u + 16u * (unsigned)lane;
-        vo[u] = o < wbytes ? o : 0u;
-    }
-    const int npieces = __builtin_amdgcn_readfirstlane((int)((wbytes + 1023u) >> 10));
+    const RowDma dma((unsigned)(((npairs + dw) * 8 + 15) & ~15), lane);   // (the bytes of the window)
+    const int npieces = dma.npieces;
     auto dma_row = [&](int e) {
         const int ec = e < npairs ? e : wave;
-        const char *src = reinterpret_cast<const char *>(in + (int64_t)ec * in_ld) - 8 * dw;
-#pragma unroll
-        for (unsigned u = 0; u < kPdRaw; ++u)
-            if ((int)u < npieces) glds_s(vo[u], src, rowb + 1024u * u);
+        dma.request(reinterpret_cast<const char *>(in + (int64_t)ec * in_ld) - 8 * dw, rowb);
     };
     dma_row(e0);
     // Y2: the M1 row of the same pair (rows on 16-byte granules: the launch checks it, the window is the SB row's)
@@ -169,10 +118,7 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
     constexpr unsigned kRowM = 4 * kPdRB;   // the wave's M1 row: this far behind its SB row
     [[maybe_unused]] auto dma_mrow = [&](int e) {
         const int ec = e < npairs ? e : wave;
-        const char *src = reinterpret_cast<const char *>(M1 + (int64_t)ec * in_ld);
-#pragma unroll
-        for (unsigned u = 0; u < kPdRaw; ++u)
-            if ((int)u < npieces) glds_s(vo[u], src, rowb + kRowM + 1024u * u);
+        dma.request(reinterpret_cast<const char *>(M1 + (int64_t)ec * in_ld), rowb + kRowM);
     };
     if constexpr (Y2) {
         if (lane < 8) *reinterpret_cast<double *>(lds + rowb + kRowM + kPdRaw * 1024 + 8 * lane) = 0.0;
@@ -229,8 +175,6 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
         }
     }
     const int wrows = DOT ? npairs : npairs - 16 * wave;   // pass k valid <=> 64 k < wrows (DOT: every wave takes all 64 rows)
-    // stores of an N phase that are younger than its DMA (passes c = 1..3 of the phase): what the wait for the next
-    // operand row leaves in flight
     int vmask = 0;   // bit k: this wave writes pass k
 #pragma unroll
     for (int k = 0; k < 8; ++k) vmask |= (64 * k < wrows) ? 1 << k : 0;
@@ -241,6 +185,34 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
         cntA += (64 * c < wrows) ? 1 : 0;
         cntB += (64 * (4 + c) < wrows) ? 1 : 0;
     }
+    // THE COUNTED WAIT for the operand row of matrix i + 1, requested in the last N phase: what the wave issued behind that
+    // request may stay in flight.  Dense store: the stores of that phase's passes c = 1..3 (none before iteration 2).
+    // Packed store: they vary from tile to tile -- vmcnt(0), they are a phase old by then.  DOT: its int2e_ip1 loads are
+    // buffer loads the compiler counts -- vmcnt(0).  (Y2 adds the DMA of its M1 row: y2_wait_sb_row.)
+    auto younger = [&](bool odd, int i) { return (MODE == 0 && !DOT && i >= 3) ? (odd ? cntA : cntB) : 0; };
+    // The storing write-outs: pass k of the tile at `ob` from the thread's stage values dv.  Packed: kd is the pass that
+    // holds the diagonal u == v of this tile's columns, cf the multiplicities of the thread's two columns.
+    [[maybe_unused]] auto store_pass = [&](int k, d2 dv, char *ob, int kd, d2 cf, int jt) {
+        if constexpr (MODE == 0) {
+            gstore16(gvo, dv, ob + (int64_t)(64 * k) * out_ld * 8);
+        } else {
+            const int u = ur + 64 * k;
+            d2 f = cf * frow[k];
+            if (k != kd) {          // below the diagonal: both columns, rows beyond the last one masked
+                const d2 v = dv * f;
+                if (u < npairs) gstore16(tv[k], v, ob);
+            } else {                // the diagonal pass: column v of row u only for u >= v, diag_mult on u == v
+                const int d = u - (8 * (t_begin + jt) + wl);
+                if (d == 0) f[0] *= a.diag_mult;
+                if (d == 1) f[1] *= a.diag_mult;
+                const d2 v = dv * f;
+                if (u < npairs) {
+                    if (d >= 1) *reinterpret_cast<d2 *>(ob + tv[k]) = v;
+                    else if (d == 0) *reinterpret_cast<double *>(ob + tv[k]) = v[0];
+                }
+            }
+        }
+    };
     // DOT: the thread's pair of the tile and its row pair; of the rows 64 k + 2 du, + 1 a bit each for "diagonal pair"
     // (weight 1, else 2; bits k, 8 + k) and for "a row of the result" (bits 16 + k, 24 + k); the int2e_ip1 blocks of the
     // three components; the offsets bo of the rows (hi, lo), (lo, hi) of the tile being loaded; the sums; the register
@@ -342,6 +314,15 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
 #pragma unroll
             for (int ta = 0; ta < NT; ++ta) yy[ti][ta] = (d4){0.0, 0.0, 0.0, 0.0};
     }
+    // ... WITH TWO ROWS IN FLIGHT.  The SB row: `younger` and the M1 row requested behind the last Y phase (none before the first)
+    [[maybe_unused]] auto y2_wait_sb_row = [&](int i, int K) { wait_vm_dyn8(i == 0 ? 0 : K + npieces); };
+    // The M1 row of this matrix (requested behind the Y phase of the last one): younger than it are this phase's SB row
+    // and its stores so far (passes c = 0..2, `stores` their bits); then its first fragments
+    [[maybe_unused]] auto y2_wait_m1_row = [&](int stores) {
+        wait_vm_dyn8(npieces + __builtin_popcount((unsigned)stores & 7u));
+        mb[0][0] = lds_ld(fa[0][0] + kRowM);
+        mb[1][0] = lds_ld(fa[1][0] + kRowM);
+    };
 
     double mf[NT][KS];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -376,10 +357,11 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
 #pragma unroll
                 for (int m = 0; m < NT * NT; ++m) {
                     if constexpr (COMPUTE) {
+                        // (s_setprio: a wave issuing MFMAs back to back keeps the port from its SIMD mate's loads, mfma_f64_coissue.txt)
                         const int rt = m / NT, st = m % NT;
-                        EVC_PTD_PRIO(0);
+                        __builtin_amdgcn_s_setprio(0);
                         h[rt][st] = mfma_f64(mf[rt][kk], xf[kk][st], kk == 0 ? zero : h[rt][st]);
-                        EVC_PTD_PRIO(1);
+                        __builtin_amdgcn_s_setprio(1);
                     }
                     const int f = kk * 2 + m;
                     if (m < 2 && f < 12) {
@@ -403,11 +385,7 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
             const int jt = (ODD ? i - 3 : i - 2) >> 1;
             constexpr unsigned bimm = (TP ^ 1u) * 8u * kPdP;
             char *ob = outg + (int64_t)(8 * (t_begin + jt)) * 8;
-#ifdef EVC_PTD_K0
-            const int K = 0;
-#else
-            const int K = (MODE == 0 && !DOT && i >= 3) ? (ODD ? cntA : cntB) : 0;
-#endif
+            const int K = younger(ODD, i);
             if constexpr (DOT) {
                 // the int2e_ip1 rows (hi, lo) and (lo, hi) of the thread's pair of the tile whose passes 0..3 this phase
                 // requests and 4..7 the next one (idle slots: pair 0, not written)
@@ -448,14 +426,14 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
                 for (int m = 0; m < 3; ++m) {
                     if constexpr (COMPUTE) {
                         const int it = m == 0 ? 0 : 1, st = m == 2 ? 1 : 0;
-                        EVC_PTD_PRIO(0);
+                        __builtin_amdgcn_s_setprio(0);
                         nn[it][st] = mfma_f64(xf[kk][it], h[kk / 4][st][kk % 4], kk == 0 ? zero : nn[it][st]);
-                        EVC_PTD_PRIO(1);
+                        __builtin_amdgcn_s_setprio(1);
                         if (m == 0) {
                             // the operand row of matrix i+1 (requested one iteration ago) has landed -> fragments;
                             // then the row of matrix i+2 is requested into the same LDS row
                             if (kk == 0) {
-                                if constexpr (Y2) wait_vm_dyn8(i == 0 ? 0 : K + npieces);   // (+ the M1 row requested behind the last Y phase)
+                                if constexpr (Y2) y2_wait_sb_row(i, K);
                                 else wait_vm_dyn(K);
                             }
                             if (kk < 2) {
@@ -482,13 +460,7 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
                                     ha[rt][k2] = lds_ld(sqr[rt] + 8u * 4u * k2);
                             }
                         }
-                        // the M1 row of this matrix (requested behind the Y phase of the last one) has landed: younger
-                        // than it are this phase's SB row and its stores so far (passes c = 0..2); then its first fragments
-                        if (m == 0 && kk == 7) {
-                            wait_vm_dyn8(npieces + __builtin_popcount((unsigned)(act >> (ODD ? 4 : 0)) & 7u));
-                            mb[0][0] = lds_ld(fa[0][0] + kRowM);
-                            mb[1][0] = lds_ld(fa[1][0] + kRowM);
-                        }
+                        if (m == 0 && kk == 7) y2_wait_m1_row(act >> (ODD ? 4 : 0));
                     }
                     if (m == 2 && (kk & 1) == 1) {
                         const int c = kk / 2, k = (ODD ? 4 : 0) + c;
@@ -499,24 +471,8 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
                             const int kn = ODD ? c : 4 + c;
                             if ((vmask >> kn & 1) && (ODD ? jt + 1 < t_end - t_begin : i >= 2)) dot_load(c, kn);
                             if (c == 3 && ODD && i >= 3) dot_reduce(TP ^ 1u);
-                        } else if constexpr (MODE == 0) {
-                            if (act >> k & 1) gstore16(gvo, dv[c], ob + (int64_t)(64 * k) * out_ld * 8);
                         } else if (act >> k & 1) {
-                            const int u = ur + 64 * k;
-                            d2 f = cf * frow[k];
-                            if (k != kd) {          // below the diagonal: both columns, rows beyond the last one masked
-                                const d2 v = dv[c] * f;
-                                if (u < npairs) gstore16(tv[k], v, ob);
-                            } else {                // the diagonal pass: column v of row u only for u >= v, diag_mult on u == v
-                                const int d = u - (8 * (t_begin + jt) + wl);
-                                if (d == 0) f[0] *= a.diag_mult;
-                                if (d == 1) f[1] *= a.diag_mult;
-                                const d2 v = dv[c] * f;
-                                if (u < npairs) {
-                                    if (d >= 1) *reinterpret_cast<d2 *>(ob + tv[k]) = v;
-                                    else if (d == 0) *reinterpret_cast<double *>(ob + tv[k]) = v[0];
-                                }
-                            }
+                            store_pass(k, dv[c], ob, kd, cf, jt);
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -540,9 +496,9 @@ __device__ __forceinline__ void ptd_body(const PairTransformArgs &a, const Y2dAr
                     for (int m = 0; m < NT * NT; ++m) {
                         const int ti = m / NT, ta = m % NT;
                         if constexpr (LIVE) {
-                            EVC_PTD_PRIO(0);
+                            __builtin_amdgcn_s_setprio(0);
                             yy[ti][ta] = mfma_f64(ha[ti][kk], mb[ta][kk], yy[ti][ta]);
-                            EVC_PTD_PRIO(1);
+                            __builtin_amdgcn_s_setprio(1);
                             if (m == 0 && kk < KS - 1) {
                                 mb[0][kk + 1] = lds_ld(fa[0][kk + 1] + kRowM);
                                 mb[1][kk + 1] = lds_ld(fa[1][kk + 1] + kRowM);
@@ -635,8 +591,18 @@ __global__ __launch_bounds__(256, 1) void ptd_kernel(PairTransformArgs a, PairDo
     ptd_body<MODE, false, DOT != 0>(a, Y2dArgs{}, dt);
 }
 
+// y2d_kernel<PS>: one name, two kernels with a body each (explicit specialisations; why not two functions: DESIGN.md 4.5).
+// PS = 1: the first gradient-side pair step with Y2 inside (R = X^T T_v X written as ptd_kernel<0> writes it); one
+// workgroup per CU for its LDS.
+template <int PS>
+__global__ void y2d_kernel(Y2dArgs ya, PairTransformArgs pa);
+template <>
+__global__ __launch_bounds__(256, 1) void y2d_kernel<1>(Y2dArgs ya, PairTransformArgs pa) {
+    ptd_body<0, true>(pa, ya);
+}
+
 // ---------------------------------------------------------------------------------- Y2 with LDS-DMA operand rows
-// y2_fused_kernel (y2.hip) with the machinery above: per pair v one wave computes H^T = X^T M1_v (32 MFMAs) and
+// PS = 0 (pa is a dummy): y2_fused_kernel (y2.hip) with the machinery above: per pair v one wave computes H^T = X^T M1_v (32 MFMAs) and
 // Y += mult(v) T_v H^T (32 MFMAs), M1_v = row v of the first pair step's intermediate, T_v = row v of SB, both dense
 // (pair, pair) forms at the pitch pair_ld(n).  The two rows come by LDS-DMA into two wave-private LDS rows; the T
 // fragments are read during the H phase and the next T row requested, the next M fragments during the Y phase and
@@ -644,20 +610,13 @@ __global__ __launch_bounds__(256, 1) void ptd_kernel(PairTransformArgs a, PairDo
 // constant "one row younger" vmcnt.  No barrier, no store, no vector instruction in the loop: the multiplicity of the
 // pair (1 on the diagonal i == j, else 2) selects one of two accumulator sets (wave-uniform branch), Y = Yd + 2 Yo at
 // the end.
-//
-// PS = 1: the kernel is the first gradient-side pair step as well (ptd_body above, R = X^T T_v X written as ptd_kernel<0>
-// writes it); one workgroup per CU for its LDS.  PS = 0: Y2 alone, as described here.
-template <int PS>
-__global__ __launch_bounds__(256, PS ? 1 : 2) void y2d_kernel(Y2dArgs ya, PairTransformArgs pa) {
-    if constexpr (PS) {
-        ptd_body<0, true>(pa, ya);
-        return;
-    }
+template <>
+__global__ __launch_bounds__(256, 2) void y2d_kernel<0>(Y2dArgs ya, PairTransformArgs) {
     const double *__restrict__ SB = ya.SB, *__restrict__ M1 = ya.M1, *__restrict__ X = ya.X;
     double *__restrict__ partial = ya.partial;
     const int64_t sX = ya.sX, sws = ya.sws;
     const int n = ya.n, tiles_per_wg = ya.tiles_per_wg, ppt = ya.ppt;
-    constexpr int KS = 8, NT = 2, NPAD = 32;
+    constexpr int KS = 8, NT = 2;
     extern __shared__ __align__(16) char lds[];
     const int npairs = n * (n + 1) / 2, ld = pair_ld(n);
     const int64_t g = blockIdx.y;
@@ -691,19 +650,10 @@ __global__ __launch_bounds__(256, PS ? 1 : 2) void y2d_kernel(Y2dArgs ya, PairTr
             *reinterpret_cast<double *>(lds + rowM + kPdRaw * 1024 + 8 * lane) = 0.0;
             *reinterpret_cast<double *>(lds + rowT + kPdRaw * 1024 + 8 * lane) = 0.0;
         }
-        const unsigned wbytes = (unsigned)((npairs * 8 + 15) & ~15);   // (rows start on 128-byte lines)
-        unsigned vo[kPdRaw];
-#pragma unroll
-        for (unsigned u = 0; u < kPdRaw; ++u) {
-            const unsigned o = 1024u * u + 16u * (unsigned)lane;
-            vo[u] = o < wbytes ? o : 0u;
-        }
-        const int npieces = __builtin_amdgcn_readfirstlane((int)((wbytes + 1023u) >> 10));
+        const RowDma dma((unsigned)((npairs * 8 + 15) & ~15), lane);   // (rows start on 128-byte lines)
+        const int npieces = dma.npieces;
         auto dma_row = [&](const double *base, int e, unsigned dst) {
-            const char *src = reinterpret_cast<const char *>(base + (int64_t)(e < npairs ? e : wave) * ld);
-#pragma unroll
-            for (unsigned u = 0; u < kPdRaw; ++u)
-                if ((int)u < npieces) glds_s(vo[u], src, dst + 1024u * u);
+            dma.request(reinterpret_cast<const char *>(base + (int64_t)(e < npairs ? e : wave) * ld), dst);
         };
         // "everything but the youngest row has landed": npieces DMA instructions may stay in flight
         auto wait_older = [&]() {
@@ -797,7 +747,8 @@ __global__ __launch_bounds__(256, PS ? 1 : 2) void y2d_kernel(Y2dArgs ya, PairTr
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    // cross-wave sum (every workgroup writes its slab, workgroups without tiles a zero one)
+    // cross-wave sum of Y = Yd + 2 Yo over the rows (every workgroup writes its slab, workgroups without tiles a zero one)
+    constexpr int NPAD = 32;
     __syncthreads();
     double *red = reinterpret_cast<double *>(lds);   // [4][NPAD][NPAD + 1], over the rows once they are done with
 #pragma unroll

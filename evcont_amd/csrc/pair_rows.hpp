@@ -5,6 +5,7 @@
 // addresses fa / sa and the X-fragment load xf[kk][t].  Through an array-reference helper all 8 pt_pipe* instantiations
 // came out different (pt_pipe_kernel<32,0> 188 -> 202 VGPRs, <32,1> 206 -> 214), through a scalar-returning helper inside
 // the existing loops still all 8 (offsets) or 4 (X fragments): hand-scheduled code nobody has measured in that form.
+// Likewise in pair_dma.hip (fa, X fragments, zero slots, walker) and for the Y2 kernels' cross-wave sum: DESIGN.md 4.5.
 #pragma once
 #include "common.hpp"
 
