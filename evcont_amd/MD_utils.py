@@ -328,14 +328,19 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
 def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=()):
     """``evaluate(R (G,A,3)) -> (E (G,nroots), grads (G,nroots,A,3))`` for geometries of the s-Gaussian molecule of
     ``mols``, device-resident from the coordinates on: the training set and the batched evaluator are built once, every
-    call uploads the coordinates, computes the AO integrals there (``hchain_device.DeviceSGaussians``) and runs the
+    call uploads the coordinates, computes the AO integrals there (``hchain_device.DeviceSGaussians``, or
+    ``gto_device.DeviceGaussians`` for a molecule with ``shells``) and runs the
     batched several-roots call on them.  With ``observables``: ``(E, grads (G,1,A,3), props)`` of the highest root alone,
     forces and observables from one solve (``BatchedEvaluator.multistate_properties``)."""
     from .ab_initio_eigenvector_continuation import resolve_compression
     from .ab_initio_gradients_loewdin import _batched_evaluator
-    from .hchain_device import DeviceSGaussians
     mol0, G = mols[0], len(mols)
-    if not all(hasattr(mol0, k) for k in ("charges", "exponents", "coefficients")):
+    # molecules of s and p shells (gto_small.GaussianMol) and of one s function per centre (hchain.HChainMol)
+    if getattr(mol0, "shells", None) is not None and hasattr(mol0, "charges"):
+        from .gto_device import DeviceGaussians as producer
+    elif all(hasattr(mol0, k) for k in ("charges", "exponents", "coefficients")):
+        from .hchain_device import DeviceSGaussians as producer
+    else:
         raise ValueError('integrals="device" needs s-Gaussian molecules (evcont_amd.hchain.HChainMol)')
     if G * nroots > 4096:
         raise ValueError(f"{G} trajectories x {nroots} roots exceed the 4096 slots of one call")
@@ -343,7 +348,7 @@ def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=()):
                         resolve_compression("default", one_rdm, two_rdm, overlap, ao_arrays(mol0, need_grad=True)))
     natm = int(np.asarray(mol0.charges).shape[0])
     ev = _batched_evaluator(t, natm, G)
-    sg = DeviceSGaussians.from_mol(mol0, device=t.device)
+    sg = producer.from_mol(mol0, device=t.device)
     packed = t.layout == _lib.LAYOUT_SYM8 and t.n <= 64
 
     def evaluate(R):
@@ -376,7 +381,8 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
     frame per step with ``coord``/``veloc`` (G,A,3), ``epot``/``ekin`` (G,) and ``time``.  Plain adiabatic dynamics:
     no surface hopping, and at (near-)degenerate roots the forces follow whichever eigenvector the solver returned.
     ``integrals``: "host" rebuilds every molecule with ``with_coords`` (numpy) at every step; "device" (s-Gaussian
-    molecules, ``evcont_amd.hchain``) uploads the (G,A,3) coordinates and computes the AO integrals on the device.
+    molecules, ``evcont_amd.hchain``, or molecules of s and p shells, ``evcont_amd.gto_small``) uploads the (G,A,3)
+    coordinates and computes the AO integrals on the device.
     ``observables``: None (the frames above, nothing else) or a selection of "dipole", "mulliken", "loewdin": every frame
     gains ``dipole`` (G,3) (atomic units, origin (0,0,0)) and ``mulliken_charges`` / ``loewdin_charges`` (G,A) of the
     propagated root (plain Mulliken, not meta-Loewdin), from the solve that gives the forces; with

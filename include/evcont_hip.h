@@ -48,7 +48,9 @@ extern "C" {
                                  EVC_PROF_FCI_PACK; additive: evc_fci_spin_apply, evc_fci_spin_diag;
                                  evc_trdm_plan_describe; additive: evc_cas_expand_rows,
                                  evc_cas_expand_workspace_bytes, evc_cas_expand_describe; additive:
-                                 evc_properties_roots_batch, evc_properties_workspace_bytes, evc_sgto_dipole_batch */
+                                 evc_properties_roots_batch, evc_properties_workspace_bytes, evc_sgto_dipole_batch;
+                                 additive: evc_spgto_workspace_bytes, evc_spgto_integrals_batch,
+                                 evc_spgto_dipole_batch */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -626,6 +628,43 @@ int evc_sgto_integrals_batch(int natm, int nprim, int count, const double *coord
  * bits from run to run and for every batch size. */
 int evc_sgto_dipole_batch(int natm, int nprim, int count, const double *coords, const double *ex, const double *co,
                           const double origin[3], double *dip, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * AO integrals of molecules of contracted Cartesian s and p Gaussian shells on the device (csrc/spgto.hip; the host
+ * statement is evcont_amd/gto_small.py sp_gaussian_mol): water, Zundel, ... in STO-3G or 6-31G from the coordinates.  One
+ * call writes every array of an evc_geometry_batch for `count` geometries (N = the number of contracted functions, A =
+ * natm), into the evc_sgto_outputs of evc_sgto_integrals_batch, with its flags and forms.  AO order: shells in the given
+ * order, a p shell as x, y, z.  dhcore: the operator term of nucleus A plus the rows and columns of all functions on A.
+ *   coords        DEVICE (count, natm, 3), Bohr.          charges       DEVICE (natm).
+ *   shell_atom, shell_l, shell_prim_offset, exponents, coefficients   HOST: per shell its centre (ascending), l (0 or 1)
+ *                 and the range [shell_prim_offset[s], shell_prim_offset[s+1]) of its primitives (offset[0] = 0; nshell+1
+ *                 entries) in exponents (> 0) / coefficients (of NORMALISED primitives, used as given: a caller that wants
+ *                 contracted functions of unit norm scales them beforehand).  They reach the kernels by value.
+ *   flags         EVC_FLAG_ENERGY_ONLY, EVC_FLAG_ERI_S4, EVC_FLAG_IP1_S2KL as for evc_sgto_integrals_batch; any other flag
+ *                 is refused.
+ *   ws            DEVICE workspace (the primitive-pair table), 16-byte aligned, at least
+ *                 evc_spgto_workspace_bytes(natm, nshell, nprim_total, nao, count).
+ * Limits: l <= 1, 1 <= natm <= 64, nao <= 64, 1 ... 8 primitives per shell, at most 128 primitives in all,
+ * 1 <= count <= 65535.  A null required pointer, a shape outside the limits, an l outside {0, 1}, a shell_atom out of
+ * range or not ascending, a non-positive exponent, an unknown flag or a workspace that is too small or misaligned is
+ * refused before anything is launched (rc < 0, evc_last_error names the function).  Caller's stream, no allocation, no
+ * library state; nothing but the output arrays and the workspace is written.  No sum is split between threads: the same
+ * bits from run to run and for every batch size (geometry g of a batch = the call on it alone), and the full forms are
+ * the unpacked packed forms.  S and hcore are exactly symmetric, eri within each index pair, dhcore in its last two
+ * indices.  No primitive quartet is screened.  eri with EVC_FLAG_ENERGY_ONLY need NOT have the bits of eri without it (the
+ * two use Boys functions of different highest order); they agree to rounding.
+ * evc_spgto_workspace_bytes: 0 (and a message) on a shape outside the limits.
+ * evc_spgto_dipole_batch: dip (count,3,N,N) = <mu| r - origin |nu> of the same molecules; origin HOST; needs no workspace;
+ * one sum per element over the primitive pairs in ascending order, mirrored: exactly symmetric.
+ * --------------------------------------------------------------------------------- */
+size_t evc_spgto_workspace_bytes(int natm, int nshell, int nprim_total, int nao, int count);
+int evc_spgto_integrals_batch(int natm, int nshell, int count, const double *coords, const double *charges,
+                              const int *shell_atom, const int *shell_l, const int *shell_prim_offset,
+                              const double *exponents, const double *coefficients, const evc_sgto_outputs *out, int flags,
+                              void *ws, size_t ws_bytes, void *stream);
+int evc_spgto_dipole_batch(int natm, int nshell, int count, const double *coords, const int *shell_atom,
+                           const int *shell_l, const int *shell_prim_offset, const double *exponents,
+                           const double *coefficients, const double origin[3], double *dip, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Observables of continuation states (csrc/properties.hip; host statement: evcont_amd/properties.py; the reference's

@@ -1,0 +1,135 @@
+"""CPU tests of the host statement of s and p Gaussian integrals (``evcont_amd.gto_small``): against the independent
+truth file, against ``hchain.s_gaussian_mol`` on s-only shells, the derivative arrays against finite differences, the
+rotation behaviour of the p blocks, the basis tables, and the RHF energy of STO-3G water."""
+import numpy as np
+import pytest
+
+import spgto_cases as sc
+from evcont_amd import gto_small as gs
+from evcont_amd.hchain import STO3G_H_COEFFICIENTS, STO3G_H_EXPONENTS, s_gaussian_mol
+from oracle import evcont_oracle as orc
+
+
+@pytest.fixture(scope="module")
+def truth():
+    return sc.load_truth()
+
+
+@pytest.fixture(scope="module")
+def water():
+    return gs.water("sto-3g")
+
+
+@pytest.mark.parametrize("name", sc.CASES)
+def test_host_statement_against_truth(truth, name):
+    """All eight arrays and the dipole integrals against tests/golden/spgto_truth.npz.  Measured (max error relative to
+    max(1, max |array|)): 2.1e-12, dhcore of case "c" (exponent 5000); every other array and case < 1e-15.  Gate: 10 times
+    the measured value, under the ceiling of 1e-10."""
+    m = sc.case_mol(truth, name)
+    worst = {}
+    for f in sc.NAMES:
+        worst[f] = sc.rel_err(getattr(m, f), truth, name, f)
+    worst["dip"] = sc.rel_err(m.dipole_integrals(truth[f"{name}/origin"]), truth, name, "dip")
+    print(name, {k: "%.1e" % v for k, v in worst.items()})
+    assert sc.TRUTH_GATE <= sc.CEILING
+    assert max(worst.values()) < sc.TRUTH_GATE, worst
+
+
+def test_s_only_shells_reproduce_hchain():
+    rng = np.random.default_rng(4)
+    R = np.zeros((4, 3))
+    R[:, 0] = 1.8 * np.arange(4)
+    R += 0.3 * rng.standard_normal((4, 3))
+    h = s_gaussian_mol(R)
+    shells = [[gs.Shell(0, STO3G_H_EXPONENTS, STO3G_H_COEFFICIENTS)] for _ in range(4)]
+    m = gs.sp_gaussian_mol(R, np.ones(4), shells, renormalize=False)
+    for f in sc.NAMES:
+        assert np.abs(getattr(m, f) - getattr(h, f)).max() < 1e-13, f
+    assert np.abs(m.dipole_integrals((0.1, -0.2, 0.3)) - h.dipole_integrals((0.1, -0.2, 0.3))).max() < 1e-13
+    assert np.array_equal(m.aoslices, h.aoslices) and m.nelec == h.nelec
+
+
+def fd(fun, R, h=1e-5):
+    out = []
+    for a in range(R.shape[0]):
+        row = []
+        for x in range(3):
+            Rp, Rm = R.copy(), R.copy()
+            Rp[a, x] += h
+            Rm[a, x] -= h
+            row.append((fun(Rp) - fun(Rm)) / (2 * h))
+        out.append(row)
+    return np.array(out)
+
+
+def test_derivative_arrays_against_finite_differences(water):
+    """As tests/test_hchain_physics.py does for chains (step 1e-5, 1e-9 for the overlap, 1e-8 for the rest), with the
+    general AO-to-atom map."""
+    m, R = water, water.atom_coords()
+    at = lambda r: water.with_coords(r, need_grad=False)
+    dS = orc.overlap_grad(m.ipovlp, m.aoslices)
+    assert np.allclose(dS, fd(lambda r: at(r).S, R).transpose(2, 3, 0, 1), atol=1e-9)
+    assert np.allclose(m.dhcore, fd(lambda r: at(r).hcore, R), atol=1e-8)
+    de_fd = fd(lambda r: at(r).eri, R)
+    ip1 = m.eri_ip1
+    for A, (s0, s1) in enumerate(m.aoslices):
+        sl = slice(s0, s1)
+        for x in range(3):
+            d = np.zeros_like(m.eri)
+            d[sl] -= ip1[x, sl]
+            d[:, sl] -= ip1[x, sl].transpose(1, 0, 2, 3)
+            d[:, :, sl] -= ip1[x, sl].transpose(2, 3, 0, 1)
+            d[:, :, :, sl] -= ip1[x, sl].transpose(2, 3, 1, 0)
+            assert np.allclose(d, de_fd[A, x], atol=1e-8), (A, x)
+    assert np.allclose(m.gnuc, fd(lambda r: np.float64(at(r).enuc), R), atol=1e-8)
+
+
+def test_rotation(water):
+    """S, hcore and eri of a rotated water are the originals transformed by the rotation of the p blocks."""
+    rng = np.random.default_rng(7)
+    Q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
+    if np.linalg.det(Q) < 0:
+        Q[:, 0] = -Q[:, 0]
+    rot = water.with_coords(water.atom_coords() @ Q.T, need_grad=False)
+    # AO transformation: identity on s functions, Q on every (x, y, z) block
+    U = np.eye(water.nao)
+    k = 0
+    for atom in water.shells:
+        for sh in atom:
+            if sh.l == 1:
+                U[k:k + 3, k:k + 3] = Q
+            k += 2 * sh.l + 1
+    assert np.abs(rot.S - U @ water.S @ U.T).max() < 1e-13
+    assert np.abs(rot.hcore - U @ water.hcore @ U.T).max() < 1e-12
+    assert np.abs(rot.eri - np.einsum("ai,bj,ck,dl,ijkl->abcd", U, U, U, U, water.eri, optimize=True)).max() < 1e-13
+    assert abs(rot.enuc - water.enuc) < 1e-13
+
+
+@pytest.mark.parametrize("table", ["sto-3g", "6-31g"])
+def test_tables_are_normalised(table):
+    for el in ("H", "O"):
+        for sh in gs.element_shells(gs.BASES[table], el):
+            assert abs(gs.shell_self_overlap(sh) - 1.0) < 1e-5, (table, el, sh)
+    m = gs.water(table, need_grad=False)
+    assert m.nao == {"sto-3g": 7, "6-31g": 13}[table]
+    assert np.abs(np.diag(m.S) - 1.0).max() < 1e-14
+    assert np.array_equal(m.aoslices, {"sto-3g": [[0, 5], [5, 6], [6, 7]], "6-31g": [[0, 9], [9, 11], [11, 13]]}[table])
+    assert m.nelec == (5, 5) and np.allclose(m.atom_mass_list(), [15.999, 1.008, 1.008])
+    with pytest.raises(ValueError):
+        gs.sp_gaussian_mol(m.coords, [6.0, 1.0, 1.0], m.shells, need_grad=False).atom_mass_list()
+    with pytest.raises(ValueError):
+        gs.Shell(2, (1.0,), (1.0,))
+
+
+def test_water_rhf_known_answer():
+    """RHF of STO-3G water at the geometry of a public SCF tutorial: recorded and printed, not a gate on the energy (the
+    expected value, about -74.942079928 Ha with enuc about 8.002367061810, is quoted from memory)."""
+    from evcont_amd.scf_small import rhf
+    m = gs.molecule(("O", "H", "H"), [[0.0, -0.143225816552, 0.0], [1.638036840407, 1.136548822547, 0.0],
+                                      [-1.638036840407, 1.136548822547, 0.0]], "sto-3g", need_grad=False)
+    C, _, converged = rhf(m.S, m.hcore, m.eri, m.nelec)
+    D = 2.0 * C[:, :5] @ C[:, :5].T
+    F = m.hcore + np.einsum("pqrs,rs->pq", m.eri, D) - 0.5 * np.einsum("prqs,rs->pq", m.eri, D)
+    e = 0.5 * float(np.sum(D * (m.hcore + F))) + m.enuc
+    print("STO-3G water: enuc = %.12f, E(RHF) = %.9f (expected about -74.942079928)" % (m.enuc, e))
+    assert converged and np.isfinite(e)
