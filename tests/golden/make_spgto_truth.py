@@ -17,10 +17,15 @@ Cases:
              the quartets; b_flat: the same with the centres coincident in one coordinate
   c          a tight and a diffuse centre (exponents 5000 and 0.1)
   d          12 Bohr apart: large t
-A few minutes on 16 processes.
+  e_lo, e_hi the basis of b with the distance chosen so that t of the (AA|BB) quartets is 12 - 1e-3 and 12 + 1e-3: the
+             longest series and the least stable upward recursion of the Boys scheme, side by side
+The cases are kept in two files (FILES): spgto_truth.npz and, added later, spgto_truth_crossover.npz, so that new cases
+never touch the stored bits of the old ones.  A few minutes on 16 processes.
 
-    python tests/golden/make_spgto_truth.py [case ...]     # no argument: all cases, writes the file
-                                                           # with arguments: recomputes those and compares with the file
+    python tests/golden/make_spgto_truth.py [case ...]     # no argument: all cases, writes both files
+                                                           # with arguments: recomputes those and compares with their file
+    python tests/golden/make_spgto_truth.py --write spgto_truth_crossover.npz      # writes that file alone
+    python tests/golden/make_spgto_truth.py --boys [case ...]   # prints t of every quartet class and attraction term
 """
 import os
 import sys
@@ -32,7 +37,7 @@ import sympy as sp
 from mpmath import mp, mpf
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.path.join(HERE, "spgto_truth.npz")
+FILES = {"spgto_truth.npz": ("a", "b", "b_flat", "c", "d"), "spgto_truth_crossover.npz": ("e_lo", "e_hi")}
 mp.dps = 40
 NAMES = ("enuc", "S", "hcore", "eri", "ipovlp", "dhcore", "eri_ip1", "gnuc", "dip")
 
@@ -50,6 +55,9 @@ def cases():
         "b_flat": ([[0.0, 0.4, 0.0], [2.1, 0.4, 0.9]], [3.0, 2.0], [one(3.0), one(2.2)], (0.0, 0.0, 0.0)),
         "c": ([[0.0, 0.0, 0.0], [0.7, -0.5, 0.9]], [8.0, 1.0], [one(5000.0), one(0.1)], (0.2, 0.0, -0.3)),
         "d": ([[0.0, 0.0, 0.0], [7.0, -8.0, 5.5677643628]], [1.0, 2.0], [one(1.1), one(0.6)], (0.0, 0.0, 0.0)),
+        # (AA|BB): rho = 6.0 x 4.4 / 10.4, t = rho |A - B|^2 = 11.999000000 and 12.001000000 (--boys prints every class)
+        "e_lo": ([[0.0, 0.0, 0.0], [1.5, 1.2, 1.0182724527]], [3.0, 2.0], [one(3.0), one(2.2)], (0.3, -0.1, 0.2)),
+        "e_hi": ([[0.0, 0.0, 0.0], [1.5, 1.2, 1.0186592495]], [3.0, 2.0], [one(3.0), one(2.2)], (0.3, -0.1, 0.2)),
     }
 
 
@@ -231,8 +239,43 @@ def pack(name, arrays):
     return out
 
 
+def boys_arguments(name):
+    """{label: t} of every class of primitive quartets (t = rho |P - Q|^2) and of every nuclear-attraction term
+    (t = p |P - C|^2) of a case; a class is a pair of shell pairs, since the primitives of a shell share their centre."""
+    R, Z, shells, origin = cases()[name]
+    prims = [(at, s, k, float(e)) for at, atom in enumerate(shells) for s, (l, ex, co) in enumerate(atom)
+             for k, e in enumerate(ex)]
+    R = np.asarray(R, dtype=np.float64)
+    pairs = {}
+    for i, (ai, si, ki, ea) in enumerate(prims):
+        for aj, sj, kj, eb in prims[:i + 1]:
+            pairs[f"{ai}.{si}.{ki} {aj}.{sj}.{kj}"] = (ea + eb, (ea * R[ai] + eb * R[aj]) / (ea + eb))
+    out = {}
+    for kb, (p, P) in pairs.items():
+        for c in range(len(Z)):
+            out[f"<{kb}| 1/r_{c}"] = p * float(np.sum((P - R[c]) ** 2))
+        for kk, (q, Q) in pairs.items():
+            out[f"({kb}|{kk})"] = p * q / (p + q) * float(np.sum((P - Q) ** 2))
+    return out
+
+
 def main(argv):
-    chosen = argv or sorted(cases())
+    if argv[:1] == ["--boys"]:
+        for name in argv[1:] or sorted(cases()):
+            seen = {}
+            for label, t in boys_arguments(name).items():
+                seen.setdefault(round(t, 9), label)
+            print(f"{name}: t of the distinct classes (atom.shell.primitive; the first of each value)")
+            for t in sorted(seen):
+                print(f"    t = {t:16.9f}   {seen[t]}")
+        return 0
+    only = None
+    if argv[:1] == ["--write"]:
+        only, argv = argv[1], []
+        chosen = list(FILES[only])
+    else:
+        chosen = argv or sorted(cases())
+    where = {name: os.path.join(HERE, f) for f, names in FILES.items() for name in names}
     jobs = []
     for name in chosen:
         n = len(functions(cases()[name][2]))
@@ -244,13 +287,21 @@ def main(argv):
         rows = {(mu, nu): r for (nm, mu, nu), r in zip(jobs, res) if nm == name}
         made.update({f"{name}/{k}": v for k, v in pack(name, assemble(name, rows)).items()})
     if not argv:
-        np.savez_compressed(OUT, **made)
-        print(f"wrote {OUT}: {os.path.getsize(OUT)} bytes, {len(made)} arrays")
+        for f, names in FILES.items():
+            if only not in (None, f):
+                continue
+            part = {k: v for k, v in made.items() if k.split("/")[0] in names}
+            np.savez_compressed(os.path.join(HERE, f), **part)
+            print(f"wrote {f}: {os.path.getsize(os.path.join(HERE, f))} bytes, {len(part)} arrays")
         return 0
-    with np.load(OUT) as old:
-        same = all(np.array_equal(old[k], v) and old[k].dtype == v.dtype for k, v in made.items())
-    print(f"{', '.join(chosen)}: {'reproduces' if same else 'DIFFERS FROM'} {OUT}")
-    return 0 if same else 1
+    status = 0
+    for name in chosen:
+        with np.load(where[name]) as old:
+            same = all(np.array_equal(old[k], v) and old[k].dtype == v.dtype for k, v in made.items()
+                       if k.split("/")[0] == name)
+        print(f"{name}: {'reproduces' if same else 'DIFFERS FROM'} {os.path.basename(where[name])}")
+        status |= 0 if same else 1
+    return status
 
 
 if __name__ == "__main__":

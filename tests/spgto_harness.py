@@ -1,0 +1,106 @@
+"""How tests/test_gpu_spgto_limits.py calls ``evc_spgto_integrals_batch`` and ``evc_spgto_dipole_batch`` -- a helper, no
+test, the s + p counterpart of tests/sgto_harness.py: through ctypes, with the flattened basis and arbitrary flags, on
+NaN-poisoned output buffers and workspace between two guards each (``Fenced``)."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from evcont_amd import _lib
+from evcont_amd.gto_small import contraction_coefficients
+from sgto_harness import DEV, FENCE, GUARD, Fenced                      # noqa: F401 (FENCE, GUARD: for the tests)
+
+S4, S2KL, ENERGY = _lib.FLAG_ERI_S4, _lib.FLAG_IP1_S2KL, _lib.FLAG_ENERGY_ONLY
+ENERGY_FIELDS = ("enuc", "S", "hcore", "eri")
+GRAD_FIELDS = ("ipovlp", "dhcore", "eri_ip1", "gnuc")
+
+
+class Basis:
+    """The flattened basis of a molecule as the C calls take it: ``charges`` (A,), ``shells`` per atom a list of
+    ``gto_small.Shell`` (an empty list: a nucleus without functions).  The coefficients go through
+    ``gto_small.contraction_coefficients``, so the device and ``sp_gaussian_mol`` see the same numbers."""
+
+    def __init__(self, charges, shells, renormalize=True):
+        coef = contraction_coefficients(shells, renormalize)
+        atom, l, off, ex, co, slices, n = [], [], [0], [], [], [], 0
+        for at, (shs, cs) in enumerate(zip(shells, coef)):
+            start = n
+            for sh, c in zip(shs, cs):
+                atom.append(at)
+                l.append(sh.l)
+                off.append(off[-1] + len(sh.exponents))
+                ex += list(sh.exponents)
+                co += list(c)
+                n += 2 * sh.l + 1
+            slices.append((start, n))
+        self.charges = np.ascontiguousarray(charges, dtype=np.float64).reshape(-1)
+        assert len(shells) == self.charges.shape[0]
+        self.shell_atom = np.array(atom, dtype=np.int32)
+        self.shell_l = np.array(l, dtype=np.int32)
+        self.shell_prim_offset = np.array(off, dtype=np.int32)
+        self.exponents = np.array(ex, dtype=np.float64)
+        self.coefficients = np.array(co, dtype=np.float64)
+        self.aoslices = np.array(slices, dtype=np.int64).reshape(-1, 2)
+        self.natm, self.nshell, self.nprim, self.nao = len(shells), len(atom), off[-1], n
+
+    def pointers(self):
+        return tuple(a.ctypes.data for a in (self.shell_atom, self.shell_l, self.shell_prim_offset, self.exponents,
+                                             self.coefficients))
+
+
+def shapes(A, n, G, flags):
+    ms = n * (n + 1) // 2
+    return {"enuc": (G,), "S": (G, n, n), "hcore": (G, n, n), "eri": (G, ms, ms) if flags & S4 else (G, n, n, n, n),
+            "ipovlp": (G, 3, n, n), "dhcore": (G, A, 3, n, n), "gnuc": (G, A, 3),
+            "eri_ip1": (G, 3, n, n, ms) if flags & S2KL else (G, 3, n, n, n, n)}
+
+
+def _coords(R, natm):
+    R = np.ascontiguousarray(R, dtype=np.float64).reshape(-1, natm, 3)
+    return R.shape[0], torch.from_numpy(R).to(DEV)
+
+
+def run(R, basis, flags, null_grad=False, fetch=None):
+    """One call of ``evc_spgto_integrals_batch`` on fresh poisoned buffers -> (rc, {name: host array}, fences intact, raw
+    Fenced buffers).  ``null_grad``: null pointers for the gradient arrays (no buffers for them).  ``fetch``: the names
+    to read back (default: all); the others stay on the device in their Fenced buffers."""
+    lib = _lib.load()
+    G, dR = _coords(R, basis.natm)
+    shp = shapes(basis.natm, basis.nao, G, flags)
+    bufs = {k: Fenced(int(np.prod(s))) for k, s in shp.items() if not (null_grad and k in GRAD_FIELDS)}
+    need = lib.evc_spgto_workspace_bytes(basis.natm, basis.nshell, basis.nprim, basis.nao, G)
+    assert need > 0 and need % 8 == 0, lib.evc_last_error()
+    ws = Fenced(need // 8)
+    dZ = torch.from_numpy(basis.charges).to(DEV)
+    out = _lib.SgtoOutputs(**{k: (bufs[k].ptr if k in bufs else None) for k in shp})
+    rc = lib.evc_spgto_integrals_batch(basis.natm, basis.nshell, G, dR.data_ptr(), dZ.data_ptr(), *basis.pointers(),
+                                       C.byref(out), int(flags), ws.ptr, need, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    arrays = {k: b.payload(shp[k]) for k, b in bufs.items() if fetch is None or k in fetch}
+    intact = all(b.fences_intact() for b in bufs.values()) and ws.fences_intact()
+    return rc, arrays, intact, bufs
+
+
+def run_dipole(R, basis, origin):
+    """One call of ``evc_spgto_dipole_batch`` on a fresh poisoned buffer -> (rc, host (G,3,N,N), fences intact, Fenced)."""
+    lib = _lib.load()
+    G, dR = _coords(R, basis.natm)
+    n = basis.nao
+    dip = Fenced(G * 3 * n * n)
+    o = (C.c_double * 3)(*[float(x) for x in origin])
+    rc = lib.evc_spgto_dipole_batch(basis.natm, basis.nshell, G, dR.data_ptr(), *basis.pointers(), C.cast(o, C.c_void_p),
+                                    dip.ptr, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return rc, dip.payload((G, 3, n, n)), dip.fences_intact(), dip
+
+
+def pack_eri(full):
+    """(G,n,n,n,n) -> the s4 form (G,Ms,Ms): the elements mu >= nu, kappa >= lambda."""
+    iu, ju = np.tril_indices(full.shape[-1])
+    return full[:, iu, ju][:, :, iu, ju]
+
+
+def pack_ip1(full):
+    """(G,3,n,n,n,n) -> the s2kl form (G,3,n,n,Ms)."""
+    iu, ju = np.tril_indices(full.shape[-1])
+    return full[..., iu, ju]

@@ -40,11 +40,13 @@ def to_numpy(aob, n):
 @pytest.mark.parametrize("name", sc.CASES + ("water",))
 def test_device_against_truth_and_host(truth, molecules, name):
     """Measured on MI355X (max error relative to max(1, max |array|), all forms): against the truth 1.1e-14 (dhcore of
-    case "c"), every other array < 2e-15; against the host statement 2.1e-12 (the host's own error in that array)."""
+    case "c"), every other array of every case at most 7.6e-16 (dhcore of "b"), at the crossover cases "e_lo" / "e_hi" at
+    most 3.5e-16; against the host statement 2.1e-12 (the host's own error in dhcore of "c").  Gate against the truth: per
+    case and array, ``spgto_cases.truth_gate``."""
     from evcont_amd.gto_device import DeviceGaussians
     mol = molecules[name]
     dg = DeviceGaussians.from_mol(mol, device=DEV)
-    worst_truth, worst_host = 0.0, 0.0
+    worst_truth, worst_host = {}, 0.0
     for need_grad in (True, False):
         for packed in (False, True):
             aob = dg.integrals(mol.atom_coords(), need_grad=need_grad, packed=packed)
@@ -56,14 +58,16 @@ def test_device_against_truth_and_host(truth, molecules, name):
                 assert x.shape[1:] == np.shape(getattr(mol, f)), f
                 worst_host = max(worst_host, sc.scaled_diff(x[0], getattr(mol, f)))
                 if name != "water":
-                    worst_truth = max(worst_truth, sc.rel_err(x[0], truth, name, f))
+                    worst_truth[f] = max(worst_truth.get(f, 0.0), sc.rel_err(x[0], truth, name, f))
     origin = truth[f"{name}/origin"] if name != "water" else (0.1, -0.2, 0.3)
     dip = dg.dipole_integrals(mol.atom_coords(), origin).cpu().numpy()[0]
     worst_host = max(worst_host, sc.scaled_diff(dip, mol.dipole_integrals(origin)))
     if name != "water":
-        worst_truth = max(worst_truth, sc.rel_err(dip, truth, name, "dip"))
-    print(f"{name}: device against truth {worst_truth:.1e}, against the host statement {worst_host:.1e}")
-    assert worst_truth < sc.TRUTH_GATE
+        worst_truth["dip"] = sc.rel_err(dip, truth, name, "dip")
+    print(f"{name}: device against truth " + ", ".join(f"{f} {v:.1e}" for f, v in worst_truth.items())
+          + f"; against the host statement {worst_host:.1e}")
+    over = {f: (v, sc.truth_gate(name, f)) for f, v in worst_truth.items() if not v < sc.truth_gate(name, f)}
+    assert not over, over
     assert worst_host < sc.DEVICE_HOST_GATE
 
 
