@@ -329,7 +329,8 @@ def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=()):
     """``evaluate(R (G,A,3)) -> (E (G,nroots), grads (G,nroots,A,3))`` for geometries of the s-Gaussian molecule of
     ``mols``, device-resident from the coordinates on: the training set and the batched evaluator are built once, every
     call uploads the coordinates, computes the AO integrals there (``hchain_device.DeviceSGaussians``, or
-    ``gto_device.DeviceGaussians`` for a molecule with ``shells``) and runs the
+    ``gto_device.DeviceGaussians`` for a molecule with ``shells``, ``gto_spd_device.DeviceSpdGaussians`` when the
+    shells contain l = 2) and runs the
     batched several-roots call on them.  With ``observables``: ``(E, grads (G,1,A,3), props)`` of the highest root alone,
     forces and observables from one solve (``BatchedEvaluator.multistate_properties``)."""
     from .ab_initio_eigenvector_continuation import resolve_compression
@@ -337,7 +338,11 @@ def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=()):
     mol0, G = mols[0], len(mols)
     # molecules of s and p shells (gto_small.GaussianMol) and of one s function per centre (hchain.HChainMol)
     if getattr(mol0, "shells", None) is not None and hasattr(mol0, "charges"):
-        from .gto_device import DeviceGaussians as producer
+        if any(sh.l == 2 for atom in mol0.shells for sh in atom):
+            # d shells (gto_spd.SpdGaussianMol): the general route, csrc/spdgto.hip
+            from .gto_spd_device import DeviceSpdGaussians as producer
+        else:
+            from .gto_device import DeviceGaussians as producer
     elif all(hasattr(mol0, k) for k in ("charges", "exponents", "coefficients")):
         from .hchain_device import DeviceSGaussians as producer
     else:
@@ -381,7 +386,8 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
     frame per step with ``coord``/``veloc`` (G,A,3), ``epot``/``ekin`` (G,) and ``time``.  Plain adiabatic dynamics:
     no surface hopping, and at (near-)degenerate roots the forces follow whichever eigenvector the solver returned.
     ``integrals``: "host" rebuilds every molecule with ``with_coords`` (numpy) at every step; "device" (s-Gaussian
-    molecules, ``evcont_amd.hchain``, or molecules of s and p shells, ``evcont_amd.gto_small``) uploads the (G,A,3)
+    molecules, ``evcont_amd.hchain``, molecules of s and p shells, ``evcont_amd.gto_small``, or of s, p and d shells,
+    ``evcont_amd.gto_spd``) uploads the (G,A,3)
     coordinates and computes the AO integrals on the device.
     ``observables``: None (the frames above, nothing else) or a selection of "dipole", "mulliken", "loewdin": every frame
     gains ``dipole`` (G,3) (atomic units, origin (0,0,0)) and ``mulliken_charges`` / ``loewdin_charges`` (G,A) of the

@@ -29,6 +29,10 @@ class DeviceGaussians:
     """``shells``: per atom a list of ``gto_small.Shell``; ``charges``: the nuclear charges; ``renormalize``: scale every
     contracted function to unit self-overlap (on the host, once), as ``sp_gaussian_mol`` does."""
 
+    # the C calls and the host normalisation of the route; ``gto_spd_device.DeviceSpdGaussians`` names its own
+    _WORKSPACE, _INTEGRALS, _DIPOLE = "evc_spgto_workspace_bytes", "evc_spgto_integrals_batch", "evc_spgto_dipole_batch"
+    _coefficients = staticmethod(contraction_coefficients)
+
     def __init__(self, charges: Sequence[float], shells, nelec: Optional[Tuple[int, int]] = None,
                  renormalize: bool = True, device=None):
         self.lib = _lib.load()
@@ -38,7 +42,8 @@ class DeviceGaussians:
         if len(self.shells) != self._charges_host.shape[0]:
             raise ValueError(f"{len(self.shells)} shell lists for {self._charges_host.shape[0]} charges")
         self.nelec = None if nelec is None else tuple(nelec)
-        coef = contraction_coefficients(self.shells, renormalize)
+        self.renormalize = bool(renormalize)
+        coef = self._coefficients(self.shells, renormalize)
         atom, l, off, ex, co, slices, n = [], [], [0], [], [], [], 0
         for at, (shs, cs) in enumerate(zip(self.shells, coef)):
             start = n
@@ -126,9 +131,9 @@ class DeviceGaussians:
         if dip is None:
             dip = self._dip[G] = torch.zeros((G, 3, self.nao, self.nao), dtype=F64, device=self.device)
         o = (C.c_double * 3)(*[float(x) for x in origin])
-        _lib.check(self.lib.evc_spgto_dipole_batch(
+        _lib.check(getattr(self.lib, self._DIPOLE)(
             self.natm, int(self.shell_l.shape[0]), G, R.data_ptr(), *self._basis_args(), C.cast(o, C.c_void_p),
-            dip.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream), "evc_spgto_dipole_batch")
+            dip.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream), self._DIPOLE)
         return dip
 
     def integrals(self, coords, need_grad: bool = True, packed: bool = False, out: Optional[dict] = None) -> DeviceAOBatch:
@@ -145,18 +150,18 @@ class DeviceGaussians:
             if out is None:
                 out = self._buffers[key] = self.allocate(G, need_grad, packed)
         nshell = int(self.shell_l.shape[0])
-        nbytes = self.lib.evc_spgto_workspace_bytes(A, nshell, int(self.exponents.shape[0]), self.nao, G)
+        nbytes = getattr(self.lib, self._WORKSPACE)(A, nshell, int(self.exponents.shape[0]), self.nao, G)
         if nbytes == 0:
-            raise _lib.EvcontHipError("evc_spgto_workspace_bytes: " + self.lib.evc_last_error().decode())
+            raise _lib.EvcontHipError(self._WORKSPACE + ": " + self.lib.evc_last_error().decode())
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         flags = (0 if need_grad else _lib.FLAG_ENERGY_ONLY) | \
                 ((_lib.FLAG_ERI_S4 | _lib.FLAG_IP1_S2KL) if packed else 0)
         cs = _lib.SgtoOutputs(**{k: (out[k].data_ptr() if out.get(k) is not None else None) for k in _FIELDS})
-        _lib.check(self.lib.evc_spgto_integrals_batch(
+        _lib.check(getattr(self.lib, self._INTEGRALS)(
             A, nshell, G, R.data_ptr(), self._charges.data_ptr(), *self._basis_args(), C.byref(cs), flags,
             self._ws.data_ptr(), int(self._ws.numel()), torch.cuda.current_stream(self.device).cuda_stream),
-            "evc_spgto_integrals_batch")
+            self._INTEGRALS)
         return DeviceAOBatch(S=out["S"], hcore=out["hcore"], eri=out["eri"], enuc=out["enuc"], natm=A,
                              ipovlp=out.get("ipovlp"), dhcore=out.get("dhcore"), eri_ip1=out.get("eri_ip1"),
                              gnuc=out.get("gnuc"), aoslices=self._aoslices, ip1_s2kl=packed and need_grad,

@@ -50,7 +50,8 @@ extern "C" {
                                  evc_cas_expand_workspace_bytes, evc_cas_expand_describe; additive:
                                  evc_properties_roots_batch, evc_properties_workspace_bytes, evc_sgto_dipole_batch;
                                  additive: evc_spgto_workspace_bytes, evc_spgto_integrals_batch,
-                                 evc_spgto_dipole_batch */
+                                 evc_spgto_dipole_batch; additive: evc_spdgto_workspace_bytes,
+                                 evc_spdgto_integrals_batch, evc_spdgto_dipole_batch */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -665,6 +666,31 @@ int evc_spgto_integrals_batch(int natm, int nshell, int count, const double *coo
 int evc_spgto_dipole_batch(int natm, int nshell, int count, const double *coords, const int *shell_atom,
                            const int *shell_l, const int *shell_prim_offset, const double *exponents,
                            const double *coefficients, const double origin[3], double *dip, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * AO integrals of molecules of contracted s, p and REAL SPHERICAL d Gaussian shells on the device (csrc/spdgto.hip; the
+ * host statement is evcont_amd/gto_spd.py spd_gaussian_mol): water in cc-pVDZ from the coordinates.  The argument lists,
+ * the outputs (evc_sgto_outputs), the three flags, the forms and the guarantees are those of the evc_spgto_* calls above;
+ * shell_l may be 0, 1 or 2.  AO order: shells in the given order, a p shell as x, y, z, a d shell as its five real
+ * spherical functions in the order m = -2 ... 2: xy, yz, 2z^2 - x^2 - y^2, xz, x^2 - y^2, each of the norm of the
+ * normalised primitive x y exp(-a r^2) times its coefficient (the Cartesian combination x^2 + y^2 + z^2 never appears).
+ * Limits: l <= 2, 1 <= natm <= 64, nao <= 64 (2l + 1 functions per shell), 1 ... 8 primitives per shell, at most 128
+ * primitives in all, 1 <= count <= 65535; contractions are segmented (a generally contracted table repeats its
+ * primitives).  A null required pointer (the gradient outputs are required unless EVC_FLAG_ENERGY_ONLY), a shape outside
+ * the limits, an l outside {0, 1, 2}, a shell_atom out of range or not ascending, a bad shell_prim_offset, a non-positive
+ * exponent, an unknown flag or a workspace that is too small or misaligned is refused before anything is launched
+ * (rc < 0, evc_last_error names the function).  A nucleus without functions is allowed.  Caller's stream, no allocation,
+ * no library state.  Molecules of s and p shells alone are served by both families; evc_spgto_* is the faster route for
+ * them and the two need not agree in the last bits.
+ * --------------------------------------------------------------------------------- */
+size_t evc_spdgto_workspace_bytes(int natm, int nshell, int nprim_total, int nao, int count);
+int evc_spdgto_integrals_batch(int natm, int nshell, int count, const double *coords, const double *charges,
+                               const int *shell_atom, const int *shell_l, const int *shell_prim_offset,
+                               const double *exponents, const double *coefficients, const evc_sgto_outputs *out, int flags,
+                               void *ws, size_t ws_bytes, void *stream);
+int evc_spdgto_dipole_batch(int natm, int nshell, int count, const double *coords, const int *shell_atom,
+                            const int *shell_l, const int *shell_prim_offset, const double *exponents,
+                            const double *coefficients, const double origin[3], double *dip, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Observables of continuation states (csrc/properties.hip; host statement: evcont_amd/properties.py; the reference's

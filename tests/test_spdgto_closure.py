@@ -1,0 +1,134 @@
+"""Host-side closure for csrc/spdgto.hip (device AO integrals of s, p and real spherical d shells), modelled on
+tests/test_spgto_closure.py: the calls are declared in the header, bound in ``_lib`` and exported, the file is built,
+every kernel it defines is launched through ``spdgto_launch`` and through nothing else, the calls add neither a profile
+stage nor an ABI version, spgto.hip keeps its five kernels and sgto.hip its four, and every refusal happens on the host."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "evcont_amd", "csrc")
+CALLS = ("evc_spdgto_workspace_bytes", "evc_spdgto_integrals_batch", "evc_spdgto_dipole_batch")
+KERNELS = {"spdgto_pair_kernel", "spdgto_one_kernel", "spdgto_nuc_kernel", "spdgto_two_kernel", "spdgto_dipole_kernel"}
+GLOBAL = r"__global__[^;{]*?\bvoid\s+(\w+)\s*\("
+
+
+def source(name="spdgto.hip"):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def test_calls_are_declared_bound_and_built():
+    from evcont_amd import _lib, build
+    build.build()
+    lib = _lib.load()
+    with open(os.path.join(REPO, "include", "evcont_hip.h")) as f:
+        hdr = f.read()
+    for name in CALLS:
+        assert f"{name}(" in hdr, name
+        assert name in _lib.SIGNATURES and hasattr(lib, name), name
+        assert name in hdr[:hdr.index("#define EVC_LAYOUT_FULL6")], "listed as additive in the ABI comment"
+        assert _lib.SIGNATURES[name] == _lib.SIGNATURES[name.replace("spdgto", "spgto")], "the s + p argument list"
+    assert "const evc_sgto_outputs *out" in hdr[hdr.index("int evc_spdgto_integrals_batch("):]
+    assert C.sizeof(_lib.SgtoOutputs) == 8 * 8
+    assert "spdgto.hip" in build.SOURCES and "spgto.hip" in build.SOURCES and "sgto.hip" in build.SOURCES
+
+
+def test_every_kernel_is_launched_through_spdgto_launch():
+    src = source()
+    defined = set(re.findall(GLOBAL, src))
+    launched = set(re.findall(r"\bspdgto_launch\(\s*(\w+)\s*[<,]", src))
+    assert defined == launched == KERNELS, sorted(defined ^ launched)
+    assert "<<<" not in src and "hipLaunchKernelGGL" not in src
+    assert len(re.findall(r"\bhipLaunchKernel\(", src)) == 1
+    helper = src[src.index("static void spdgto_launch("):]
+    assert "hipLaunchKernel(" in helper[:helper.index("\n}\n")]
+    assert "atomic" not in src.lower()
+
+
+def test_no_new_profile_stage_no_new_abi_version_and_the_other_files_as_they_were():
+    from evcont_amd import _lib
+    assert re.search(r"constexpr int kProfStages = 14;", source("pipeline.hpp"))
+    with open(os.path.join(REPO, "include", "evcont_hip.h")) as f:
+        assert re.search(r"#define\s+EVC_ABI_VERSION\s+10\b", f.read())
+    assert _lib.ABI_VERSION == 10
+    assert "note_kernel" not in source() and "EVC_PROF_" not in source()
+    assert set(re.findall(GLOBAL, source("spgto.hip"))) == \
+        {"spgto_pair_kernel", "spgto_one_kernel", "spgto_nuc_kernel", "spgto_two_kernel", "spgto_dipole_kernel"}
+    assert set(re.findall(GLOBAL, source("sgto.hip"))) == \
+        {"sgto_pair_kernel", "sgto_one_kernel", "sgto_nuc_kernel", "sgto_two_kernel"}
+
+
+def test_refusals_need_no_device():
+    """Every refused argument is caught on the host, before anything is launched: rc < 0 and a message that names the
+    function.  l = 2 passes the shape check (the call with it is refused only for what else is wrong), and a d shell
+    counts five functions."""
+    from evcont_amd import _lib, build
+    build.build()
+    lib = _lib.load()
+    i32 = lambda *v: np.array(v, dtype=np.int32)
+    f64 = lambda *v: np.array(v, dtype=np.float64)
+    # water-like: O with s(3), p(3), d(3); two H with s(3)
+    sa, sl, so = i32(0, 0, 0, 1, 2), i32(0, 1, 2, 0, 0), i32(0, 3, 6, 9, 12, 15)
+    ex, co = f64(*([3.4, 0.6, 0.2] * 5)), f64(*([0.2, 0.5, 0.4] * 5))
+    out = _lib.SgtoOutputs(*([256] * 8))
+    need = lib.evc_spdgto_workspace_bytes(3, 5, 15, 11, 2)
+    assert need >= 2 * 15 * 15 * 8
+    good = dict(natm=3, nshell=5, count=2, coords=256, charges=256, sa=sa, sl=sl, so=so, ex=ex, co=co,
+                out=C.byref(out), flags=0, ws=256, ws_bytes=need)
+    ptr = lambda a: None if a is None else a.ctypes.data
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return lib.evc_spdgto_integrals_batch(a["natm"], a["nshell"], a["count"], a["coords"], a["charges"], ptr(a["sa"]),
+                                              ptr(a["sl"]), ptr(a["so"]), ptr(a["ex"]), ptr(a["co"]), a["out"],
+                                              a["flags"], a["ws"], a["ws_bytes"], None)
+
+    no_grad = _lib.SgtoOutputs(256, 256, 256, 256, None, None, None, None)
+    no_eri = _lib.SgtoOutputs(256, 256, 256, None, 256, 256, 256, 256)
+    many = 17                                     # 17 shells of 8 primitives: 136 primitives
+    nine = i32(0, 9, 10, 11, 12, 13)              # a shell of 9 primitives
+    wide = 13                                     # 13 d shells: 65 functions
+    cases = (
+        (dict(natm=0), b"natm"), (dict(natm=65), b"natm"), (dict(nshell=0), b"nshell"), (dict(nshell=65), b"nshell"),
+        (dict(count=0), b"count"), (dict(count=65536), b"count"),
+        (dict(coords=None), b"null"), (dict(charges=None), b"null"), (dict(sa=None), b"null"), (dict(sl=None), b"null"),
+        (dict(so=None), b"null"), (dict(ex=None), b"null"), (dict(co=None), b"null"), (dict(out=None), b"null"),
+        (dict(ws=None), b"null"), (dict(out=C.byref(no_eri)), b"null"), (dict(out=C.byref(no_grad)), b"null"),
+        (dict(sl=i32(0, 0, 3, 0, 0)), b"l=3"), (dict(sl=i32(0, -1, 1, 0, 0)), b"l=-1"),
+        (dict(sa=i32(0, 0, 0, 1, 3)), b"shell_atom"), (dict(sa=i32(0, 0, 0, -1, 2)), b"shell_atom"),
+        (dict(sa=i32(0, 1, 0, 1, 2)), b"ascending"),
+        (dict(so=i32(1, 3, 6, 9, 12, 15)), b"shell_prim_offset"), (dict(so=i32(0, 3, 3, 9, 12, 15)), b"primitives"),
+        (dict(so=nine), b"primitives"),
+        (dict(nshell=many, natm=many, sa=i32(*range(many)), sl=i32(*([0] * many)), so=i32(*range(0, 8 * many + 1, 8)),
+              ex=f64(*([1.0] * 8 * many)), co=f64(*([1.0] * 8 * many))), b"primitives"),
+        (dict(nshell=wide, natm=wide, sa=i32(*range(wide)), sl=i32(*([2] * wide)), so=i32(*range(wide + 1)),
+              ex=f64(*([1.0] * wide)), co=f64(*([1.0] * wide))), b"nao=65"),
+        (dict(ex=f64(*([3.4, 0.0, 0.2] * 5))), b"exponent"), (dict(ex=f64(*([3.4, -1.0, 0.2] * 5))), b"exponent"),
+        (dict(flags=2), b"flags"), (dict(flags=64), b"flags"),
+        (dict(ws_bytes=need - 1), b"workspace"), (dict(ws=264), b"aligned"),
+    )
+    for kw, word in cases:
+        assert call(**kw) < 0, kw
+        msg = lib.evc_last_error()
+        assert word in msg and b"evc_spdgto_integrals_batch" in msg, (kw, msg)
+    # l = 2 is accepted by the shape check: with the d shell in place the first thing wrong is the workspace
+    assert call(ws_bytes=need - 1) < 0 and b"l=" not in lib.evc_last_error()
+    assert call(flags=_lib.FLAG_ENERGY_ONLY, out=C.byref(no_grad), natm=0) < 0       # (no_grad is fine with the flag)
+    for args in ((0, 5, 15, 11, 1), (65, 5, 15, 11, 1), (3, 0, 15, 11, 1), (3, 65, 65, 65, 1), (3, 5, 129, 11, 1),
+                 (3, 5, 15, 65, 1), (3, 5, 15, 26, 1), (3, 5, 15, 11, 0), (3, 5, 15, 11, 65536)):
+        assert lib.evc_spdgto_workspace_bytes(*args) == 0, args
+        assert b"evc_spdgto_workspace_bytes" in lib.evc_last_error()
+    assert lib.evc_spdgto_workspace_bytes(3, 5, 15, 25, 1) > 0                       # five functions per shell
+    assert lib.evc_spgto_workspace_bytes(3, 5, 15, 16, 1) == 0                       # the s + p call: three
+    o = f64(0.0, 0.0, 0.0)
+    dip = lambda **kw: lib.evc_spdgto_dipole_batch(
+        kw.get("natm", 3), 5, 2, kw.get("coords", 256), ptr(kw.get("sa", sa)), ptr(kw.get("sl", sl)), ptr(so),
+        ptr(kw.get("ex", ex)), ptr(co), kw.get("origin", o.ctypes.data), kw.get("dip", 256), None)
+    for kw, word in ((dict(natm=65), b"natm"), (dict(coords=None), b"null"), (dict(origin=None), b"null"),
+                     (dict(dip=None), b"null"), (dict(sa=i32(0, 1, 0, 1, 2)), b"ascending"),
+                     (dict(sl=i32(0, 1, 3, 0, 0)), b"l=3"), (dict(ex=f64(*([3.4, 0.0, 0.2] * 5))), b"exponent")):
+        assert dip(**kw) < 0, kw
+        assert word in lib.evc_last_error() and b"evc_spdgto_dipole_batch" in lib.evc_last_error(), kw
