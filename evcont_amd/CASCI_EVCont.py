@@ -12,7 +12,12 @@ pruning, the device-resident packed copy — is shared with the other containers
 With a ``cisolver`` (``fci_small.SmallFCI()`` or ``fci_device.DeviceFCI()``) nothing third-party is needed:
 ``append_to_rdms(mol)`` runs ``cas_small.casci`` on the molecule's RHF orbitals and reduces each pair of CAS states in
 different orbital sets to a non-orthogonal ``transform_ci`` and an active-space t-RDM (``cas_small``),
-on the device when the solver has ``cas_trans_rdm12_rows``.  Ground state only, as in the reference.
+on the device when the solver has ``cas_trans_rdm12_rows``.
+
+``nroots`` / ``roots_train`` mean what they mean in ``FCI_EVCont_obj``: ``max(roots_train) + 1`` CASCI roots are solved per
+geometry (``cas_small.casci_roots``) and the listed ones appended in root order, with one ``mol_index`` per geometry.  The
+roots of a geometry share their orbitals, so their rows against the stored states come from one block call
+(``cas_small.trans_rdm12_block`` / ``DeviceFCI.cas_trans_rdm12_block``).  Built-in route only.
 """
 from __future__ import annotations
 
@@ -22,8 +27,15 @@ from .containers import TRDMContainer
 
 
 class CAS_EVCont_obj(TRDMContainer):
-    def __init__(self, ncas, neleca, casci_solver=None, pair_rdm_fun=None, cisolver=None):
+    def __init__(self, ncas, neleca, casci_solver=None, pair_rdm_fun=None, cisolver=None, nroots=1, roots_train=None):
         super().__init__()
+        self.nroots = nroots
+        if roots_train is None:
+            self.roots_train = list(range(nroots))
+        else:
+            assert isinstance(roots_train, list) and roots_train and min(roots_train) >= 0
+            self.roots_train = sorted(roots_train)
+        self.mol_index = []
         self.ncas = ncas
         self.neleca = neleca
         self.cascis = []
@@ -35,6 +47,9 @@ class CAS_EVCont_obj(TRDMContainer):
     def _append_own(self, mol):
         """The built-in route: ``cas_small.casci`` and the pair reduction of ``cas_small`` (host or device)."""
         from . import cas_small
+        mindex = 0 if len(self.mol_index) == 0 else max(self.mol_index) + 1
+        if self.roots_train != [0]:
+            return self._append_own_roots(mol, mindex)
         state = cas_small.casci(mol, self.ncas, self.neleca, self.cisolver)
         kets = self.cascis + [state]
         # (a pair beyond the conditioning guard raises here: the container is then as it was)
@@ -44,11 +59,34 @@ class CAS_EVCont_obj(TRDMContainer):
             ovlp, one, two = cas_small.trans_rdm12_rows(state, kets, self.cisolver)
         self.cascis.append(state)
         self.ens.append(state.e_tot)
+        self.mol_index.append(mindex)
         self._append_state(ovlp, one, two)
+
+    def _append_own_roots(self, mol, mindex):
+        """Several roots of one geometry: one block call gives the rows of all of them, the new corner included."""
+        from . import cas_small
+        roots = cas_small.casci_roots(mol, self.ncas, self.neleca, self.cisolver, max(self.roots_train) + 1)
+        bras = [roots[k] for k in self.roots_train]
+        kets = self.cascis + bras
+        # (a pair beyond the conditioning guard raises here: the container is then as it was)
+        if hasattr(self.cisolver, "cas_trans_rdm12_block"):
+            ovlp, one, two = self.cisolver.cas_trans_rdm12_block(bras, kets)
+        else:
+            ovlp, one, two = cas_small.trans_rdm12_block(bras, kets, self.cisolver)
+        T = len(self.cascis)
+        for r, state in enumerate(bras):
+            # root r as the bra against everything before it and itself: the arrays a one-by-one append would give
+            self.cascis.append(state)
+            self.ens.append(state.e_tot)
+            self.mol_index.append(mindex)
+            self._append_state(ovlp[r, :T + r + 1], one[r, :T + r + 1], two[r, :T + r + 1])
 
     def append_to_rdms(self, mol):
         if self.cisolver is not None:
             return self._append_own(mol)
+        if self.roots_train != [0]:
+            raise NotImplementedError("CAS_EVCont_obj: several roots per geometry need the built-in route (cisolver=...); "
+                                      "the PySCF / pair_rdm_fun route is ground state only")
         if self.casci_solver is None:
             try:
                 from pyscf.mcscf import CASCI
@@ -78,5 +116,7 @@ class CAS_EVCont_obj(TRDMContainer):
         """``CASCI_EVCont.py:345-361``."""
         self._prune_arrays(keep_ids)
         self.cascis = [self.cascis[i] for i in keep_ids]
+        if self.mol_index:
+            self.mol_index = [self.mol_index[i] for i in keep_ids]
         if self.ens:
             self.ens = [self.ens[i] for i in keep_ids]

@@ -166,6 +166,11 @@ SIGNATURES = {
     "evc_fci_rotate_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int]),
     "evc_fci_rotate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_fci_rotate_block_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                                          C.c_int]),
+    "evc_fci_rotate_block": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
     "evc_sgto_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "evc_sgto_integrals_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(SgtoOutputs), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -25,7 +25,10 @@ where the minors of ``transform_ci`` compound it: unrelated random orbitals with
 1e-10 inside the guard.
 
 ``casci(mol, ncas, nelecas, cisolver)`` is the ground-state CASCI on RHF orbitals (``scf_small.rhf``) that produces such
-states for any molecule ``integrals.ao_arrays`` accepts.
+states for any molecule ``integrals.ao_arrays`` accepts; ``casci_roots(..., nroots)`` gives the lowest ``nroots`` states on
+the same orbitals.  The intermediates above depend on the two orbital sets, not on the CI vectors, so for several bras of
+one orbital set ``trans_rdm12_block(bras, kets)`` forms them once per group of kets that share their orbitals (DESIGN.md
+8.1.6); it is the statement ``DeviceFCI.cas_trans_rdm12_block`` is held to.
 """
 from __future__ import annotations
 
@@ -52,6 +55,19 @@ class CASState:
 
 def casci(mol, ncas: int, nelecas, cisolver) -> CASState:
     """Ground-state CASCI of ``mol`` on its RHF orbitals; ``nelecas``: active electrons, a number or ``(alpha, beta)``."""
+    return _casci_states(mol, ncas, nelecas, cisolver, None)[0]
+
+
+def casci_roots(mol, ncas: int, nelecas, cisolver, nroots: int):
+    """The ``nroots`` lowest CASCI states of ``mol`` on its RHF orbitals, ``e_tot`` ascending: one RHF, one set of
+    active-space integrals and one ``cisolver.kernel(..., nroots=nroots)``; every state holds the same ``U`` array."""
+    if int(nroots) < 1:
+        raise ValueError(f"casci_roots: nroots={nroots}, at least 1")
+    return _casci_states(mol, ncas, nelecas, cisolver, int(nroots))
+
+
+def _casci_states(mol, ncas: int, nelecas, cisolver, nroots: Optional[int]):
+    """The body of ``casci`` (``nroots=None``: the solver's plain ground-state call) and ``casci_roots``."""
     from .integrals import ao_arrays, energy_nuc
     from .scf_small import rhf
     ao = ao_arrays(mol, need_grad=False)
@@ -78,11 +94,19 @@ def casci(mol, ncas: int, nelecas, cisolver) -> CASState:
     ecore = float(energy_nuc(mol)) + float(np.sum(Dc * (h + 0.5 * Vc)))
     h1eff = Ca.T @ (h + Vc) @ Ca
     h2 = np.einsum("pqrs,pi,qj,rk,sl->ijkl", eri, Ca, Ca, Ca, Ca, optimize=True)
-    e, ci = cisolver.kernel(h1eff, h2, ncas, nel)
+    if nroots is None:
+        e, ci = cisolver.kernel(h1eff, h2, ncas, nel)
+        es, cis = [e], [ci]
+    else:
+        es, cis = cisolver.kernel(h1eff, h2, ncas, nel, nroots=nroots)
+        if nroots == 1 and np.ndim(es) == 0:        # (a solver that returns one root bare)
+            es, cis = [es], [cis]
+        order = np.argsort(np.asarray(es, dtype=np.float64), kind="stable")
+        es, cis = [es[i] for i in order], [cis[i] for i in order]
     w, V = np.linalg.eigh(S)
     U = (V * np.sqrt(w)) @ V.T @ Cm                 # X S C with X = S^(-1/2)
-    return CASState(U=U, ncore=ncore, ncas=ncas, nelecas=nel, ci=np.asarray(ci, dtype=np.float64),
-                    e_tot=float(e) + ecore)
+    return [CASState(U=U, ncore=ncore, ncas=ncas, nelecas=nel, ci=np.asarray(ci, dtype=np.float64),
+                     e_tot=float(e) + ecore) for e, ci in zip(es, cis)]
 
 
 def _same_shape(bra: CASState, ket: CASState) -> None:
@@ -147,4 +171,58 @@ def trans_rdm12_rows(bra: CASState, kets: Sequence[CASState], cisolver: Optional
         ovlp[i] = float(np.dot(ca.reshape(-1), ck.reshape(-1)))
         d1, d2 = solver.trans_rdm12(ca, ck.reshape(ca.shape), bra.ncas, tuple(bra.nelecas))
         dm1[i], dm2[i] = expand(ovlp[i], d1, d2, A_a, B_a, Qc)
+    return ovlp, dm1, dm2
+
+
+def same_orbitals(a: CASState, b: CASState) -> bool:
+    return a.U is b.U or (a.U.shape == b.U.shape and np.array_equal(a.U, b.U))
+
+
+def ket_groups(kets: Sequence[CASState]):
+    """``[(first, count)]``: the runs of consecutive kets that share their orbitals (one geometry's roots)."""
+    groups, i = [], 0
+    while i < len(kets):
+        j = i + 1
+        while j < len(kets) and same_orbitals(kets[i], kets[j]) and (kets[i].ncore, kets[i].ncas, tuple(
+                kets[i].nelecas)) == (kets[j].ncore, kets[j].ncas, tuple(kets[j].nelecas)):
+            j += 1
+        groups.append((i, j - i))
+        i = j
+    return groups
+
+
+def check_block(who: str, bras: Sequence[CASState], kets: Sequence[CASState]) -> None:
+    if not bras or not kets:
+        raise ValueError(f"{who}: no bras or no kets")
+    for r, bra in enumerate(bras[1:], 1):
+        _same_shape(bras[0], bra)
+        if not same_orbitals(bras[0], bra):
+            raise ValueError(f"{who}: bra {r} differs from bra 0 in its orbitals U (the bras of a block are the roots of "
+                             "one geometry)")
+
+
+def trans_rdm12_block(bras: Sequence[CASState], kets: Sequence[CASState], cisolver: Optional[object] = None):
+    """``(ovlp (R,K), dm1 (R,K,N,N), dm2 (R,K,N,N,N,N))``: the stack of ``trans_rdm12_rows(bra_r, kets)`` for bras that
+    share their orbitals (``ValueError`` otherwise).  The pair intermediates depend on the two orbital sets alone, so
+    they are formed once per group of consecutive kets that share a ``U``, and each ket is rotated once.  Kets in the
+    bras' own orbitals take the same route (``s_eff = 1`` to rounding)."""
+    bras, kets = list(bras), list(kets)
+    check_block("cas_small.trans_rdm12_block", bras, kets)
+    rotate = getattr(cisolver, "transform_ci", None) or fci_small.transform_ci
+    solver = cisolver if hasattr(cisolver, "trans_rdm12") else fci_small.SmallFCI()
+    bra0 = bras[0]
+    n, R, K = bra0.U.shape[0], len(bras), len(kets)
+    nelec = tuple(bra0.nelecas)
+    ovlp, dm1, dm2 = np.empty((R, K)), np.empty((R, K, n, n)), np.empty((R, K, n, n, n, n))
+    for first, count in ket_groups(kets):
+        fac, s_eff, A_a, B_a, Qc = pair_intermediates(bra0, kets[first], f"(bras, ket {first})")
+        u = np.ascontiguousarray(s_eff.T)
+        for i in range(first, first + count):
+            _same_shape(bra0, kets[i])
+            ck = fac * np.asarray(rotate(kets[i].ci, nelec, u))
+            for r, bra in enumerate(bras):
+                ca = np.asarray(bra.ci, dtype=np.float64)
+                ovlp[r, i] = float(np.dot(ca.reshape(-1), ck.reshape(-1)))
+                d1, d2 = solver.trans_rdm12(ca, ck.reshape(ca.shape), bra0.ncas, nelec)
+                dm1[r, i], dm2[r, i] = expand(ovlp[r, i], d1, d2, A_a, B_a, Qc)
     return ovlp, dm1, dm2

@@ -13,6 +13,8 @@
 // rows of u it needs and every element it reads are wave-uniform.
 // T is formed in panels of its columns (the new strings J', I'), whose width depends on the shape alone; a panel cuts
 // the output index of a product, never a sum, so every workspace gives the same bits.
+// evc_fci_rotate_block rotates several vectors under one u: each panel of T is formed once and the product launches
+// take the vectors in their grid's z, every vector through the arithmetic of the single call.
 #include <math.h>
 
 #include "common.hpp"
@@ -22,6 +24,7 @@ namespace evc {
 
 constexpr int kRotMaxMinor = 8;             // largest instantiated determinant
 constexpr int64_t kRotPanelDoubles = 1 << 19;   // a panel of T holds about this many doubles (4 MiB)
+constexpr int kRotVecs = 16;                // vectors one product launch takes (its grid's z)
 
 struct RotU {
     double v[kFciMaxOrb * kFciMaxOrb];      // row-major (norb, norb)
@@ -128,10 +131,19 @@ __global__ __launch_bounds__(64) void fci_minor_kernel(RotU w, const int32_t *__
 // MFMA s of a step, lane group g = lane / 16 carries l = l0 + 4 g + s, so that the four operands a lane holds are
 // adjacent in l (a row of an A stored l-contiguous is read in whole 128-byte lines) and a fragment of an operand
 // stored [l][.] is one line.  Elements beyond m, n, k are neither read nor written; they enter as 0.
-__global__ __launch_bounds__(256) void fci_rotate_gemm_kernel(const double *__restrict__ A, int64_t sam, int64_t sak,
-                                                              const double *__restrict__ B, int64_t ldb,
-                                                              double *__restrict__ C, int64_t ldc, int64_t m, int64_t n,
-                                                              int64_t k) {
+// blockIdx.z picks one of up to kRotVecs products of the same shape and strides (evc_fci_rotate_block: the vectors that
+// share a panel of T); the operands reach the kernel by value, and an element of C is the same sum in the same order
+// whichever z computes it.
+struct RotOps {
+    const double *A[kRotVecs];
+    const double *B[kRotVecs];
+    double *C[kRotVecs];
+};
+__global__ __launch_bounds__(256) void fci_rotate_gemm_kernel(RotOps ops, int64_t sam, int64_t sak, int64_t ldb,
+                                                              int64_t ldc, int64_t m, int64_t n, int64_t k) {
+    const double *__restrict__ A = ops.A[blockIdx.z];
+    const double *__restrict__ B = ops.B[blockIdx.z];
+    double *__restrict__ C = ops.C[blockIdx.z];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int64_t i0 = (int64_t)blockIdx.y * 64 + (wave >> 1) * 32, j0 = (int64_t)blockIdx.x * 64 + (wave & 1) * 32;
@@ -271,7 +283,7 @@ static int64_t rot_panel_width(int64_t ns) {
     return w < ns ? w : ns;
 }
 
-static int rot_plan_spin(int norb, int nocc, int64_t ns, const double *u, RotSpin &s) {
+static int rot_plan_spin(const char *who, int norb, int nocc, int64_t ns, const double *u, RotSpin &s) {
     const uint32_t full = norb >= 32 ? 0xFFFFFFFFu : (1u << norb) - 1u;
     s.ns = ns;
     s.pw = rot_panel_width(ns);
@@ -298,8 +310,8 @@ static int rot_plan_spin(int norb, int nocc, int64_t ns, const double *u, RotSpi
     }
     bool singular = false;
     const double det = rot_det(norb, u, singular);
-    EVC_REQUIRE(!singular, "evc_fci_rotate: u is numerically singular (smallest pivot below 1e-12 of the largest) and "
-                "%d electrons in %d orbitals need its inverse (complementary minors)", nocc, norb);
+    EVC_REQUIRE(!singular, "%s: u is numerically singular (smallest pivot below 1e-12 of the largest) and "
+                "%d electrons in %d orbitals need its inverse (complementary minors)", who, nocc, norb);
     double inv[kFciMaxOrb * kFciMaxOrb];
     rot_invert(norb, u, inv);
     s.K = norb - nocc;
@@ -327,16 +339,17 @@ static void rot_launch_minor(const RotSpin &s, const int32_t *strs, int64_t j0, 
     }
 }
 
-static void rot_launch_gemm(const double *A, int64_t sam, int64_t sak, const double *B, int64_t ldb, double *C,
-                            int64_t ldc, int64_t m, int64_t n, int64_t k, hipStream_t st) {
-    rotate_launch(fci_rotate_gemm_kernel, dim3((unsigned)ceil_div(n, 64), (unsigned)ceil_div(m, 64)), dim3(256), st, A, sam,
-                  sak, B, ldb, C, ldc, m, n, k);
+// nz products of one shape, operands z of `ops`
+static void rot_launch_gemm(const RotOps &ops, int nz, int64_t sam, int64_t sak, int64_t ldb, int64_t ldc, int64_t m,
+                            int64_t n, int64_t k, hipStream_t st) {
+    rotate_launch(fci_rotate_gemm_kernel, dim3((unsigned)ceil_div(n, 64), (unsigned)ceil_div(m, 64), (unsigned)nz),
+                  dim3(256), st, ops, sam, sak, ldb, ldc, m, n, k);
 }
 
-// Workspace: M (na, nb) | T_a | T_b.  Resident: T_a (na, na) and T_b (nb, nb) whole; when both spins have the same
-// strings and the same u, T_b is formed once and serves as T_a.  Panelled: one panel (ns, pw) of each.
+// Workspace: M (nvec of (na, nb)) | T_a | T_b.  Resident: T_a (na, na) and T_b (nb, nb) whole; when both spins have the
+// same strings and the same u, T_b is formed once and serves as T_a.  Panelled: one panel (ns, pw) of each.
 struct RotLayout {
-    size_t m_bytes, ta_full, tb_full, ta_panel, tb_panel;
+    size_t m_bytes, ta_full, tb_full, ta_panel, tb_panel;   // m_bytes: the M of one vector
 };
 static RotLayout rot_layout(int64_t na, int64_t nb) {
     RotLayout l;
@@ -348,9 +361,9 @@ static RotLayout rot_layout(int64_t na, int64_t nb) {
     return l;
 }
 // the resident grant, and the least one: the panelled form where it is the smaller
-static size_t rot_resident_bytes(const RotLayout &l) { return l.m_bytes + l.ta_full + l.tb_full; }
-static size_t rot_least_bytes(const RotLayout &l) {
-    const size_t part = l.m_bytes + l.ta_panel + l.tb_panel, full = rot_resident_bytes(l);
+static size_t rot_resident_bytes(const RotLayout &l, int nvec) { return nvec * l.m_bytes + l.ta_full + l.tb_full; }
+static size_t rot_least_bytes(const RotLayout &l, int nvec) {
+    const size_t part = nvec * l.m_bytes + l.ta_panel + l.tb_panel, full = rot_resident_bytes(l, nvec);
     return part < full ? part : full;
 }
 static void clear_rotate_record() { note_kernel(EVC_PROF_FCI_ROTATE, "%s", ""); }
@@ -365,39 +378,39 @@ static int rot_shape(const char *who, int norb, int nocc_a, int nocc_b, int64_t 
     return 0;
 }
 
-}  // namespace evc
-
-using namespace evc;
-
-extern "C" size_t evc_fci_rotate_workspace_bytes(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, int minimal) {
-    if (rot_shape("evc_fci_rotate_workspace_bytes", norb, nocc_a, nocc_b, na, nb)) return 0;
-    const RotLayout l = rot_layout(na, nb);
-    return minimal ? rot_least_bytes(l) : rot_resident_bytes(l);
-}
-
-extern "C" int evc_fci_rotate(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, const int32_t *strs_a,
-                              const int32_t *strs_b, const double *u_a, const double *u_b, const double *c, double *out,
-                              void *ws, size_t ws_bytes, void *stream) {
-    if (int rc = rot_shape("evc_fci_rotate", norb, nocc_a, nocc_b, na, nb)) return rc;
-    EVC_REQUIRE(strs_a && strs_b && u_a && u_b && c && out && ws, "evc_fci_rotate: null pointer");
-    EVC_REQUIRE(c != out, "evc_fci_rotate: out must not alias c");
-    EVC_REQUIRE(aligned16(ws), "evc_fci_rotate: workspace not 16-byte aligned");
+// Both entry points: every refusal, then the launches for c[v] -> out[v], v < nvec, under one (u_a, u_b).  A panel of
+// T is formed once and applied to all vectors, kRotVecs of them per product launch; vector v goes through the launches
+// of a single call on it with the same arguments but its own M, so it has that call's bits.  The record is the caller's.
+static int rot_run(const char *who, int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, const int32_t *strs_a,
+                   const int32_t *strs_b, const double *u_a, const double *u_b, int nvec, const double *const *c,
+                   double *const *out, void *ws, size_t ws_bytes, void *stream, RotSpin &sa, RotSpin &sb) {
+    if (int rc = rot_shape(who, norb, nocc_a, nocc_b, na, nb)) return rc;
+    EVC_REQUIRE(nvec >= 1, "%s: nvec=%d, at least 1", who, nvec);
+    EVC_REQUIRE(strs_a && strs_b && u_a && u_b && c && out && ws, "%s: null pointer", who);
+    for (int v = 0; v < nvec; ++v) EVC_REQUIRE(c[v] && out[v], "%s: null pointer (vector %d)", who, v);
+    for (int v = 0; v < nvec; ++v)
+        for (int w = 0; w < nvec; ++w) {
+            EVC_REQUIRE(out[v] != c[w], "%s: out must not alias c (output %d, input %d)", who, v, w);
+            EVC_REQUIRE(v == w || out[v] != out[w], "%s: outputs %d and %d are the same", who, v, w);
+        }
+    EVC_REQUIRE(aligned16(ws), "%s: workspace not 16-byte aligned", who);
     const RotLayout l = rot_layout(na, nb);
     bool shared = nocc_a == nocc_b;   // one T serves both spins
     for (int i = 0; shared && i < norb * norb; ++i) shared = u_a[i] == u_b[i];
-    const size_t full = rot_resident_bytes(l), need = rot_least_bytes(l);
-    EVC_REQUIRE(ws_bytes >= need, "evc_fci_rotate: workspace of %zu bytes, at least %zu needed for %lld x %lld strings",
-                ws_bytes, need, (long long)na, (long long)nb);
-    RotSpin sa, sb;
-    if (int rc = rot_plan_spin(norb, nocc_a, na, u_a, sa)) return rc;
-    if (int rc = rot_plan_spin(norb, nocc_b, nb, u_b, sb)) return rc;
+    const size_t full = rot_resident_bytes(l, nvec), need = rot_least_bytes(l, nvec);
+    EVC_REQUIRE(ws_bytes >= need, "%s: workspace of %zu bytes, at least %zu needed for %d vector(s) of %lld x %lld strings",
+                who, ws_bytes, need, nvec, (long long)na, (long long)nb);
+    if (int rc = rot_plan_spin(who, norb, nocc_a, na, u_a, sa)) return rc;
+    if (int rc = rot_plan_spin(who, norb, nocc_b, nb, u_b, sb)) return rc;
     hipStream_t st = as_stream(stream);
     clear_rotate_record();
     const bool resident = ws_bytes >= full;
-    double *M = static_cast<double *>(ws);
-    double *Ta = reinterpret_cast<double *>(static_cast<char *>(ws) + l.m_bytes);
-    double *Tb = resident ? (shared ? Ta : reinterpret_cast<double *>(static_cast<char *>(ws) + l.m_bytes + l.ta_full))
-                          : reinterpret_cast<double *>(static_cast<char *>(ws) + l.m_bytes + l.ta_panel);
+    char *base = static_cast<char *>(ws);
+    char *tbase = base + nvec * l.m_bytes;
+    double *Ta = reinterpret_cast<double *>(tbase);
+    double *Tb = resident ? (shared ? Ta : reinterpret_cast<double *>(tbase + l.ta_full))
+                          : reinterpret_cast<double *>(tbase + l.ta_panel);
+    auto M = [&](int v) { return reinterpret_cast<double *>(base + v * l.m_bytes); };
     // M[:, J'] = sum_J c[:, J] T_b[J, J'], panel of J' by panel
     for (int64_t p = 0; p < sb.npanels; ++p) {
         const int64_t j0 = p * sb.pw, w = nb - j0 < sb.pw ? nb - j0 : sb.pw;
@@ -405,8 +418,17 @@ extern "C" int evc_fci_rotate(int norb, int nocc_a, int nocc_b, int64_t na, int6
         const int64_t ld = resident ? nb : sb.pw;
         rot_launch_minor(sb, strs_b, j0, w, T, ld, st);
         EVC_LAUNCH_CHECK("fci_minor_kernel");
-        rot_launch_gemm(c, nb, 1, T, ld, M + j0, nb, na, w, nb, st);
-        EVC_LAUNCH_CHECK("fci_rotate_gemm_kernel");
+        for (int v0 = 0; v0 < nvec; v0 += kRotVecs) {
+            const int nz = nvec - v0 < kRotVecs ? nvec - v0 : kRotVecs;
+            RotOps ops = {};
+            for (int z = 0; z < nz; ++z) {
+                ops.A[z] = c[v0 + z];
+                ops.B[z] = T;
+                ops.C[z] = M(v0 + z) + j0;
+            }
+            rot_launch_gemm(ops, nz, nb, 1, ld, nb, na, w, nb, st);
+            EVC_LAUNCH_CHECK("fci_rotate_gemm_kernel");
+        }
     }
     // out[I', :] = sum_I T_a[I, I'] M[I, :], panel of I' by panel
     for (int64_t p = 0; p < sa.npanels; ++p) {
@@ -417,9 +439,62 @@ extern "C" int evc_fci_rotate(int norb, int nocc_a, int nocc_b, int64_t na, int6
             rot_launch_minor(sa, strs_a, i0, w, T, ld, st);
             EVC_LAUNCH_CHECK("fci_minor_kernel");
         }
-        rot_launch_gemm(T, 1, ld, M, nb, out + i0 * nb, nb, w, nb, na, st);
-        EVC_LAUNCH_CHECK("fci_rotate_gemm_kernel");
+        for (int v0 = 0; v0 < nvec; v0 += kRotVecs) {
+            const int nz = nvec - v0 < kRotVecs ? nvec - v0 : kRotVecs;
+            RotOps ops = {};
+            for (int z = 0; z < nz; ++z) {
+                ops.A[z] = T;
+                ops.B[z] = M(v0 + z);
+                ops.C[z] = out[v0 + z] + i0 * nb;
+            }
+            rot_launch_gemm(ops, nz, 1, ld, nb, nb, w, nb, na, st);
+            EVC_LAUNCH_CHECK("fci_rotate_gemm_kernel");
+        }
     }
+    return 0;
+}
+
+}  // namespace evc
+
+using namespace evc;
+
+extern "C" size_t evc_fci_rotate_workspace_bytes(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, int minimal) {
+    if (rot_shape("evc_fci_rotate_workspace_bytes", norb, nocc_a, nocc_b, na, nb)) return 0;
+    const RotLayout l = rot_layout(na, nb);
+    return minimal ? rot_least_bytes(l, 1) : rot_resident_bytes(l, 1);
+}
+
+extern "C" size_t evc_fci_rotate_block_workspace_bytes(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, int nvec,
+                                                       int minimal) {
+    if (rot_shape("evc_fci_rotate_block_workspace_bytes", norb, nocc_a, nocc_b, na, nb)) return 0;
+    if (nvec < 1) {
+        set_error("evc_fci_rotate_block_workspace_bytes: nvec=%d, at least 1", nvec);
+        return 0;
+    }
+    const RotLayout l = rot_layout(na, nb);
+    return minimal ? rot_least_bytes(l, nvec) : rot_resident_bytes(l, nvec);
+}
+
+extern "C" int evc_fci_rotate_block(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, const int32_t *strs_a,
+                                    const int32_t *strs_b, const double *u_a, const double *u_b, int nvec,
+                                    const double *const *c, double *const *out, void *ws, size_t ws_bytes, void *stream) {
+    RotSpin sa, sb;
+    if (int rc = rot_run("evc_fci_rotate_block", norb, nocc_a, nocc_b, na, nb, strs_a, strs_b, u_a, u_b, nvec, c, out, ws,
+                         ws_bytes, stream, sa, sb))
+        return rc;
+    note_kernel(EVC_PROF_FCI_ROTATE, "fci_minor_kernel<%d> + fci_minor_kernel<%d> comp=%d,%d panels=%lld,%lld + "
+                "fci_rotate_gemm_kernel vecs=%d", sa.K, sb.K, sa.comp, sb.comp, (long long)sa.npanels, (long long)sb.npanels,
+                nvec);
+    return 0;
+}
+
+extern "C" int evc_fci_rotate(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, const int32_t *strs_a,
+                              const int32_t *strs_b, const double *u_a, const double *u_b, const double *c, double *out,
+                              void *ws, size_t ws_bytes, void *stream) {
+    RotSpin sa, sb;
+    if (int rc = rot_run("evc_fci_rotate", norb, nocc_a, nocc_b, na, nb, strs_a, strs_b, u_a, u_b, 1, &c, &out, ws, ws_bytes,
+                         stream, sa, sb))
+        return rc;
     note_kernel(EVC_PROF_FCI_ROTATE, "fci_minor_kernel<%d> + fci_minor_kernel<%d> comp=%d,%d panels=%lld,%lld + "
                 "fci_rotate_gemm_kernel", sa.K, sb.K, sa.comp, sb.comp, (long long)sa.npanels, (long long)sb.npanels);
     return 0;

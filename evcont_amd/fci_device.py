@@ -10,7 +10,9 @@ same call with its two-body rows written on the device in the evaluator's layout
 set of ``resident.ResidentFCI_EVCont_obj``), and ``transform_ci(ci, nelec, u)``
 (``csrc/fci_rotate.hip``), which rotates a state solved in another orbital basis into the OAO basis, and
 ``cas_trans_rdm12_rows(bra, kets)``: the t-RDMs between CAS states in different orbital sets, expanded to all N orbitals
-on the device (``csrc/cas_expand.hip``; ``CAS_EVCont_obj(ncas, neleca, cisolver=DeviceFCI())``).  Opt in with
+on the device (``csrc/cas_expand.hip``; ``CAS_EVCont_obj(ncas, neleca, cisolver=DeviceFCI())``), with
+``cas_trans_rdm12_block(bras, kets)`` for the roots of one geometry (one ``evc_fci_rotate_block`` per stored geometry;
+``transform_ci_block`` is that rotation on its own).  Opt in with
 ``FCI_EVCont_obj(cisolver=DeviceFCI(), cibasis="OAO")``, or ``cibasis="canonical"`` to solve in the Hartree-Fock basis,
 where the Davidson solver's diagonal preconditioner works best near equilibrium.
 
@@ -511,6 +513,131 @@ class DeviceFCI:
                                  ub.ctypes.data, dc.data_ptr(), out.data_ptr(), self._ws.data_ptr(), grant,
                                  self._stream()), "evc_fci_rotate")
         return out, na, nb
+
+    def transform_ci_block(self, cis, nelec, u):
+        """``transform_ci`` of several vectors under one ``u`` (or pair): a list of numpy ``(na, nb)`` arrays, each with
+        the bits ``transform_ci`` gives on it.  One ``evc_fci_rotate_block`` call: the minors of ``u`` are formed once."""
+        outs, na, nb = self._rotate_block(cis, _nelec(nelec), u)
+        return [o.cpu().numpy().reshape(na, nb) for o in outs]
+
+    def _rotate_block(self, cis, nelec, u):
+        """``transform_ci_block`` with the results left on the device: ``([na * nb doubles] per vector, na, nb)``."""
+        cis = list(cis)
+        if not cis:
+            raise EvcontHipError("DeviceFCI.transform_ci_block: no vectors")
+        if isinstance(u, (tuple, list)):
+            ua, ub = (np.ascontiguousarray(x, dtype=np.float64) for x in u)
+        else:
+            ua = ub = np.ascontiguousarray(u, dtype=np.float64)
+        norb, nvec = ua.shape[0], len(cis)
+        if ua.shape != (norb, norb) or ub.shape != (norb, norb):
+            raise EvcontHipError(f"DeviceFCI.transform_ci_block: u of shape {ua.shape} / {ub.shape} (square matrices of "
+                                 "one size)")
+        lib, _, _, na, nb, _ = self._setup(norb, nelec)
+        dsa, dsb = self._masks[(norb, nelec)]
+        least = lib.evc_fci_rotate_block_workspace_bytes(norb, nelec[0], nelec[1], na, nb, nvec, 1)
+        full = lib.evc_fci_rotate_block_workspace_bytes(norb, nelec[0], nelec[1], na, nb, nvec, 0)
+        if least == 0 or full == 0:
+            check(-1, "evc_fci_rotate_block_workspace_bytes")
+        # the rule of _rotate, with one intermediate per vector
+        grant = ((full if full <= ROTATE_RESIDENT_BYTES else least) if self.workspace_bytes is None
+                 else min(int(self.workspace_bytes), full))
+        if grant < least:
+            raise EvcontHipError(f"DeviceFCI.transform_ci_block: workspace_bytes={grant}, but {nvec} vectors of {na} x {nb} "
+                                 f"strings need at least {least} bytes ({full} to keep both matrices of minors resident)")
+        if self._ws.numel() < grant:
+            self._ws = None
+            self._ws = torch.empty(grant, dtype=torch.uint8, device=self._dev())
+        dcs = [self._upload(ci, na, nb, cache=False) for ci in cis]
+        outs = [torch.empty(na * nb, dtype=F64, device=self._dev()) for _ in cis]
+        cp = (C.c_void_p * nvec)(*[t.data_ptr() for t in dcs])
+        op = (C.c_void_p * nvec)(*[t.data_ptr() for t in outs])
+        check(lib.evc_fci_rotate_block(norb, nelec[0], nelec[1], na, nb, dsa.data_ptr(), dsb.data_ptr(), ua.ctypes.data,
+                                       ub.ctypes.data, nvec, cp, op, self._ws.data_ptr(), grant, self._stream()),
+              "evc_fci_rotate_block")
+        return outs, na, nb
+
+    def cas_trans_rdm12_block(self, bras, kets, layout=None, out_rows: Optional[torch.Tensor] = None):
+        """``cas_trans_rdm12_rows`` for several bras that share their orbitals (the roots of one geometry; the statement
+        is ``cas_small.trans_rdm12_block``), with a leading bra axis: ``(ovlp (R,K), dm1 (R,K,N,N), dm2 (R,K,N,N,N,N))``
+        without a layout; with one, ``out_rows`` is a contiguous ``(R K, ld)`` float64 device tensor, bra-major, and
+        ``(ovlp, dm1)`` is returned.  Row ``(r, k)`` has the bits of ``cas_trans_rdm12_rows(bras[r], kets)`` row ``k``.
+
+        The pair intermediates depend on the two orbital sets alone: they are formed once per group of consecutive kets
+        that share a ``U``, the group's kets are rotated by one ``evc_fci_rotate_block`` call and scaled by ``fac`` on the
+        device, and ``A_a / B_a / Qc`` are uploaded once for all bras.  Per bra: one ``evc_fci_trdm_rows`` call against
+        all rotated kets and one ``evc_cas_expand_rows`` call.  A pair beyond the conditioning guard raises ``ValueError``
+        before anything is launched."""
+        from . import cas_small
+        bras, kets = list(bras), list(kets)
+        if not bras or not kets:
+            raise EvcontHipError("DeviceFCI.cas_trans_rdm12_block: no bras or no kets")
+        cas_small.check_block("DeviceFCI.cas_trans_rdm12_block", bras, kets)
+        bra0 = bras[0]
+        R, K, n, ncas, nelec = len(bras), len(kets), int(bra0.U.shape[0]), int(bra0.ncas), _nelec(bra0.nelecas)
+        lay = {None: _lib.LAYOUT_FULL6, "pack2": _lib.LAYOUT_PACK2, "sym8": _lib.LAYOUT_SYM8}.get(layout, layout)
+        if lay not in (_lib.LAYOUT_FULL6, _lib.LAYOUT_PACK2, _lib.LAYOUT_SYM8):
+            raise EvcontHipError(f"DeviceFCI.cas_trans_rdm12_block: layout={layout!r}, expected None, 'pack2' or 'sym8'")
+        groups = cas_small.ket_groups(kets)
+        for ket in kets:
+            cas_small._same_shape(bra0, ket)
+        inter = [cas_small.pair_intermediates(bra0, kets[first], f"(bras, ket {first})") for first, _ in groups]
+        lib, dta, dtb, na, nb, grant = self._setup(ncas, nelec)
+        dev = self._dev()
+        if lay != _lib.LAYOUT_FULL6:
+            rows_all = out_rows
+            on_dev = (torch.is_tensor(rows_all) and rows_all.device.type == dev.type
+                      and dev.index in (None, rows_all.device.index))
+            if not (on_dev and rows_all.dtype == F64 and rows_all.dim() == 2 and rows_all.shape[0] == R * K
+                    and rows_all.stride(1) == 1 and (R * K == 1 or rows_all.stride(0) == rows_all.shape[1])):
+                raise EvcontHipError(f"DeviceFCI.cas_trans_rdm12_block: out_rows must be a contiguous ({R * K}, ld) float64 "
+                                     f"tensor on {dev}")
+        else:
+            # (one tensor per bra: evc_cas_expand_rows wants 16-byte aligned rows, which n^4 doubles do not keep)
+            rows_all = [torch.empty((K, n ** 4), dtype=F64, device=dev) for _ in bras]
+        dkets = []
+        for (first, count), (fac, s_eff, _, _, _) in zip(groups, inter):
+            rotated, _, _ = self._rotate_block([k.ci for k in kets[first:first + count]], nelec,
+                                               np.ascontiguousarray(s_eff.T))
+            dkets.extend(t.mul_(fac) for t in rotated)
+        lib, dta, dtb, na, nb, grant = self._setup(ncas, nelec)      # (the rotation may have replaced the workspace)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        per_ket = [x for (_, count), x in zip(groups, inter) for _ in range(count)]
+        A_act = up(np.stack([x[2] for x in per_ket]))                  # (K, n, ncas), the same for every bra
+        B_act = up(np.stack([x[3] for x in per_ket]))
+        Qc = up(np.stack([x[4] for x in per_ket])) if bra0.ncore else None
+        need = lib.evc_cas_expand_workspace_bytes(n, ncas, K)
+        if need == 0:
+            check(-1, "evc_cas_expand_workspace_bytes")
+        if self._cas_ws is None or self._cas_ws.numel() < need:
+            self._cas_ws = None
+            self._cas_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ovlp = [torch.empty(K, dtype=F64, device=dev) for _ in bras]
+        d1 = torch.empty((K, ncas, ncas), dtype=F64, device=dev)
+        d2 = torch.empty((K, ncas ** 4), dtype=F64, device=dev)
+        dm1 = [torch.empty((K, n, n), dtype=F64, device=dev) for _ in bras]
+        ptrs = (C.c_void_p * K)(*[t.data_ptr() for t in dkets])
+        for r, bra in enumerate(bras):
+            rows = rows_all[r] if lay == _lib.LAYOUT_FULL6 else rows_all[r * K:(r + 1) * K]
+            dbra = self._upload(bra.ci, na, nb, cache=False)
+            check(lib.evc_fci_trdm_rows(ncas, na, nb, dta.data_ptr(), dtb.data_ptr(), dbra.data_ptr(), ptrs, K,
+                                        ovlp[r].data_ptr(), d1.data_ptr(), d2.data_ptr(), self._ws.data_ptr(), grant,
+                                        self._stream()), "evc_fci_trdm_rows")
+            check(lib.evc_cas_expand_rows(n, ncas, K, A_act.data_ptr(), B_act.data_ptr(),
+                                          None if Qc is None else Qc.data_ptr(), ovlp[r].data_ptr(), d1.data_ptr(),
+                                          d2.data_ptr(), dm1[r].data_ptr(), lay, rows.data_ptr(), int(rows.shape[1]),
+                                          self._cas_ws.data_ptr(), need, self._stream()), "evc_cas_expand_rows")
+        # (each bra's results straight into their place on the host: no stacked copy on the device)
+        h_ovlp, h_dm1 = np.empty((R, K)), np.empty((R, K, n, n))
+        for r in range(R):
+            torch.from_numpy(h_ovlp[r]).copy_(ovlp[r])
+            torch.from_numpy(h_dm1[r]).copy_(dm1[r])
+        if lay != _lib.LAYOUT_FULL6:
+            return h_ovlp, h_dm1
+        h_dm2 = np.empty((R, K, n ** 4))
+        for r in range(R):
+            torch.from_numpy(h_dm2[r]).copy_(rows_all[r])
+        return h_ovlp, h_dm1, h_dm2.reshape(R, K, n, n, n, n)
 
     def cas_trans_rdm12_rows(self, bra, kets, layout=None, out_rows: Optional[torch.Tensor] = None):
         """Overlaps and transition RDMs, in the OAO basis, of one CAS state against ``kets`` whose orbitals differ from

@@ -51,7 +51,8 @@ extern "C" {
                                  evc_properties_roots_batch, evc_properties_workspace_bytes, evc_sgto_dipole_batch;
                                  additive: evc_spgto_workspace_bytes, evc_spgto_integrals_batch,
                                  evc_spgto_dipole_batch; additive: evc_spdgto_workspace_bytes,
-                                 evc_spdgto_integrals_batch, evc_spdgto_dipole_batch */
+                                 evc_spdgto_integrals_batch, evc_spdgto_dipole_batch; additive:
+                                 evc_fci_rotate_block, evc_fci_rotate_block_workspace_bytes */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -584,6 +585,20 @@ size_t evc_fci_rotate_workspace_bytes(int norb, int nocc_a, int nocc_b, int64_t 
 int evc_fci_rotate(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, const int32_t *strs_a,
                    const int32_t *strs_b, const double *u_a, const double *u_b, const double *c, double *out, void *ws,
                    size_t ws_bytes, void *stream);
+/* evc_fci_rotate_block: nvec >= 1 vectors under one (u_a, u_b): out[v] = T_a^T . c[v] . T_b.  `c` and `out` are HOST
+ *       arrays of nvec DEVICE pointers (the form evc_fci_trdm_rows takes its kets); no output may be an input or another
+ *       output (refused).  Every panel of T_b and of T_a is formed once per call and applied to all vectors, 16 of them
+ *       per product launch; the workspace holds one intermediate per vector.  Vector v has the bits evc_fci_rotate gives
+ *       on c[v], for every accepted workspace and from run to run.  Refusals (nvec < 1, a null pointer, aliasing, a short
+ *       workspace, the shape) come before any launch.  The record of EVC_PROF_FCI_ROTATE is that of evc_fci_rotate
+ *       followed by " vecs=<nvec>".
+ * evc_fci_rotate_block_workspace_bytes(..., nvec, minimal): as evc_fci_rotate_workspace_bytes with nvec intermediates;
+ *       0 on an argument error. */
+size_t evc_fci_rotate_block_workspace_bytes(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, int nvec,
+                                            int minimal);
+int evc_fci_rotate_block(int norb, int nocc_a, int nocc_b, int64_t na, int64_t nb, const int32_t *strs_a,
+                         const int32_t *strs_b, const double *u_a, const double *u_b, int nvec, const double *const *c,
+                         double *const *out, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * AO integrals of s-Gaussian molecules on the device (csrc/sgto.hip; the host statement is evcont_amd/hchain.py
@@ -767,7 +782,8 @@ int evc_properties_roots_batch(const evc_trdm_set *t, const evc_property_inputs 
                                      "fci_spin_apply_kernel beta=1 tiles=870", "fci_spin_diag_kernel" (not cleared by
                                      the other evc_fci_* entry points) */
 #define EVC_PROF_FCI_ROTATE 12    /* evc_fci_rotate: the minor kernel of each spin, whether it took the complementary
-                                     minors, the panels of each T, and the product kernel */
+                                     minors, the panels of each T, and the product kernel; evc_fci_rotate_block: the
+                                     same followed by " vecs=<nvec>" */
 #define EVC_PROF_FCI_PACK 13      /* evc_fci_trdm_rows_packed: the packing kernel, e.g.
                                      "fci_row_pack_kernel<8> rows=3 cols=231 ld=240" (<1>: PACK2, <8>: SYM8) */
 int evc_profile_begin(int max_samples);
