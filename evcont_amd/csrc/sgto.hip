@@ -27,9 +27,8 @@
 //   sgto_nuc_kernel    nuclear repulsion and its gradient, one thread per centre.
 // The contraction is a HOST argument and reaches the pair kernel by value.  fp contraction is off in the kernels and every
 // fused multiply-add is written out: the two instantiations of sgto_two_kernel must round int2e alike.
-#include <math.h>
-
-#include "common.hpp"
+// Of gto_shells.hpp, the core of the shell routes, this file takes the launch helper gto_launch and the flags kGtoFlags.
+#include "gto_shells.hpp"
 
 namespace evc {
 
@@ -39,25 +38,11 @@ constexpr int kSgtoMaxPrim = 8;          // primitives of the contraction
 constexpr int kSgtoMaxCount = 65535;     // geometries per call (gridDim.z)
 constexpr int kSgtoKet = 5;            // fields of the ket part of the pair table
 constexpr int kSgtoBra = 12;           // doubles of a row of its bra part
-constexpr int kSgtoFlags = EVC_FLAG_ENERGY_ONLY | EVC_FLAG_ERI_S4 | EVC_FLAG_IP1_S2KL;
 
 struct SgtoBasis {
     double ex[kSgtoMaxPrim];   // exponents
     double cn[kSgtoMaxPrim];   // coefficient x norm of the primitive
 };
-
-// Every launch of this file: the runtime call, not the chevrons (tests/test_sgto_closure.py).
-template <typename T>
-struct sgto_same_type {
-    using type = T;
-};
-template <typename... P>
-static void sgto_launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t st,
-                        typename sgto_same_type<P>::type... a) {
-    void *args[] = {(void *)&a...};
-    // the result is read by the EVC_LAUNCH_CHECK (hipGetLastError) that follows the call
-    (void)hipLaunchKernel(reinterpret_cast<const void *>(kernel), grid, block, args, 0, st);
-}
 
 // doubles of the pair table of one geometry: the ket part, then the bra part
 __host__ __device__ __forceinline__ int64_t sgto_ket_doubles(int N, int K) {
@@ -368,7 +353,7 @@ extern "C" int evc_sgto_integrals_batch(int natm, int nprim, int count, const do
                                         int flags, void *ws, size_t ws_bytes, void *stream) {
     const char *who = "evc_sgto_integrals_batch";
     if (int rc = sgto_shape(who, natm, nprim, count)) return rc;
-    EVC_REQUIRE((flags & ~kSgtoFlags) == 0, "%s: flags=%d, accepted EVC_FLAG_ENERGY_ONLY, EVC_FLAG_ERI_S4 and "
+    EVC_REQUIRE((flags & ~kGtoFlags) == 0, "%s: flags=%d, accepted EVC_FLAG_ENERGY_ONLY, EVC_FLAG_ERI_S4 and "
                 "EVC_FLAG_IP1_S2KL", who, flags);
     const bool grad = !(flags & EVC_FLAG_ENERGY_ONLY);
     const int s4 = (flags & EVC_FLAG_ERI_S4) != 0, s2kl = (flags & EVC_FLAG_IP1_S2KL) != 0;
@@ -396,27 +381,27 @@ extern "C" int evc_sgto_integrals_batch(int natm, int nprim, int count, const do
     hipStream_t st = as_stream(stream);
     const int N = natm, K = nprim, Ms = N * (N + 1) / 2;
     double *tab = static_cast<double *>(ws);
-    sgto_launch(sgto_pair_kernel, dim3((unsigned)ceil_div((int64_t)K * K * N * N, 256), (unsigned)count), dim3(256), st, bs,
-                coords, N, K, tab);
+    gto_launch(sgto_pair_kernel, dim3((unsigned)ceil_div((int64_t)K * K * N * N, 256), (unsigned)count), dim3(256), st, bs,
+               coords, N, K, tab);
     EVC_LAUNCH_CHECK("sgto_pair_kernel");
     const dim3 grid1((unsigned)Ms, (unsigned)count), grid2((unsigned)ceil_div(Ms, 64), (unsigned)(grad ? N * N : Ms),
                                                            (unsigned)count);
     if (grad) {
-        sgto_launch(sgto_one_kernel<true>, grid1, dim3(64), st, (const double *)tab, coords, charges, N, K, out->S,
-                    out->hcore, out->ipovlp, out->dhcore);
+        gto_launch(sgto_one_kernel<true>, grid1, dim3(64), st, (const double *)tab, coords, charges, N, K, out->S,
+                   out->hcore, out->ipovlp, out->dhcore);
         EVC_LAUNCH_CHECK("sgto_one_kernel");
-        sgto_launch(sgto_nuc_kernel<true>, dim3((unsigned)count), dim3(128), st, coords, charges, N, out->enuc, out->gnuc);
+        gto_launch(sgto_nuc_kernel<true>, dim3((unsigned)count), dim3(128), st, coords, charges, N, out->enuc, out->gnuc);
         EVC_LAUNCH_CHECK("sgto_nuc_kernel");
-        sgto_launch(sgto_two_kernel<true>, grid2, dim3(64), st, (const double *)tab, N, K, s4, s2kl, out->eri, out->eri_ip1);
+        gto_launch(sgto_two_kernel<true>, grid2, dim3(64), st, (const double *)tab, N, K, s4, s2kl, out->eri, out->eri_ip1);
     } else {
-        sgto_launch(sgto_one_kernel<false>, grid1, dim3(64), st, (const double *)tab, coords, charges, N, K, out->S,
-                    out->hcore, (double *)nullptr, (double *)nullptr);
+        gto_launch(sgto_one_kernel<false>, grid1, dim3(64), st, (const double *)tab, coords, charges, N, K, out->S,
+                   out->hcore, (double *)nullptr, (double *)nullptr);
         EVC_LAUNCH_CHECK("sgto_one_kernel");
-        sgto_launch(sgto_nuc_kernel<false>, dim3((unsigned)count), dim3(128), st, coords, charges, N, out->enuc,
-                    (double *)nullptr);
+        gto_launch(sgto_nuc_kernel<false>, dim3((unsigned)count), dim3(128), st, coords, charges, N, out->enuc,
+                   (double *)nullptr);
         EVC_LAUNCH_CHECK("sgto_nuc_kernel");
-        sgto_launch(sgto_two_kernel<false>, grid2, dim3(64), st, (const double *)tab, N, K, s4, 0, out->eri,
-                    (double *)nullptr);
+        gto_launch(sgto_two_kernel<false>, grid2, dim3(64), st, (const double *)tab, N, K, s4, 0, out->eri,
+                   (double *)nullptr);
     }
     EVC_LAUNCH_CHECK("sgto_two_kernel");
     return 0;

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .evaluator import DeviceAOBatch, F64, _dev
-from .gto_small import contraction_coefficients
+from .gto_small import contraction_coefficients, flatten_shells
 
 _FIELDS = ("enuc", "S", "hcore", "eri", "ipovlp", "dhcore", "eri_ip1", "gnuc")
 
@@ -43,27 +43,11 @@ class DeviceGaussians:
             raise ValueError(f"{len(self.shells)} shell lists for {self._charges_host.shape[0]} charges")
         self.nelec = None if nelec is None else tuple(nelec)
         self.renormalize = bool(renormalize)
-        coef = self._coefficients(self.shells, renormalize)
-        atom, l, off, ex, co, slices, n = [], [], [0], [], [], [], 0
-        for at, (shs, cs) in enumerate(zip(self.shells, coef)):
-            start = n
-            for sh, c in zip(shs, cs):
-                atom.append(at)
-                l.append(sh.l)
-                off.append(off[-1] + len(sh.exponents))
-                ex += list(sh.exponents)
-                co += list(c)
-                n += 2 * sh.l + 1
-            slices.append((start, n))
         # the HOST description of the basis every call passes
-        self.shell_atom = np.array(atom, dtype=np.int32)
-        self.shell_l = np.array(l, dtype=np.int32)
-        self.shell_prim_offset = np.array(off, dtype=np.int32)
-        self.exponents = np.array(ex, dtype=np.float64)
-        self.coefficients = np.array(co, dtype=np.float64)
-        self.nao = n
+        (self.shell_atom, self.shell_l, self.shell_prim_offset, self.exponents, self.coefficients, slices,
+         self.nao) = flatten_shells(self.shells, self._coefficients(self.shells, renormalize))
         self._charges = torch.from_numpy(self._charges_host).to(self.device)
-        self._aoslices = torch.from_numpy(np.array(slices, dtype=np.int64).reshape(-1, 2)).to(self.device)
+        self._aoslices = torch.from_numpy(slices).to(self.device)
         self._buffers = {}         # (G, need_grad, packed) -> dict of output tensors
         self._coords = {}          # G -> device (G,A,3) staging of host coordinates
         self._dip = {}             # G -> device (G,3,N,N) dipole integrals

@@ -106,6 +106,25 @@ def contraction_coefficients(shells, renormalize: bool = True):
              for sh in atom] for atom in shells]
 
 
+def flatten_shells(shells, coef):
+    """The basis as the device calls take it, from per-atom shell lists and their ``contraction_coefficients``:
+    (shell_atom, shell_l, shell_prim_offset, exponents, coefficients, aoslices (A,2), nao)."""
+    atom, l, off, ex, co, slices, n = [], [], [0], [], [], [], 0
+    for at, (shs, cs) in enumerate(zip(shells, coef)):
+        start = n
+        for sh, c in zip(shs, cs):
+            atom.append(at)
+            l.append(sh.l)
+            off.append(off[-1] + len(sh.exponents))
+            ex += list(sh.exponents)
+            co += list(c)
+            n += 2 * sh.l + 1
+        slices.append((start, n))
+    return (np.array(atom, dtype=np.int32), np.array(l, dtype=np.int32), np.array(off, dtype=np.int32),
+            np.array(ex, dtype=np.float64), np.array(co, dtype=np.float64),
+            np.array(slices, dtype=np.int64).reshape(-1, 2), n)
+
+
 def boys(nmax: int, t) -> np.ndarray:
     """F_0 ... F_nmax of ``t`` (>= 0), shape (nmax+1,) + t.shape."""
     t = np.asarray(t, dtype=np.float64)

@@ -1,8 +1,10 @@
 """Host-side closure for csrc/sgto.hip (device AO integrals of s-Gaussian molecules), modelled on
 tests/test_fci_pack_closure.py: the two calls are declared in the header, bound in ``_lib`` and exported, the file is
-built, every kernel it defines is launched through ``sgto_launch`` and through nothing else, and the call adds neither
-a profile stage nor an ABI version."""
+built, every kernel it defines is launched through ``gto_launch`` of csrc/gto_shells.hpp, the one place of the shell
+routes that calls the runtime, and through nothing else, the call adds neither a profile stage nor an ABI version, and
+every local header a source includes is a dependency of the build."""
 import ctypes as C
+import glob
 import os
 import re
 
@@ -28,17 +30,24 @@ def test_calls_are_declared_bound_and_built():
     assert re.findall(r"double \*(\w+);", fields) == [f[0] for f in _lib.SgtoOutputs._fields_]
     assert C.sizeof(_lib.SgtoOutputs) == 8 * 8
     assert "sgto.hip" in build.SOURCES
+    # an edit to a header rebuilds what includes it: every local header named in csrc is in build.HEADERS
+    known = {os.path.normpath(os.path.join(CSRC, h)) for h in build.HEADERS}
+    for path in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")):
+        with open(path) as f:
+            for inc in re.findall(r'(?m)^\s*#\s*include\s+"([^"]+)"', f.read()):
+                assert os.path.normpath(os.path.join(CSRC, inc)) in known, (os.path.basename(path), inc)
 
 
-def test_every_kernel_is_launched_through_sgto_launch():
-    src = source()
+def test_every_kernel_is_launched_through_gto_launch():
+    src, core = source(), source("gto_shells.hpp")
     defined = set(re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", src))
-    launched = set(re.findall(r"\bsgto_launch\(\s*(\w+)\s*[<,]", src))
+    launched = set(re.findall(r"\bgto_launch\(\s*(\w+)\s*[<,]", src))
     assert defined == launched == {"sgto_pair_kernel", "sgto_one_kernel", "sgto_nuc_kernel", "sgto_two_kernel"}, \
         sorted(defined ^ launched)
-    assert "<<<" not in src and "hipLaunchKernelGGL" not in src
-    assert len(re.findall(r"\bhipLaunchKernel\(", src)) == 1
-    helper = src[src.index("static void sgto_launch("):]
+    assert "<<<" not in src and "hipLaunchKernelGGL" not in src and "hipLaunchKernel(" not in src
+    assert "<<<" not in core and "hipLaunchKernelGGL" not in core
+    assert len(re.findall(r"\bhipLaunchKernel\(", core)) == 1
+    helper = core[core.index("static void gto_launch("):]
     assert "hipLaunchKernel(" in helper[:helper.index("\n}\n")]
     assert "atomic" not in src.lower()
 

@@ -1,6 +1,7 @@
 """Host-side closure for csrc/spgto.hip (device AO integrals of s and p Gaussian shells), modelled on
 tests/test_sgto_closure.py: the calls are declared in the header, bound in ``_lib`` and exported, the file is built,
-every kernel it defines is launched through ``spgto_launch`` and through nothing else, the calls add neither a profile
+every kernel it defines is launched through ``gto_launch`` of csrc/gto_shells.hpp (by the shared host templates, from
+the kernel list of the route description ``SpRoute``) and through nothing else, the calls add neither a profile
 stage nor an ABI version, sgto.hip keeps its four kernels, and every refusal happens on the host."""
 import ctypes as C
 import os
@@ -35,14 +36,20 @@ def test_calls_are_declared_bound_and_built():
     assert "spgto.hip" in build.SOURCES and "sgto.hip" in build.SOURCES
 
 
-def test_every_kernel_is_launched_through_spgto_launch():
-    src = source()
+def test_every_kernel_is_launched_through_gto_launch():
+    src, core = source(), source("gto_shells.hpp")
     defined = set(re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", src))
-    launched = set(re.findall(r"\bspgto_launch\(\s*(\w+)\s*[<,]", src))
+    # the launches are in the host templates of the shared header, which take their kernels from the route description
+    route = src[src.index("struct SpRoute {"):]
+    listed = dict(re.findall(r"\b(k\w+) = (\w+_kernel)\b", route[:route.index("\n};\n")]))
+    passed = [re.findall(r"\bR::(k\w+)", first) for first in re.findall(r"(?<!void )\bgto_launch\(([^,]*),", core)]
+    assert all(passed) and {m for ms in passed for m in ms} == set(listed), (passed, listed)
+    launched = set(listed.values())
     assert defined == launched == KERNELS, sorted(defined ^ launched)
-    assert "<<<" not in src and "hipLaunchKernelGGL" not in src
-    assert len(re.findall(r"\bhipLaunchKernel\(", src)) == 1
-    helper = src[src.index("static void spgto_launch("):]
+    assert "<<<" not in src and "hipLaunchKernelGGL" not in src and "hipLaunchKernel(" not in src
+    assert "<<<" not in core and "hipLaunchKernelGGL" not in core
+    assert len(re.findall(r"\bhipLaunchKernel\(", core)) == 1
+    helper = core[core.index("static void gto_launch("):]
     assert "hipLaunchKernel(" in helper[:helper.index("\n}\n")]
     assert "atomic" not in src.lower()
 
