@@ -325,7 +325,7 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
                  data_addition=data_addition, **kwargs)
 
 
-def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=()):
+def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=(), device_trdms=None):
     """``evaluate(R (G,A,3)) -> (E (G,nroots), grads (G,nroots,A,3))`` for geometries of the s-Gaussian molecule of
     ``mols``, device-resident from the coordinates on: the training set and the batched evaluator are built once, every
     call uploads the coordinates, computes the AO integrals there (``hchain_device.DeviceSGaussians``, or
@@ -349,8 +349,9 @@ def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=()):
         raise ValueError('integrals="device" needs s-Gaussian molecules (evcont_amd.hchain.HChainMol)')
     if G * nroots > 4096:
         raise ValueError(f"{G} trajectories x {nroots} roots exceed the 4096 slots of one call")
-    t = _resident_trdms(one_rdm, two_rdm, overlap,
-                        resolve_compression("default", one_rdm, two_rdm, overlap, ao_arrays(mol0, need_grad=True)))
+    t = device_trdms if device_trdms is not None else _resident_trdms(
+        one_rdm, two_rdm, overlap,
+        resolve_compression("default", one_rdm, two_rdm, overlap, ao_arrays(mol0, need_grad=True)))
     natm = int(np.asarray(mol0.charges).shape[0])
     ev = _batched_evaluator(t, natm, G)
     sg = producer.from_mol(mol0, device=t.device)
@@ -377,7 +378,7 @@ _OBSERVABLES = {"dipole": "dipole", "mulliken": "mulliken_charges", "loewdin": "
 
 
 def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_veloc=None, integrals="host",
-                observables=None):
+                observables=None, device_trdms=None):
     """Velocity-Verlet NVE of G trajectories on the continuation surface ``root`` (0 = ground state), advanced in lock
     step: every step is ONE batched call for all G geometries (``get_multistate_energies_with_grads``, all trajectories'
     roots 0 .. root in one pass).  ``mols``: the G initial geometries of one array-level molecule that can be rebuilt at
@@ -393,7 +394,9 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
     gains ``dipole`` (G,3) (atomic units, origin (0,0,0)) and ``mulliken_charges`` / ``loewdin_charges`` (G,A) of the
     propagated root (plain Mulliken, not meta-Loewdin), from the solve that gives the forces; with
     ``integrals="device"`` that adds the observables' G (3 + A) doubles per kind of charge to the step's download and
-    no upload."""
+    no upload.
+    ``device_trdms``: as for ``get_scanner`` (training data already on the device, e.g. a resident container's
+    ``device_trdms()``; the host arrays may then be ``None``)."""
     from .ab_initio_gradients_loewdin import get_multistate_energies_with_grads
     mols = list(mols)
     root = int(root)
@@ -412,7 +415,7 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
     observed = lambda props: {_OBSERVABLES[k]: props[_OBSERVABLES[k]][:, 0] for k in observables}
 
     if integrals == "device":
-        surfaces = _device_surfaces(mols, one_rdm, two_rdm, overlap, root + 1, observables)
+        surfaces = _device_surfaces(mols, one_rdm, two_rdm, overlap, root + 1, observables, device_trdms)
 
         def evaluate(ms):
             if observables:
@@ -427,9 +430,10 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
             if observables:
                 from .ab_initio_eigenvector_continuation import get_multistate_properties
                 E, props = get_multistate_properties(ms, one_rdm, two_rdm, overlap, root + 1, [(root, root)],
-                                                     return_forces=True)
+                                                     return_forces=True, device_trdms=device_trdms)
                 return E[:, root], props["grads"][:, 0], observed(props)
-            E, grads = get_multistate_energies_with_grads(ms, one_rdm, two_rdm, overlap, root + 1)
+            E, grads = get_multistate_energies_with_grads(ms, one_rdm, two_rdm, overlap, root + 1,
+                                                          device_trdms=device_trdms)
             return E[:, root], grads[:, root], {}
 
         rebuild = lambda ms, R: [m_.with_coords(r) for m_, r in zip(ms, R)]

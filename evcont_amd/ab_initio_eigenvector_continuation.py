@@ -253,7 +253,7 @@ def _dipole_inputs(mol, origin):
 
 
 def get_multistate_properties(mols, one_rdm, two_rdm, overlap, nroots=1, pairs=None, origin=None, hermitian=True,
-                              return_forces=False):
+                              return_forces=False, device_trdms=None):
     """Dipole moments, transition dipole moments and atomic charges of the lowest ``nroots`` continuation states at
     every geometry of ``mols`` (geometries of ONE molecule), on the device in batches
     (``BatchedEvaluator.multistate_properties``): what the reference computes per geometry on the host at the end of
@@ -264,6 +264,7 @@ def get_multistate_properties(mols, one_rdm, two_rdm, overlap, nroots=1, pairs=N
     it).  Returns ``E (G,nroots)`` and a dict of ``dipole (G,P,3)`` in atomic units (diagonal slots: total dipole;
     slot (k,l): the electronic transition dipole), ``mulliken_charges`` and ``loewdin_charges (G,P,A)``, ``C
     (G,nroots,T)``; with ``return_forces`` also ``grads (G,P,A,3)`` of the same slots from the same solve.
+    ``device_trdms``: training data already on the device (``get_scanner``'s keyword), used instead of the host arrays.
 
     The populations are PLAIN Mulliken (PySCF's ``mulliken_pop``) and Loewdin; the reference script's
     ``mulliken_meta`` (meta-Loewdin, orthogonalised against PySCF's tabulated atomic reference orbitals) is not
@@ -284,10 +285,10 @@ def get_multistate_properties(mols, one_rdm, two_rdm, overlap, nroots=1, pairs=N
     natm = int(np.asarray(aos[0].aoslices).shape[0])
     if any(int(np.asarray(a.aoslices).shape[0]) != natm or a.S.shape != aos[0].S.shape for a in aos):
         raise ValueError("get_multistate_properties: the geometries must be of one molecule")
-    t = _resident_trdms(one_rdm, two_rdm, overlap,
-                        resolve_compression("default", one_rdm, two_rdm, overlap,
-                                            mols[0] if not is_array_mol(mols[0]) else aos[0], hermitian=hermitian,
-                                            need_grad=need_grad))
+    t = device_trdms if device_trdms is not None else _resident_trdms(
+        one_rdm, two_rdm, overlap, resolve_compression("default", one_rdm, two_rdm, overlap,
+                                                       mols[0] if not is_array_mol(mols[0]) else aos[0],
+                                                       hermitian=hermitian, need_grad=need_grad))
     if pairs is None:
         pairs = [(k, k) for k in range(nroots)]
     pairs = [tuple(int(x) for x in p) for p in np.asarray(pairs).reshape(-1, 2)]

@@ -108,8 +108,20 @@ def get_energy_with_grad(mol, one_RDM, two_RDM, S, hermitian=True, return_densit
     return ev.energy_with_grad(dao, return_density_matrices=return_density_matrices)
 
 
+def _evaluator_of(t, natm: int):
+    """The single-geometry evaluator on training data already on the device (``device_trdms=``), cached like the
+    others."""
+    from . import cache
+    from .evaluator import ContinuationEvaluator
+    key = ("evaluator", id(t), int(natm))
+    ev = cache.get(key)
+    if ev is None or ev.t is not t:
+        ev = cache.put(key, ContinuationEvaluator(t, natm))
+    return ev
+
+
 def get_multistate_energy_with_grad(mol, one_RDM, two_RDM, S, nroots=1, hermitian=True, return_couplings=False,
-                                    return_density_matrices=False):
+                                    return_density_matrices=False, device_trdms=None):
     """Total energies ``E[nroots]`` and nuclear gradients ``grad[nroots,A,3]`` of the lowest ``nroots`` continuation
     states at ``mol``'s geometry: ``get_energy_with_grad`` with the eigenvector c_k of root k in place of c_0
     (S_train does not depend on the geometry, so dE_k/dR = c_k^T dH/dR c_k), all roots in one device pass.
@@ -118,14 +130,20 @@ def get_multistate_energy_with_grad(mol, one_RDM, two_RDM, S, nroots=1, hermitia
     k, l; the diagonal is the electronic gradient of root k; the derivative coupling is h_kl / (E_l - E_k)).
     ``return_density_matrices``: also the predicted RDMs of every root, ``D[nroots,N,N]`` and ``G[nroots,N,N,N,N]``,
     as ``get_energy_with_grad`` returns them.  Storage of the resident training data as for ``get_energy_with_grad``.
+    ``device_trdms``: training data already on the device (``get_scanner``'s keyword, e.g. a resident container's
+    ``device_trdms()``), used instead of the host arrays, which may then be ``None``.
     At (near-)degenerate roots the forces follow whichever eigenvectors the solver returned."""
     nroots = int(nroots)
     ao = ao_arrays(mol, need_grad=True)
     natm = int(np.asarray(ao.aoslices).shape[0])
-    ev = _evaluator(one_RDM, two_RDM, S, natm,
-                    compress=resolve_compression("default", one_RDM, two_RDM, S, mol if not is_array_mol(mol) else ao,
-                                                 hermitian=hermitian, want_rdms=return_density_matrices),
-                    auto=get_trdm_compression() == "auto")
+    if device_trdms is not None:
+        ev = _evaluator_of(device_trdms, natm)
+    else:
+        ev = _evaluator(one_RDM, two_RDM, S, natm,
+                        compress=resolve_compression("default", one_RDM, two_RDM, S,
+                                                     mol if not is_array_mol(mol) else ao, hermitian=hermitian,
+                                                     want_rdms=return_density_matrices),
+                        auto=get_trdm_compression() == "auto")
     pairs = _root_pairs(nroots, return_couplings)
     res = ev.energies_with_grads(DeviceAO.from_arrays(ao, ev.t.device), nroots, pairs,
                                  return_density_matrices=return_density_matrices, hermitian=hermitian)
@@ -172,14 +190,16 @@ def _batched_evaluator(t, natm: int, count: int):
     return ev
 
 
-def get_multistate_energies_with_grads(mols, one_RDM, two_RDM, S, nroots=1, hermitian=True, return_couplings=False):
+def get_multistate_energies_with_grads(mols, one_RDM, two_RDM, S, nroots=1, hermitian=True, return_couplings=False,
+                                       device_trdms=None):
     """``get_multistate_energy_with_grad`` for a list of geometries of ONE molecule, evaluated in batches (every
     geometry of a batch and all its roots in one pass of the gradient chain, ``evc_phase_gradient_roots_batch``).
 
     Returns stacked arrays ``E[G,nroots]`` and ``grad[G,nroots,A,3]``, with ``return_couplings`` also
     ``h[G,nroots,nroots,A,3]`` (symmetric in k, l; the diagonal is the electronic gradient of root k), with the storage
     of the training data and the coupling conventions of ``get_multistate_energy_with_grad``.  The list is split so
-    that a batch holds at most 4096 (geometry, root pair) slots and ``BATCH_WORKSPACE_BUDGET`` bytes of workspace."""
+    that a batch holds at most 4096 (geometry, root pair) slots and ``BATCH_WORKSPACE_BUDGET`` bytes of workspace.
+    ``device_trdms``: as for ``get_multistate_energy_with_grad``."""
     import ctypes as C
     from . import _lib
     from .ab_initio_eigenvector_continuation import _resident_trdms
@@ -192,9 +212,9 @@ def get_multistate_energies_with_grads(mols, one_RDM, two_RDM, S, nroots=1, herm
     natm = int(np.asarray(aos[0].aoslices).shape[0])
     if any(int(np.asarray(a.aoslices).shape[0]) != natm or a.S.shape != aos[0].S.shape for a in aos):
         raise ValueError("get_multistate_energies_with_grads: the geometries must be of one molecule")
-    t = _resident_trdms(one_RDM, two_RDM, S,
-                        resolve_compression("default", one_RDM, two_RDM, S,
-                                            mols[0] if not is_array_mol(mols[0]) else aos[0], hermitian=hermitian))
+    t = device_trdms if device_trdms is not None else _resident_trdms(
+        one_RDM, two_RDM, S, resolve_compression("default", one_RDM, two_RDM, S,
+                                                 mols[0] if not is_array_mol(mols[0]) else aos[0], hermitian=hermitian))
     pairs = _root_pairs(nroots, return_couplings)
     npairs = len(pairs)
     lib = _lib.load()

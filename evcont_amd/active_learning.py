@@ -185,10 +185,14 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
     """
     from .MD_utils import get_trajectory
     from .ab_initio_eigenvector_continuation import get_trdm_compression, integrals_have_symmetry
-    from .resident import ResidentFCI_EVCont_obj
     # a resident container has its two-body rows on the device alone: trajectories and the subset energies read its
     # view, the checkpoint gets the packed rows ((P, M) as two_rdm.npy for pack2, (P, cols8) as two_rdm_sym8.npy)
-    resident = isinstance(EVCont_obj, ResidentFCI_EVCont_obj)
+    # (resident.ResidentFCI_EVCont_obj and resident.ResidentCAS_EVCont_obj say so themselves)
+    resident = bool(getattr(EVCont_obj, "resident_rows", False))
+    if resident and getattr(EVCont_obj, "single_root_loop_only", False) and EVCont_obj.roots_train != [0]:
+        raise NotImplementedError("converge_EVCont_MD: a resident CAS container with several roots per geometry "
+                                  f"(roots_train={EVCont_obj.roots_train}) is not supported: the loop adds one state per "
+                                  "trajectory point (use roots_train=[0])")
     if trn_times:
         raise NotImplementedError("converge_EVCont_MD: restart from a previous run (trn_times) is not supported")
     if not hasattr(init_mol, "with_coords"):

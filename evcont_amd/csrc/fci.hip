@@ -5,7 +5,8 @@
 //               sigma = sum_pq E_pq (G[pq]/2 + h'_pq c)       G back through the tables
 //   rows        evc_fci_trdm_rows: the dense t-RDMs of one bra against K kets; evc_fci_trdm_rows_packed: the same product
 //               (one function, fci_trdm_rows_run) with each ket's two-body block packed on the device into a row of the
-//               evaluator's matrix (fci_pack.hip)
+//               evaluator's matrix (fci_pack.hip); evc_fci_trdm_rows_block: up to kTrdmBras bras against shared kets, the
+//               ket-side D of a determinant chunk formed once for every bra that sees the ket
 // D is materialised in HBM in chunks (the caller's workspace), so that the MFMA kernels issue nothing but operand
 // loads and MFMAs and the gather work runs in launches of its own (FP64 MFMA blocks its SIMD's vector issue).
 //
@@ -97,11 +98,26 @@ static int launch_excite(int layout, int norb, int64_t nb, int64_t dim, const in
 // A^T B over the block's rows, A = D~_bra rows, B = D_ket rows (RT * RT * 8 accumulator registers a lane: 72 at twelve
 // orbitals, where 3 x 3 waves hold 3 x 3 tiles each).  The waves of the first wave row also carry g1[rs] = sum_k bra[k] B[k][rs] on the B fragments they hold anyway (RT FP64 FMAs per RT*RT MFMAs), wave 0 the overlap.
 // Partials: Pm[blk][npad][npad], Pg[blk][npad], Po[blk].
+// blockIdx.z picks the bra r = r0 + z of a block call (evc_fci_trdm_rows_block): its D~ rows and its vector reach the
+// kernel by value, its partials lie r * nblk blocks into Pm / Pg / Po, and B is shared.  What one (bra, ket, block)
+// computes does not depend on the other bras of the launch.
+constexpr int kTrdmBras = 16;
+struct TrdmBras {
+    const double *A[kTrdmBras];     // D~ of bra r: all its blocks (a_resident) or the blocks of this launch
+    const double *c[kTrdmBras];     // the bra vectors
+    int64_t row[kTrdmBras];         // first output row of bra r
+};
 template <int RT, int NBW>
 __global__ __launch_bounds__(64 * NBW * NBW) void fci_trdm_kernel(
-    const double *__restrict__ A, const double *__restrict__ B, const double *__restrict__ bra,
-    const double *__restrict__ ket, int npad, int nq, int64_t rows, int64_t blk0, int64_t dim, int a_resident,
-    double *__restrict__ Pm, double *__restrict__ Pg, double *__restrict__ Po) {
+    TrdmBras bras, int r0, const double *__restrict__ B, const double *__restrict__ ket, int npad, int nq, int64_t rows,
+    int64_t blk0, int64_t nblk, int64_t dim, int a_resident, double *__restrict__ Pm, double *__restrict__ Pg,
+    double *__restrict__ Po) {
+    const int br = r0 + (int)blockIdx.z;
+    const double *__restrict__ A = bras.A[br];
+    const double *__restrict__ bra = bras.c[br];
+    Pm += (int64_t)br * nblk * npad * npad;
+    Pg += (int64_t)br * nblk * npad;
+    Po += (int64_t)br * nblk;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int nt = npad / 16;
@@ -176,14 +192,23 @@ __global__ __launch_bounds__(64 * NBW * NBW) void fci_trdm_kernel(
     }
 }
 
-// g1[pq] = sum over the blocks in order; dm1[q][p] = g1[p][q]; thread n2: the overlap
-__global__ __launch_bounds__(256) void fci_trdm_reduce1_kernel(const double *__restrict__ Pg,
+// g1[pq] = sum over the blocks in order; dm1[q][p] = g1[p][q]; thread n2: the overlap.  blockIdx.y: bra r0 + y, whose
+// results go to output row bras.row[r] + i (ket i).
+__global__ __launch_bounds__(256) void fci_trdm_reduce1_kernel(TrdmBras bras, int r0, int64_t i,
+                                                               const double *__restrict__ Pg,
                                                                const double *__restrict__ Po, int norb, int npad,
                                                                int64_t nblk, double *__restrict__ g1,
                                                                double *__restrict__ dm1, double *__restrict__ ovlp) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int n2 = norb * norb;
     if (t > n2) return;
+    const int br = r0 + (int)blockIdx.y;
+    const int64_t row = bras.row[br] + i;
+    Pg += (int64_t)br * nblk * npad;
+    Po += (int64_t)br * nblk;
+    g1 += (int64_t)br * npad;
+    dm1 += row * n2;
+    ovlp += row;
     double s = 0.0;
     if (t == n2) {
         for (int64_t b = 0; b < nblk; ++b) s += Po[b];
@@ -195,13 +220,19 @@ __global__ __launch_bounds__(256) void fci_trdm_reduce1_kernel(const double *__r
     dm1[(t % norb) * norb + t / norb] = s;
 }
 
-// dm2[p,q,r,s] = sum_blocks M[pq,rs] - delta_qr g1[p,s]
-__global__ __launch_bounds__(256) void fci_trdm_reduce2_kernel(const double *__restrict__ Pm,
+// dm2[p,q,r,s] = sum_blocks M[pq,rs] - delta_qr g1[p,s]; blockIdx.y: bra r0 + y.  dense: dm2 is the (rows, norb^4)
+// output and the bra writes its row bras.row[r] + i; otherwise dm2 is one scratch block (the packed call, one bra).
+__global__ __launch_bounds__(256) void fci_trdm_reduce2_kernel(TrdmBras bras, int r0, int64_t i, int dense,
+                                                               const double *__restrict__ Pm,
                                                                const double *__restrict__ g1, int norb, int npad,
                                                                int64_t nblk, double *__restrict__ dm2) {
     const int n2 = norb * norb;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= n2 * n2) return;
+    const int br = r0 + (int)blockIdx.y;
+    Pm += (int64_t)br * nblk * npad * npad;
+    g1 += (int64_t)br * npad;
+    if (dense) dm2 += (bras.row[br] + i) * ((int64_t)n2 * n2);
     const int pq = idx / n2, rs = idx - pq * n2;
     const double *__restrict__ src = Pm + (int64_t)pq * npad + rs;
     double m = 0.0;
@@ -211,16 +242,18 @@ __global__ __launch_bounds__(256) void fci_trdm_reduce2_kernel(const double *__r
 }
 
 struct TrdmLaunch {
-    const double *A, *B, *bra, *ket;
+    const TrdmBras *bras;
+    int r0, nz;                 // bras r0 ... r0 + nz - 1 (the grid's z)
+    const double *B, *ket;
     int npad, nq;
-    int64_t rows, blk0, nblocks, dim;
+    int64_t rows, blk0, nblocks, nblk, dim;
     int a_resident;
     double *Pm, *Pg, *Po;
 };
 template <int RT, int NBW>
 static void launch_trdm_t(const TrdmLaunch &a, hipStream_t st) {
-    fci_trdm_kernel<RT, NBW><<<dim3((unsigned)a.nblocks, a.nq * a.nq), 64 * NBW * NBW, 0, st>>>(
-        a.A, a.B, a.bra, a.ket, a.npad, a.nq, a.rows, a.blk0, a.dim, a.a_resident, a.Pm, a.Pg, a.Po);
+    fci_trdm_kernel<RT, NBW><<<dim3((unsigned)a.nblocks, a.nq * a.nq, a.nz), 64 * NBW * NBW, 0, st>>>(
+        *a.bras, a.r0, a.B, a.ket, a.npad, a.nq, a.rows, a.blk0, a.nblk, a.dim, a.a_resident, a.Pm, a.Pg, a.Po);
 }
 // tiles per wave edge, waves per workgroup edge, quadrants per edge for nt tiles per edge
 static void fci_trdm_config(int nt, int &rt, int &nbw, int &nq) {
@@ -376,10 +409,28 @@ static int fci_shape(const char *who, int norb, int64_t na, int64_t nb, FciShape
     s.sigma_col = (size_t)s.npad * 8;
     return 0;
 }
+// the partials and g1 of nbras bras: Pm[r][blk], Pg[r][blk], Po[r][blk], g1[r]; one bra: trdm_fixed
+static size_t fci_trdm_fixed_bytes(const FciShape &s, int nbras) {
+    return align_up((size_t)nbras * ((size_t)s.nblk * ((size_t)s.npad * s.npad + s.npad + 1) + s.npad) * 8, 256);
+}
+// the least t-RDM workspace of nbras bras: one block of D~ per bra and one of D_ket
+static size_t fci_trdm_need_bytes(const FciShape &s, int nbras) {
+    return fci_trdm_fixed_bytes(s, nbras) + (size_t)(nbras + 1) * s.trdm_block;
+}
 
 }  // namespace evc
 
 using namespace evc;
+
+extern "C" size_t evc_fci_rows_block_workspace_bytes(int norb, int64_t na, int64_t nb, int nbras, int minimal) {
+    FciShape s;
+    if (nbras < 1 || nbras > kTrdmBras) return 0;
+    if (fci_shape("evc_fci_rows_block_workspace_bytes", norb, na, nb, s)) return 0;
+    const size_t t = minimal ? fci_trdm_need_bytes(s, nbras)
+                             : fci_trdm_fixed_bytes(s, nbras) + s.trdm_block * (size_t)((nbras + 1) * s.nblk);
+    const size_t g = s.sigma_fixed + s.sigma_col * (size_t)(minimal ? 64 : s.ldg);
+    return t > g ? t : g;
+}
 
 extern "C" size_t evc_fci_workspace_bytes(int norb, int64_t na, int64_t nb, int minimal) {
     FciShape s;
@@ -404,56 +455,79 @@ extern "C" int evc_fci_excite(int norb, int64_t na, int64_t nb, const int32_t *t
     return launch_excite(layout, norb, nb, s.dim, tab_a, tab_b, c, k0, nk, D, ld, as_stream(stream));
 }
 
-// The row call behind evc_fci_trdm_rows and evc_fci_trdm_rows_packed: the bra against every ket, the determinant blocks in
-// order, then the two reductions per ket.  `dm2` (nkets, norb^4): the dense two-body results; NULL: fci_trdm_reduce2_kernel
-// writes each ket's dense block into `slot` (norb^4 doubles) and fci_row_pack_kernel (fci_pack.hip) packs it into row i of
-// `rows` (pitch ld) in `layout`.  ws / ws_bytes: the t-RDM workspace alone (at least trdm_fixed + 2 trdm_block).
-static int fci_trdm_rows_run(const FciShape &s, const int32_t *tab_a, const int32_t *tab_b, const double *bra,
-                             const double *const *kets, int nkets, double *ovlp, double *dm1, double *dm2, double *slot,
-                             int layout, double *rows, int64_t ld, void *ws, size_t ws_bytes, hipStream_t st) {
+// The row call behind evc_fci_trdm_rows, evc_fci_trdm_rows_packed (one bra) and evc_fci_trdm_rows_block: bra r against
+// kets[0 .. nkets_of[r] - 1] (counts non-decreasing, so the bras that see ket i are r0(i) ... nbras - 1), the determinant
+// blocks in order, then the two reductions per ket.  The ket-side D of a chunk is formed once and read by every bra of
+// the launch (the grid's z); what a (bra, ket) pair computes is what it computes alone.  Results go to the consecutive
+// ragged rows off_r + i.  `dm2` (rows, norb^4): the dense two-body results; NULL (one bra): fci_trdm_reduce2_kernel writes
+// each ket's dense block into `slot` (norb^4 doubles) and fci_row_pack_kernel (fci_pack.hip) packs it into row i of
+// `rows` (pitch ld) in `layout`.  ws / ws_bytes: the t-RDM workspace alone (at least fci_trdm_need_bytes(s, nbras)).
+// note_bras: 0, or nbras for the block call's record.
+static int fci_trdm_rows_run(const FciShape &s, const int32_t *tab_a, const int32_t *tab_b, const double *const *bras,
+                             int nbras, const double *const *kets, const int *nkets_of, int note_bras, double *ovlp,
+                             double *dm1, double *dm2, double *slot, int layout, double *rows, int64_t ld, void *ws,
+                             size_t ws_bytes, hipStream_t st) {
     const int norb = s.norb;
     const int64_t nb = s.nb;
-    const int64_t nfit = (int64_t)((ws_bytes - s.trdm_fixed) / s.trdm_block);
-    const bool resident = nfit >= s.nblk + 1;   // D~_bra whole: formed once for all the kets
-    const int64_t cb = resident ? (nfit - s.nblk < s.nblk ? nfit - s.nblk : s.nblk) : nfit / 2;
+    const int64_t nfit = (int64_t)((ws_bytes - fci_trdm_fixed_bytes(s, nbras)) / s.trdm_block);
+    const bool resident = nfit >= nbras * s.nblk + 1;   // D~ of every bra whole: formed once for all the kets
+    const int64_t cb = resident ? (nfit - nbras * s.nblk < s.nblk ? nfit - nbras * s.nblk : s.nblk) : nfit / (nbras + 1);
+    const int64_t bra_blocks = resident ? s.nblk : cb;  // blocks of D~ each bra holds
     double *Pm = static_cast<double *>(ws);
-    double *Pg = Pm + s.nblk * s.npad * s.npad;
-    double *Po = Pg + s.nblk * s.npad;
-    double *g1 = Po + s.nblk;
-    double *Dbra = reinterpret_cast<double *>(static_cast<char *>(ws) + s.trdm_fixed);
-    double *Dket = Dbra + (resident ? s.nblk : cb) * s.rows * s.npad;
+    double *Pg = Pm + nbras * s.nblk * s.npad * s.npad;
+    double *Po = Pg + nbras * s.nblk * s.npad;
+    double *g1 = Po + nbras * s.nblk;
+    double *Dbra = reinterpret_cast<double *>(static_cast<char *>(ws) + fci_trdm_fixed_bytes(s, nbras));
+    double *Dket = Dbra + nbras * bra_blocks * s.rows * s.npad;
     const int n2 = norb * norb;
     int trt, tnbw, nq;
     fci_trdm_config(s.nt, trt, tnbw, nq);
+    TrdmBras tb = {};
+    for (int r = 0; r < nbras; ++r) {
+        tb.A[r] = Dbra + r * bra_blocks * s.rows * s.npad;
+        tb.c[r] = bras[r];
+        tb.row[r] = r ? tb.row[r - 1] + nkets_of[r - 1] : 0;
+    }
     if (resident)
-        if (int rc = launch_excite(EVC_FCI_DET_MAJOR_T, norb, nb, s.dim, tab_a, tab_b, bra, 0, s.nblk * s.rows, Dbra,
-                                   s.npad, st))
-            return rc;
-    for (int i = 0; i < nkets; ++i) {
+        for (int r = 0; r < nbras; ++r)
+            if (int rc = launch_excite(EVC_FCI_DET_MAJOR_T, norb, nb, s.dim, tab_a, tab_b, bras[r], 0, s.nblk * s.rows,
+                                       const_cast<double *>(tb.A[r]), s.npad, st))
+                return rc;
+    int r0 = 0;
+    for (int i = 0; i < nkets_of[nbras - 1]; ++i) {
+        while (nkets_of[r0] <= i) ++r0;
+        const int nz = nbras - r0;
         for (int64_t b0 = 0; b0 < s.nblk; b0 += cb) {
             const int64_t nbk = s.nblk - b0 < cb ? s.nblk - b0 : cb;
             if (!resident)
-                if (int rc = launch_excite(EVC_FCI_DET_MAJOR_T, norb, nb, s.dim, tab_a, tab_b, bra, b0 * s.rows,
-                                           nbk * s.rows, Dbra, s.npad, st))
-                    return rc;
+                for (int r = r0; r < nbras; ++r)
+                    if (int rc = launch_excite(EVC_FCI_DET_MAJOR_T, norb, nb, s.dim, tab_a, tab_b, bras[r], b0 * s.rows,
+                                               nbk * s.rows, const_cast<double *>(tb.A[r]), s.npad, st))
+                        return rc;
             if (int rc = launch_excite(EVC_FCI_DET_MAJOR, norb, nb, s.dim, tab_a, tab_b, kets[i], b0 * s.rows,
                                        nbk * s.rows, Dket, s.npad, st))
                 return rc;
-            const TrdmLaunch a = {Dbra, Dket, bra, kets[i], s.npad, nq, s.rows, b0, nbk, s.dim, resident ? 1 : 0, Pm, Pg, Po};
+            const TrdmLaunch a = {&tb, r0, nz, Dket, kets[i], s.npad, nq, s.rows, b0, nbk, s.nblk, s.dim, resident ? 1 : 0,
+                                  Pm, Pg, Po};
             launch_trdm(trt, tnbw, a, st);
             EVC_LAUNCH_CHECK("fci_trdm_kernel");
         }
-        fci_trdm_reduce1_kernel<<<(unsigned)ceil_div(n2 + 1, 256), 256, 0, st>>>(
-            Pg, Po, norb, s.npad, s.nblk, g1, dm1 + (int64_t)i * n2, ovlp + i);
+        fci_trdm_reduce1_kernel<<<dim3((unsigned)ceil_div(n2 + 1, 256), nz), 256, 0, st>>>(
+            tb, r0, i, Pg, Po, norb, s.npad, s.nblk, g1, dm1, ovlp);
         EVC_LAUNCH_CHECK("fci_trdm_reduce1_kernel");
-        fci_trdm_reduce2_kernel<<<(unsigned)ceil_div((int64_t)n2 * n2, 256), 256, 0, st>>>(
-            Pm, g1, norb, s.npad, s.nblk, dm2 ? dm2 + (int64_t)i * n2 * n2 : slot);
+        fci_trdm_reduce2_kernel<<<dim3((unsigned)ceil_div((int64_t)n2 * n2, 256), nz), 256, 0, st>>>(
+            tb, r0, i, dm2 ? 1 : 0, Pm, g1, norb, s.npad, s.nblk, dm2 ? dm2 : slot);
         EVC_LAUNCH_CHECK("fci_trdm_reduce2_kernel");
         if (!dm2)
             if (int rc = launch_fci_row_pack(layout, norb, slot, rows + (int64_t)i * ld, ld, st)) return rc;
     }
-    note_kernel(EVC_PROF_FCI_TRDM, "fci_trdm_kernel<%d,%d> quadrants=%d blocks=%lld bra_resident=%d ket_blocks=%lld", trt,
-                tnbw, nq * nq, (long long)s.nblk, resident ? 1 : 0, (long long)cb);
+    if (note_bras)
+        note_kernel(EVC_PROF_FCI_TRDM,
+                    "fci_trdm_kernel<%d,%d> quadrants=%d blocks=%lld bra_resident=%d ket_blocks=%lld bras=%d", trt, tnbw,
+                    nq * nq, (long long)s.nblk, resident ? 1 : 0, (long long)cb, note_bras);
+    else
+        note_kernel(EVC_PROF_FCI_TRDM, "fci_trdm_kernel<%d,%d> quadrants=%d blocks=%lld bra_resident=%d ket_blocks=%lld",
+                    trt, tnbw, nq * nq, (long long)s.nblk, resident ? 1 : 0, (long long)cb);
     return 0;
 }
 
@@ -470,8 +544,54 @@ extern "C" int evc_fci_trdm_rows(int norb, int64_t na, int64_t nb, const int32_t
     EVC_REQUIRE(ws_bytes >= need, "evc_fci_trdm_rows: workspace of %zu bytes, at least %zu needed for %lld determinants",
                 ws_bytes, need, (long long)s.dim);
     clear_fci_kernels(EVC_PROF_FCI_TRDM);
-    return fci_trdm_rows_run(s, tab_a, tab_b, bra, kets, nkets, ovlp, dm1, dm2, nullptr, 0, nullptr, 0, ws, ws_bytes,
-                             as_stream(stream));
+    return fci_trdm_rows_run(s, tab_a, tab_b, &bra, 1, kets, &nkets, 0, ovlp, dm1, dm2, nullptr, 0, nullptr, 0, ws,
+                             ws_bytes, as_stream(stream));
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+static bool fci_overlaps(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+extern "C" int evc_fci_trdm_rows_block(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
+                                       const double *const *bras, int nbras, const double *const *kets,
+                                       const int *nkets_of, double *ovlp, double *dm1, double *dm2, void *ws,
+                                       size_t ws_bytes, void *stream) {
+    FciShape s;
+    if (int rc = fci_shape("evc_fci_trdm_rows_block", norb, na, nb, s)) return rc;
+    EVC_REQUIRE(tab_a && tab_b && bras && kets && nkets_of && ovlp && dm1 && dm2 && ws,
+                "evc_fci_trdm_rows_block: null pointer");
+    EVC_REQUIRE(nbras >= 1 && nbras <= kTrdmBras, "evc_fci_trdm_rows_block: nbras=%d (1 ... %d)", nbras, kTrdmBras);
+    int64_t total = 0;
+    for (int r = 0; r < nbras; ++r) {
+        EVC_REQUIRE(bras[r], "evc_fci_trdm_rows_block: bras[%d] is null", r);
+        EVC_REQUIRE(nkets_of[r] >= 1 && nkets_of[r] <= 4096, "evc_fci_trdm_rows_block: nkets_of[%d]=%d (1 ... 4096)", r,
+                    nkets_of[r]);
+        EVC_REQUIRE(r == 0 || nkets_of[r] >= nkets_of[r - 1],
+                    "evc_fci_trdm_rows_block: nkets_of[%d]=%d below nkets_of[%d]=%d (counts must not decrease)", r,
+                    nkets_of[r], r - 1, nkets_of[r - 1]);
+        total += nkets_of[r];
+    }
+    const int nkets = nkets_of[nbras - 1];
+    for (int i = 0; i < nkets; ++i) EVC_REQUIRE(kets[i], "evc_fci_trdm_rows_block: kets[%d] is null", i);
+    EVC_REQUIRE(aligned16(ws), "evc_fci_trdm_rows_block: workspace not 16-byte aligned");
+    const size_t need = fci_trdm_need_bytes(s, nbras);
+    EVC_REQUIRE(ws_bytes >= need,
+                "evc_fci_trdm_rows_block: workspace of %zu bytes, at least %zu needed for %lld determinants and %d bras",
+                ws_bytes, need, (long long)s.dim, nbras);
+    const size_t n2 = (size_t)norb * norb, vec = (size_t)s.dim * 8;
+    const struct { const void *p; size_t n; const char *name; } outs[3] = {
+        {ovlp, (size_t)total * 8, "ovlp"}, {dm1, (size_t)total * n2 * 8, "dm1"}, {dm2, (size_t)total * n2 * n2 * 8, "dm2"}};
+    for (const auto &o : outs) {
+        for (int r = 0; r < nbras; ++r)
+            EVC_REQUIRE(!fci_overlaps(o.p, o.n, bras[r], vec), "evc_fci_trdm_rows_block: %s overlaps bras[%d]", o.name, r);
+        for (int i = 0; i < nkets; ++i)
+            EVC_REQUIRE(!fci_overlaps(o.p, o.n, kets[i], vec), "evc_fci_trdm_rows_block: %s overlaps kets[%d]", o.name, i);
+    }
+    clear_fci_kernels(EVC_PROF_FCI_TRDM);
+    return fci_trdm_rows_run(s, tab_a, tab_b, bras, nbras, kets, nkets_of, nbras, ovlp, dm1, dm2, nullptr, 0, nullptr, 0,
+                             ws, ws_bytes, as_stream(stream));
 }
 
 // the scratch slot of the packed row call: one dense dm2 block, in front of the t-RDM workspace
@@ -504,8 +624,9 @@ extern "C" int evc_fci_trdm_rows_packed(int norb, int64_t na, int64_t nb, const 
                 need, (long long)s.dim);
     clear_fci_kernels(EVC_PROF_FCI_TRDM);
     clear_fci_kernels(EVC_PROF_FCI_PACK);
-    if (int rc = fci_trdm_rows_run(s, tab_a, tab_b, bra, kets, nkets, ovlp, dm1, nullptr, static_cast<double *>(ws), layout,
-                                   rows, ld, static_cast<char *>(ws) + slot, ws_bytes - slot, as_stream(stream)))
+    if (int rc = fci_trdm_rows_run(s, tab_a, tab_b, &bra, 1, kets, &nkets, 0, ovlp, dm1, nullptr,
+                                   static_cast<double *>(ws), layout, rows, ld, static_cast<char *>(ws) + slot,
+                                   ws_bytes - slot, as_stream(stream)))
         return rc;
     note_fci_row_pack(layout, norb, nkets, ld);
     return 0;

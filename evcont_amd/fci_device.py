@@ -12,7 +12,8 @@ set of ``resident.ResidentFCI_EVCont_obj``), and ``transform_ci(ci, nelec, u)``
 ``cas_trans_rdm12_rows(bra, kets)``: the t-RDMs between CAS states in different orbital sets, expanded to all N orbitals
 on the device (``csrc/cas_expand.hip``; ``CAS_EVCont_obj(ncas, neleca, cisolver=DeviceFCI())``), with
 ``cas_trans_rdm12_block(bras, kets)`` for the roots of one geometry (one ``evc_fci_rotate_block`` per stored geometry;
-``transform_ci_block`` is that rotation on its own).  Opt in with
+``transform_ci_block`` is that rotation on its own; all bras go through one ``evc_fci_trdm_rows_block`` call, and
+``triangular=True`` is the ragged form of a training-set append, ``resident.ResidentCAS_EVCont_obj``).  Opt in with
 ``FCI_EVCont_obj(cisolver=DeviceFCI(), cibasis="OAO")``, or ``cibasis="canonical"`` to solve in the Hartree-Fock basis,
 where the Davidson solver's diagonal preconditioner works best near equilibrium.
 
@@ -557,17 +558,41 @@ class DeviceFCI:
               "evc_fci_rotate_block")
         return outs, na, nb
 
-    def cas_trans_rdm12_block(self, bras, kets, layout=None, out_rows: Optional[torch.Tensor] = None):
+    def _block_grant(self, lib, norb, na, nb, nbras):
+        """``(bras per evc_fci_trdm_rows_block call, workspace bytes)``: all ``nbras`` in one call with everything
+        resident by default; under ``workspace_bytes`` as many bras per call as its least workspace allows (one bra
+        always fits: ``_setup`` checked that), so that the bound on the workspace holds here as in every other call."""
+        full = lib.evc_fci_rows_block_workspace_bytes(norb, na, nb, nbras, 0)
+        if full == 0:
+            check(-1, "evc_fci_rows_block_workspace_bytes")
+        if self.workspace_bytes is None:
+            return nbras, full
+        cap = int(self.workspace_bytes)
+        per = nbras
+        while per > 1 and lib.evc_fci_rows_block_workspace_bytes(norb, na, nb, per, 1) > cap:
+            per -= 1
+        return per, min(cap, lib.evc_fci_rows_block_workspace_bytes(norb, na, nb, per, 0))
+
+    def cas_trans_rdm12_block(self, bras, kets, layout=None, out_rows: Optional[torch.Tensor] = None,
+                              triangular: bool = False):
         """``cas_trans_rdm12_rows`` for several bras that share their orbitals (the roots of one geometry; the statement
         is ``cas_small.trans_rdm12_block``), with a leading bra axis: ``(ovlp (R,K), dm1 (R,K,N,N), dm2 (R,K,N,N,N,N))``
         without a layout; with one, ``out_rows`` is a contiguous ``(R K, ld)`` float64 device tensor, bra-major, and
         ``(ovlp, dm1)`` is returned.  Row ``(r, k)`` has the bits of ``cas_trans_rdm12_rows(bras[r], kets)`` row ``k``.
 
+        ``triangular=True`` is the form of a training-set append: the last ``R`` kets must be the bras themselves (by
+        identity, ``ValueError`` otherwise) and bra ``r`` is taken against ``kets[:K - R + r + 1]`` only.  The results are
+        ragged: lists of ``R`` arrays ``(K - R + r + 1, ...)``; with a layout ``out_rows`` is one contiguous
+        ``(sum_r (K - R + r + 1), ld)`` tensor, bra after bra -- the row order of ``resident.ResidentTRDMs`` for the
+        states ``T ... T + R - 1``.  Every row has the bits of the rectangular call's row ``(r, k)``.
+
         The pair intermediates depend on the two orbital sets alone: they are formed once per group of consecutive kets
         that share a ``U``, the group's kets are rotated by one ``evc_fci_rotate_block`` call and scaled by ``fac`` on the
-        device, and ``A_a / B_a / Qc`` are uploaded once for all bras.  Per bra: one ``evc_fci_trdm_rows`` call against
-        all rotated kets and one ``evc_cas_expand_rows`` call.  A pair beyond the conditioning guard raises ``ValueError``
-        before anything is launched."""
+        device, and ``A_a / B_a / Qc`` are uploaded once for all bras.  One ``evc_fci_trdm_rows_block`` call takes all
+        bras against the rotated kets (the ket-side excitations of a determinant chunk formed once for all of them),
+        then per bra one ``evc_cas_expand_rows`` call on the prefix it sees.  ``CASState.ci`` may be a float64 tensor
+        on the solver's device: the rotation and the bra side then read it as it is.  A pair beyond the conditioning
+        guard raises ``ValueError`` before anything is launched."""
         from . import cas_small
         bras, kets = list(bras), list(kets)
         if not bras or not kets:
@@ -575,6 +600,15 @@ class DeviceFCI:
         cas_small.check_block("DeviceFCI.cas_trans_rdm12_block", bras, kets)
         bra0 = bras[0]
         R, K, n, ncas, nelec = len(bras), len(kets), int(bra0.U.shape[0]), int(bra0.ncas), _nelec(bra0.nelecas)
+        if triangular:
+            if K < R or any(kets[K - R + r] is not bras[r] for r in range(R)):
+                raise ValueError(f"DeviceFCI.cas_trans_rdm12_block: triangular=True takes kets whose last {R} entries are "
+                                 "the bras themselves, in order")
+            counts = [K - R + r + 1 for r in range(R)]
+        else:
+            counts = [K] * R
+        offs = [sum(counts[:r]) for r in range(R)]
+        total = sum(counts)
         lay = {None: _lib.LAYOUT_FULL6, "pack2": _lib.LAYOUT_PACK2, "sym8": _lib.LAYOUT_SYM8}.get(layout, layout)
         if lay not in (_lib.LAYOUT_FULL6, _lib.LAYOUT_PACK2, _lib.LAYOUT_SYM8):
             raise EvcontHipError(f"DeviceFCI.cas_trans_rdm12_block: layout={layout!r}, expected None, 'pack2' or 'sym8'")
@@ -588,19 +622,23 @@ class DeviceFCI:
             rows_all = out_rows
             on_dev = (torch.is_tensor(rows_all) and rows_all.device.type == dev.type
                       and dev.index in (None, rows_all.device.index))
-            if not (on_dev and rows_all.dtype == F64 and rows_all.dim() == 2 and rows_all.shape[0] == R * K
-                    and rows_all.stride(1) == 1 and (R * K == 1 or rows_all.stride(0) == rows_all.shape[1])):
-                raise EvcontHipError(f"DeviceFCI.cas_trans_rdm12_block: out_rows must be a contiguous ({R * K}, ld) float64 "
+            if not (on_dev and rows_all.dtype == F64 and rows_all.dim() == 2 and rows_all.shape[0] == total
+                    and rows_all.stride(1) == 1 and (total == 1 or rows_all.stride(0) == rows_all.shape[1])):
+                raise EvcontHipError(f"DeviceFCI.cas_trans_rdm12_block: out_rows must be a contiguous ({total}, ld) float64 "
                                      f"tensor on {dev}")
         else:
             # (one tensor per bra: evc_cas_expand_rows wants 16-byte aligned rows, which n^4 doubles do not keep)
-            rows_all = [torch.empty((K, n ** 4), dtype=F64, device=dev) for _ in bras]
+            rows_all = [torch.empty((counts[r], n ** 4), dtype=F64, device=dev) for r in range(R)]
         dkets = []
         for (first, count), (fac, s_eff, _, _, _) in zip(groups, inter):
             rotated, _, _ = self._rotate_block([k.ci for k in kets[first:first + count]], nelec,
                                                np.ascontiguousarray(s_eff.T))
             dkets.extend(t.mul_(fac) for t in rotated)
         lib, dta, dtb, na, nb, grant = self._setup(ncas, nelec)      # (the rotation may have replaced the workspace)
+        per_call, grant = self._block_grant(lib, ncas, na, nb, R)
+        if self._ws.numel() < grant:
+            self._ws = None
+            self._ws = torch.empty(grant, dtype=torch.uint8, device=dev)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
         per_ket = [x for (_, count), x in zip(groups, inter) for _ in range(count)]
         A_act = up(np.stack([x[2] for x in per_ket]))                  # (K, n, ncas), the same for every bra
@@ -612,25 +650,44 @@ class DeviceFCI:
         if self._cas_ws is None or self._cas_ws.numel() < need:
             self._cas_ws = None
             self._cas_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        ovlp = [torch.empty(K, dtype=F64, device=dev) for _ in bras]
-        d1 = torch.empty((K, ncas, ncas), dtype=F64, device=dev)
-        d2 = torch.empty((K, ncas ** 4), dtype=F64, device=dev)
-        dm1 = [torch.empty((K, n, n), dtype=F64, device=dev) for _ in bras]
-        ptrs = (C.c_void_p * K)(*[t.data_ptr() for t in dkets])
-        for r, bra in enumerate(bras):
-            rows = rows_all[r] if lay == _lib.LAYOUT_FULL6 else rows_all[r * K:(r + 1) * K]
-            dbra = self._upload(bra.ci, na, nb, cache=False)
-            check(lib.evc_fci_trdm_rows(ncas, na, nb, dta.data_ptr(), dtb.data_ptr(), dbra.data_ptr(), ptrs, K,
-                                        ovlp[r].data_ptr(), d1.data_ptr(), d2.data_ptr(), self._ws.data_ptr(), grant,
-                                        self._stream()), "evc_fci_trdm_rows")
-            check(lib.evc_cas_expand_rows(n, ncas, K, A_act.data_ptr(), B_act.data_ptr(),
-                                          None if Qc is None else Qc.data_ptr(), ovlp[r].data_ptr(), d1.data_ptr(),
-                                          d2.data_ptr(), dm1[r].data_ptr(), lay, rows.data_ptr(), int(rows.shape[1]),
+        # the active-space results of all bras, ragged and consecutive: bra r holds rows offs[r] ... + counts[r] - 1
+        ovlp = torch.empty(total, dtype=F64, device=dev)
+        d1 = torch.empty((total, ncas * ncas), dtype=F64, device=dev)
+        d2 = torch.empty((total, ncas ** 4), dtype=F64, device=dev)
+        dm1 = [torch.empty((counts[r], n, n), dtype=F64, device=dev) for r in range(R)]
+        dbras = [self._upload(bra.ci, na, nb, cache=False) for bra in bras]
+        for r0 in range(0, R, per_call):
+            nr = min(per_call, R - r0)
+            nk = counts[r0 + nr - 1]
+            bp = (C.c_void_p * nr)(*[t.data_ptr() for t in dbras[r0:r0 + nr]])
+            kp = (C.c_void_p * nk)(*[t.data_ptr() for t in dkets[:nk]])
+            cnt = (C.c_int * nr)(*counts[r0:r0 + nr])
+            check(lib.evc_fci_trdm_rows_block(ncas, na, nb, dta.data_ptr(), dtb.data_ptr(), bp, nr, kp, cnt,
+                                              ovlp[offs[r0]:].data_ptr(), d1[offs[r0]:].data_ptr(),
+                                              d2[offs[r0]:].data_ptr(), self._ws.data_ptr(), grant, self._stream()),
+                  "evc_fci_trdm_rows_block")
+        # (evc_cas_expand_rows wants 16-byte aligned inputs and the block call's rows are consecutive, so a bra whose
+        # rows start at an odd double gets a copy: on the append path of every odd T, (1 + ncas^2 + ncas^4) doubles per
+        # row, small beside the n^4 the expansion writes)
+        aligned = lambda t: t if t.data_ptr() % 16 == 0 else t.clone()
+        for r in range(R):
+            o, c = offs[r], counts[r]
+            rows = rows_all[r] if lay == _lib.LAYOUT_FULL6 else rows_all[o:o + c]
+            so, s1, s2 = aligned(ovlp[o:o + c]), aligned(d1[o:o + c]), aligned(d2[o:o + c])
+            check(lib.evc_cas_expand_rows(n, ncas, c, A_act.data_ptr(), B_act.data_ptr(),
+                                          None if Qc is None else Qc.data_ptr(), so.data_ptr(), s1.data_ptr(),
+                                          s2.data_ptr(), dm1[r].data_ptr(), lay, rows.data_ptr(), int(rows.shape[1]),
                                           self._cas_ws.data_ptr(), need, self._stream()), "evc_cas_expand_rows")
         # (each bra's results straight into their place on the host: no stacked copy on the device)
+        if triangular:
+            h_ovlp = [ovlp[offs[r]:offs[r] + counts[r]].cpu().numpy() for r in range(R)]
+            h_dm1 = [dm1[r].cpu().numpy() for r in range(R)]
+            if lay != _lib.LAYOUT_FULL6:
+                return h_ovlp, h_dm1
+            return h_ovlp, h_dm1, [rows_all[r].cpu().numpy().reshape(counts[r], n, n, n, n) for r in range(R)]
         h_ovlp, h_dm1 = np.empty((R, K)), np.empty((R, K, n, n))
         for r in range(R):
-            torch.from_numpy(h_ovlp[r]).copy_(ovlp[r])
+            torch.from_numpy(h_ovlp[r]).copy_(ovlp[offs[r]:offs[r] + K])
             torch.from_numpy(h_dm1[r]).copy_(dm1[r])
         if lay != _lib.LAYOUT_FULL6:
             return h_ovlp, h_dm1
@@ -641,68 +698,21 @@ class DeviceFCI:
 
     def cas_trans_rdm12_rows(self, bra, kets, layout=None, out_rows: Optional[torch.Tensor] = None):
         """Overlaps and transition RDMs, in the OAO basis, of one CAS state against ``kets`` whose orbitals differ from
-        its own (``cas_small.CASState``; the statement is ``cas_small.trans_rdm12_rows``): the pair intermediates on the
-        host (m x m and N x m matrices), then per ket one ``evc_fci_rotate`` with ``u = s_eff^T`` scaled by ``fac``, one
-        ``evc_fci_trdm_rows`` call for all kets in the active space, and one ``evc_cas_expand_rows`` call
-        (``csrc/cas_expand.hip``) that expands its results to N orbitals with the core terms.  Nothing but the overlaps,
-        ``dm1`` and, without a layout, ``dm2`` comes back to the host.
+        its own (``cas_small.CASState``; the statement is ``cas_small.trans_rdm12_rows``): the ``R = 1`` case of
+        ``cas_trans_rdm12_block``.  The pair intermediates on the host (m x m and N x m matrices, once per group of
+        consecutive kets that share their orbitals), the kets rotated with ``u = s_eff^T`` and scaled by ``fac`` on the
+        device, one active-space row call for all kets, and one ``evc_cas_expand_rows`` call (``csrc/cas_expand.hip``)
+        that expands its results to N orbitals with the core terms.  Nothing but the overlaps, ``dm1`` and, without a
+        layout, ``dm2`` comes back to the host.
 
         ``layout=None`` returns ``(ovlp (K,), dm1 (K,N,N), dm2 (K,N,N,N,N))`` as numpy.  With ``layout`` ("pack2" /
         "sym8") the two-body rows go into ``out_rows``, a contiguous ``(K, ld)`` float64 device tensor, in the format of
         ``trans_rdm12_rows_packed``, and ``(ovlp, dm1)`` is returned.  A pair beyond the conditioning guard raises
         ``ValueError`` before anything is launched."""
-        from . import cas_small
         kets = list(kets)
         if not kets:
             raise EvcontHipError("DeviceFCI.cas_trans_rdm12_rows: no kets")
-        K, n, ncas, nelec = len(kets), int(bra.U.shape[0]), int(bra.ncas), _nelec(bra.nelecas)
-        lay = {None: _lib.LAYOUT_FULL6, "pack2": _lib.LAYOUT_PACK2, "sym8": _lib.LAYOUT_SYM8}.get(layout, layout)
-        if lay not in (_lib.LAYOUT_FULL6, _lib.LAYOUT_PACK2, _lib.LAYOUT_SYM8):
-            raise EvcontHipError(f"DeviceFCI.cas_trans_rdm12_rows: layout={layout!r}, expected None, 'pack2' or 'sym8'")
-        inter = [cas_small.pair_intermediates(bra, ket, f"(bra, ket {i})") for i, ket in enumerate(kets)]
-        lib, dta, dtb, na, nb, grant = self._setup(ncas, nelec)
-        dev = self._dev()
-        dkets = []
-        for ket, (fac, s_eff, _, _, _) in zip(kets, inter):
-            rotated, _, _ = self._rotate(ket.ci, nelec, np.ascontiguousarray(s_eff.T))
-            dkets.append(rotated.mul_(fac))
-        lib, dta, dtb, na, nb, grant = self._setup(ncas, nelec)      # (the rotation may have replaced the workspace)
-        # (not remembered: a state is a bra once, and as a ket it is uploaded for its rotation anew)
-        dbra = self._upload(bra.ci, na, nb, cache=False)
-        ovlp = torch.empty(K, dtype=F64, device=dev)
-        d1 =torch.empty((K, ncas, ncas), dtype=F64, device=dev)
-        d2 = torch.empty((K, ncas ** 4), dtype=F64, device=dev)
-        ptrs = (C.c_void_p * K)(*[t.data_ptr() for t in dkets])
-        check(lib.evc_fci_trdm_rows(ncas, na, nb, dta.data_ptr(), dtb.data_ptr(), dbra.data_ptr(), ptrs, K,
-                                    ovlp.data_ptr(), d1.data_ptr(), d2.data_ptr(), self._ws.data_ptr(), grant,
-                                    self._stream()), "evc_fci_trdm_rows")
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        A_act = up(np.stack([x[2] for x in inter]))                    # (K, n, ncas): orthogonal to each ket's core
-        B_act = up(np.stack([x[3] for x in inter]))
-        Qc = up(np.stack([x[4] for x in inter])) if bra.ncore else None
-        dm1 = torch.empty((K, n, n), dtype=F64, device=dev)
-        if lay == _lib.LAYOUT_FULL6:
-            rows = torch.empty((K, n ** 4), dtype=F64, device=dev)
-        else:
-            rows = out_rows
-            on_dev = torch.is_tensor(rows) and rows.device.type == dev.type and dev.index in (None, rows.device.index)
-            if not (on_dev and rows.dtype == F64 and rows.dim() == 2 and rows.shape[0] == K and rows.stride(1) == 1
-                    and (K == 1 or rows.stride(0) == rows.shape[1])):
-                raise EvcontHipError(f"DeviceFCI.cas_trans_rdm12_rows: out_rows must be a contiguous ({K}, ld) float64 "
-                                     f"tensor on {dev}")
-        need = lib.evc_cas_expand_workspace_bytes(n, ncas, K)
-        if need == 0:
-            check(-1, "evc_cas_expand_workspace_bytes")
-        if self._cas_ws is None or self._cas_ws.numel() < need:
-            self._cas_ws = None
-            self._cas_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        check(lib.evc_cas_expand_rows(n, ncas, K, A_act.data_ptr(), B_act.data_ptr(),
-                                      None if Qc is None else Qc.data_ptr(), ovlp.data_ptr(), d1.data_ptr(),
-                                      d2.data_ptr(), dm1.data_ptr(), lay, rows.data_ptr(), int(rows.shape[1]),
-                                      self._cas_ws.data_ptr(), need, self._stream()), "evc_cas_expand_rows")
-        if lay == _lib.LAYOUT_FULL6:
-            return ovlp.cpu().numpy(), dm1.cpu().numpy(), rows.cpu().numpy().reshape(K, n, n, n, n)
-        return ovlp.cpu().numpy(), dm1.cpu().numpy()
+        return tuple(x[0] for x in self.cas_trans_rdm12_block([bra], kets, layout=layout, out_rows=out_rows))
 
     def energy(self, h1, h2, ci, norb, nelec) -> float:
         dm1, dm2 = self.make_rdm12(ci, norb, nelec)

@@ -8,11 +8,14 @@ the reference's ``scripts/MD/H2O/md_H2O_vdz_CAS_continuation.py`` without PySCF.
     state_swarm([mol], one_rdm, two_rdm, overlap, root=0, integrals="device")
 
     python examples/h2o_cas_md.py [--small] [--states 4] [--steps 20] [--dt 5] [--nroots R --root k [--spin-penalty 0.2]]
+                                  [--resident]
 
 Default: CAS(8,8) with the device FCI solver; ``--small``: CAS(4,4) with the numpy solver (seconds).
 ``--nroots R``: R CASCI roots per training geometry (``CAS_EVCont_obj(..., nroots=R)``, one block call per geometry,
 DESIGN.md 8.1.6) and the dynamics on surface ``--root k``; the first frame prints the vertical excitation energies and
 the oscillator strengths from the ground state.  ``--spin-penalty`` keeps the roots to the ground state's multiplicity.
+``--resident``: the training set grows on the device (``resident.ResidentCAS_EVCont_obj``; device FCI
+solver, CAS(8,8) or with ``--small`` CAS(4,4)) and the calls below read ``cont.device_trdms()``.
 """
 import argparse
 import os
@@ -38,35 +41,43 @@ p.add_argument("--dt", type=float, default=5.0)
 p.add_argument("--nroots", type=int, default=1, help="CASCI roots per training geometry")
 p.add_argument("--root", type=int, default=0, help="surface of the dynamics (0 = ground state)")
 p.add_argument("--spin-penalty", type=float, default=0.0, help="penalty on S^2 in the active-space solver")
+p.add_argument("--resident", action="store_true", help="keep the two-body rows on the device (ResidentCAS_EVCont_obj)")
 a = p.parse_args()
 if not 0 <= a.root < a.nroots:
     p.error(f"--root {a.root} needs --nroots of at least {a.root + 1}")
 
-if a.small:
+if a.small and not a.resident:
     from evcont_amd.fci_small import SmallFCI
     ncas, nelecas, solver = 4, (2, 2), SmallFCI(spin_penalty=a.spin_penalty)
 else:
     from evcont_amd.fci_device import DeviceFCI
-    ncas, nelecas, solver = 8, (4, 4), DeviceFCI(spin_penalty=a.spin_penalty)
+    ncas, nelecas = (4, (2, 2)) if a.small else (8, (4, 4))
+    solver = DeviceFCI(spin_penalty=a.spin_penalty)
 
 dg = DeviceSpdGaussians(*water_shells("cc-pvdz"), nelec=(5, 5))
 t0 = time.time()
-cont = CAS_EVCont_obj(ncas, nelecas, cisolver=solver, nroots=a.nroots)
+if a.resident:
+    from evcont_amd.resident import ResidentCAS_EVCont_obj
+    cont = ResidentCAS_EVCont_obj(ncas, nelecas, cisolver=solver, nroots=a.nroots, layout="sym8")
+else:
+    cont = CAS_EVCont_obj(ncas, nelecas, cisolver=solver, nroots=a.nroots)
 for r in np.linspace(0.90, 1.08, a.states) * ANGSTROM:      # symmetric stretch around the equilibrium bond length
     cont.append_to_rdms(dg.to_mol(water_coords(r_oh=r), need_grad=False))
 print(f"{cont.ntrain} CAS({sum(nelecas)},{ncas}) training states ({a.nroots} per geometry) of water / cc-pVDZ (N = {cont.one_rdm.shape[-1]}): "
       f"{time.time() - t0:.1f} s, E = " + " ".join(f"{e:.6f}" for e in cont.ens))
 
 init = dg.to_mol(water_coords(r_oh=1.06 * 0.9572 * ANGSTROM))       # a stretched start: the molecule vibrates
+# what the excited-state calls read: the host arrays, or the resident container's view
+arrays, kw = ((cont.one_rdm, None, cont.overlap), dict(device_trdms=cont.device_trdms())) if a.resident else \
+    ((cont.one_rdm, cont.two_rdm, cont.overlap), {})
 if a.nroots > 1:
     pairs = [(0, k) for k in range(1, a.nroots)]
-    E, props = get_multistate_properties([init], cont.one_rdm, cont.two_rdm, cont.overlap, a.nroots, pairs)
+    E, props = get_multistate_properties([init], *arrays, a.nroots, pairs, **kw)
     for i, (_, k) in enumerate(pairs):
         print(f"first frame: E_{k} - E_0 = {E[0, k] - E[0, 0]:.6f} Ha, f_0{k} = "
               f"{float(oscillator_strength(E[0, 0], E[0, k], props['dipole'][0, i])):.6f}")
 t0 = time.time()
-frames = state_swarm([init], cont.one_rdm, cont.two_rdm, cont.overlap, root=a.root, dt=a.dt, steps=a.steps,
-                     integrals="device")
+frames = state_swarm([init], *arrays, root=a.root, dt=a.dt, steps=a.steps, integrals="device", **kw)
 wall = time.time() - t0
 for f in frames:
     r1 = np.linalg.norm(f["coord"][0, 1] - f["coord"][0, 0]) / ANGSTROM

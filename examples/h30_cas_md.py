@@ -12,7 +12,10 @@ usage: python examples/h30_cas_md.py [--small] [--steps 20] [--dt 5] [--iteratio
        --nroots R --root k [--spin-penalty 0.2] [--states 3]: R CASCI roots per training geometry at
        --states spacings around --spacing, then ``state_swarm`` on surface k with the integrals made on the device (the
        active-learning loop is for one root per geometry); the first frame prints the vertical excitation energies and
-       the oscillator strengths from the ground state"""
+       the oscillator strengths from the ground state
+       --resident: the training set grows on the device (``resident.ResidentCAS_EVCont_obj``): the
+       two-body rows are written in place in the evaluator's sym8 layout and every call below reads
+       ``cont.device_trdms()``"""
 import argparse
 import os
 import sys
@@ -39,14 +42,22 @@ p.add_argument("--nroots", type=int, default=1, help="CASCI roots per training g
 p.add_argument("--root", type=int, default=0, help="surface of the dynamics (0 = ground state)")
 p.add_argument("--spin-penalty", type=float, default=0.0, help="penalty on S^2 in the active-space solver")
 p.add_argument("--states", type=int, default=3, help="training geometries of the --nroots route")
+p.add_argument("--resident", action="store_true", help="keep the two-body rows on the device (ResidentCAS_EVCont_obj)")
 a = p.parse_args()
 if not 0 <= a.root < a.nroots:
     p.error(f"--root {a.root} needs --nroots of at least {a.root + 1}")
 
 natm, ncas, nact = (8, 4, 4) if a.small else (30, 10, 10)
 mol = hydrogen_chain(natm, a.spacing)
-cont = CAS_EVCont_obj(ncas, nact, cisolver=DeviceFCI(eigensolver="davidson", spin_penalty=a.spin_penalty),
-                      nroots=a.nroots)
+solver = DeviceFCI(eigensolver="davidson", spin_penalty=a.spin_penalty)
+if a.resident:
+    from evcont_amd.resident import ResidentCAS_EVCont_obj
+    cont = ResidentCAS_EVCont_obj(ncas, nact, cisolver=solver, nroots=a.nroots, layout="sym8")
+else:
+    cont = CAS_EVCont_obj(ncas, nact, cisolver=solver, nroots=a.nroots)
+# what the excited-state calls read: the host arrays, or the resident container's view
+data = lambda: ((cont.one_rdm, None, cont.overlap), dict(device_trdms=cont.device_trdms())) if a.resident else \
+    ((cont.one_rdm, cont.two_rdm, cont.overlap), {})
 if a.nroots > 1:
     from evcont_amd.MD_utils import state_swarm
     from evcont_amd.ab_initio_eigenvector_continuation import get_multistate_properties
@@ -57,12 +68,12 @@ if a.nroots > 1:
     print(f"H{natm} CAS({nact},{ncas}): {cont.ntrain} training states ({a.nroots} per geometry) in "
           f"{time.perf_counter() - t0:.1f} s")
     pairs = [(0, k) for k in range(1, a.nroots)]
-    E, props = get_multistate_properties([mol], cont.one_rdm, cont.two_rdm, cont.overlap, a.nroots, pairs)
+    arrays, kw = data()
+    E, props = get_multistate_properties([mol], *arrays, a.nroots, pairs, **kw)
     for i, (_, k) in enumerate(pairs):
         print(f"first frame: E_{k} - E_0 = {E[0, k] - E[0, 0]:.6f} Ha, f_0{k} = "
               f"{float(oscillator_strength(E[0, 0], E[0, k], props['dipole'][0, i])):.6f}")
-    frames = state_swarm([mol], cont.one_rdm, cont.two_rdm, cont.overlap, root=a.root, dt=a.dt, steps=a.steps,
-                         integrals="device")
+    frames = state_swarm([mol], *arrays, root=a.root, dt=a.dt, steps=a.steps, integrals="device", **kw)
     etot = np.array([f["epot"][0] + f["ekin"][0] for f in frames])
     print(f"{a.steps} NVE steps on root {a.root}: E_tot = {etot[0]:.10f}, drift {np.abs(etot - etot[0]).max():.2e} Ha")
     assert np.isfinite(etot).all()

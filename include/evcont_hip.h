@@ -52,7 +52,8 @@ extern "C" {
                                  additive: evc_spgto_workspace_bytes, evc_spgto_integrals_batch,
                                  evc_spgto_dipole_batch; additive: evc_spdgto_workspace_bytes,
                                  evc_spdgto_integrals_batch, evc_spdgto_dipole_batch; additive:
-                                 evc_fci_rotate_block, evc_fci_rotate_block_workspace_bytes */
+                                 evc_fci_rotate_block, evc_fci_rotate_block_workspace_bytes; additive:
+                                 evc_fci_trdm_rows_block, evc_fci_rows_block_workspace_bytes */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -461,6 +462,28 @@ int evc_fci_trdm_rows(int norb, int64_t na, int64_t nb, const int32_t *tab_a, co
                       size_t ws_bytes, void *stream);
 int evc_fci_sigma(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b, const double *h1,
                   const double *h2, const double *c, double *sigma, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * The block row call: nbras bras (1 ... 16) against shared kets.  `bras`, `kets` and `nkets_of` are HOST arrays, `bras`
+ * and `kets` of DEVICE pointers.  Bra r is taken against kets[0 .. nkets_of[r] - 1]; nkets_of must not decrease, each
+ * entry 1 ... 4096, and `kets` has nkets_of[nbras - 1] entries.  That covers the rectangular block (all counts equal)
+ * and the triangular one (T + 1, T + 2, ..., T + R) of a training-set append, where the bras are the last kets: a bra
+ * pointer may also be a ket pointer.
+ * Outputs are ragged and consecutive: row off_r + i for (bra r, ket i), off_r = sum of nkets_of[r' < r]; ovlp[row],
+ * dm1[row][norb^2] and dm2[row][norb^4] follow evc_fci_trdm_rows.  No output may overlap a bra or ket vector.
+ * The ket-side excitations D = E_pq ket of a determinant chunk are formed once for every bra that sees the ket (the
+ * bras are a dimension of the product's grid); determinant blocks, tilings and the order of the partial sums are those
+ * of evc_fci_trdm_rows, so row (r, i) has the bits of evc_fci_trdm_rows(bras[r], kets[:nkets_of[r]]) row i for every
+ * accepted workspace and every nbras.  evc_fci_trdm_rows is the nbras = 1 case of the same routine.
+ * evc_fci_rows_block_workspace_bytes(norb, na, nb, nbras, minimal): partial sums per bra, then with minimal = 0 the
+ *       bra-side D~ of all bras and one ket-side D resident, with minimal != 0 one determinant block of each; equal to
+ *       evc_fci_workspace_bytes for nbras = 1, not decreasing in nbras, 0 on an argument error.
+ * The stage EVC_PROF_FCI_TRDM records the single call's text followed by " bras=<nbras>".
+ * --------------------------------------------------------------------------------- */
+size_t evc_fci_rows_block_workspace_bytes(int norb, int64_t na, int64_t nb, int nbras, int minimal);
+int evc_fci_trdm_rows_block(int norb, int64_t na, int64_t nb, const int32_t *tab_a, const int32_t *tab_b,
+                            const double *const *bras, int nbras, const double *const *kets, const int *nkets_of,
+                            double *ovlp, double *dm1, double *dm2, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * The row call with its two-body results written in place into the (pairs, ld) DEVICE matrix the evaluator streams

@@ -2,7 +2,10 @@
 stored geometries (R G stored states, the new geometry's own roots included among the kets): the block call
 (``DeviceFCI.cas_trans_rdm12_block``: intermediates once per stored geometry, one ``evc_fci_rotate_block`` per geometry)
 against the loop of R ``DeviceFCI.cas_trans_rdm12_rows`` calls, which is what the parent of this change offers and runs
-unchanged there (the baseline).
+unchanged there (the baseline).  (Since DESIGN.md 8.1.7 ``cas_trans_rdm12_rows`` is the one-bra case of the block call and
+both routes make their row calls through ``evc_fci_trdm_rows_block``: the loop then forms its intermediates once per
+stored geometry and bra, and ``profiles/cas_roots_time.txt`` records the routes as they were when it was written;
+``tools/micro/cas_resident_time.py`` is the current record.)
 
 Both routes are split by wrapping their stages (host clock, the device synchronised at both ends of each): host
 intermediates (``cas_small.pair_intermediates``), rotate (``_rotate`` / ``_rotate_block``), row calls
@@ -57,6 +60,7 @@ class _TimedLib:
     def __init__(self, lib, stages):
         self._lib = lib
         self.evc_fci_trdm_rows = stages.timed("row calls", lib.evc_fci_trdm_rows)
+        self.evc_fci_trdm_rows_block = stages.timed("row calls", lib.evc_fci_trdm_rows_block)
         self.evc_cas_expand_rows = stages.timed("expand", lib.evc_cas_expand_rows)
 
     def __getattr__(self, name):

@@ -3,8 +3,9 @@ t-RDM row of the new state against all T, on the device route (``DeviceFCI.cas_t
 statement (``cas_small.trans_rdm12_rows`` with ``fci_small``) on the same machine, with the same states.
 
 The device route is split by a subclass that wraps its stages (host clock, the device synchronised at both ends of each):
-host intermediates (``cas_small.pair_intermediates``, T pairs), rotate (T ``evc_fci_rotate`` calls), row call (one
-``evc_fci_trdm_rows``), expand (one ``evc_cas_expand_rows``, dense layout), and the rest (uploads, the dense (T, N^4) rows
+host intermediates (``cas_small.pair_intermediates``, one per stored geometry), rotate (one ``evc_fci_rotate_block`` per
+stored geometry; T ``evc_fci_rotate`` calls when ``profiles/cas_append_time.txt`` was written), row call (one
+``evc_fci_trdm_rows_block`` with one bra, the single call's routine), expand (one ``evc_cas_expand_rows``, dense layout), and the rest (uploads, the dense (T, N^4) rows
 to the host).  The states are solved once (RHF + CASCI at T geometries of the chain, spacing 1.8 + 0.01 k), outside the
 timed region; the first call of each route at each T is a warm-up, the second is timed.  A record, not a pass/fail ratio.
 
@@ -50,6 +51,7 @@ class _TimedLib:
     def __init__(self, lib, stages):
         self._lib = lib
         self.evc_fci_trdm_rows = stages.timed("row call", lib.evc_fci_trdm_rows)
+        self.evc_fci_trdm_rows_block = stages.timed("row call", lib.evc_fci_trdm_rows_block)
         self.evc_cas_expand_rows = stages.timed("expand", lib.evc_cas_expand_rows)
 
     def __getattr__(self, name):
@@ -61,6 +63,9 @@ class TimedFCI(DeviceFCI):
 
     def _rotate(self, *a):
         return self.stages.timed("rotate", super()._rotate)(*a)
+
+    def _rotate_block(self, *a):
+        return self.stages.timed("rotate", super()._rotate_block)(*a)
 
     def _setup(self, norb, nelec):
         out = super()._setup(norb, nelec)
