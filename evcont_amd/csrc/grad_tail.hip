@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "small_mm.hpp"
+#include "unpack_tiles.hpp"
 
 namespace evc {
 
@@ -184,36 +185,22 @@ __device__ __forceinline__ void grad_prep_body(GradPrepArgs a, int64_t g) {
 __global__ __launch_bounds__(kThreads) void grad_prep_kernel(GradPrepArgs a) { grad_prep_body(a, blockIdx.x); }
 
 // The same launch ALSO unpacks the packed predicted 2-RDM of the compressed layout into the dense symmetric (pair, pair)
-// matrix SB (pack.hip unpack8_pairs_kernel: SB[u][v] = 4 p[tri(max, min)], one wave per row u, four rows per workgroup):
-// both only need what K8 has just written, so the `count` workgroups of the one and the count * ceil(npairs / 4)
+// matrix SB (SB[u][v] = 4 p[tri(max, min)], the mirrored-tile copy of unpack_tiles.hpp, as pack.hip unpack8_pairs_kernel):
+// both only need what K8 has just written, so the `count` workgroups of the one and the count * unpack_tile_count(npairs)
 // workgroups of the other share a launch instead of following each other (one kernel boundary and the shorter of the
-// two durations less on the critical path of a step).  Blocks [0, count): grad_prep; the rest: unpack.
+// two durations less on the critical path of a step).  Blocks [0, count): grad_prep; the rest: unpack, one tile each, its
+// LDS tile inside the LDS that every block of the launch reserves for grad_prep.
 __global__ __launch_bounds__(kThreads) void unpack8_prep_kernel(GradPrepArgs a, const double *__restrict__ p, int64_t sp,
                                                                 double *__restrict__ SB, int64_t sws, int count, int ld) {
     if ((int)blockIdx.x < count) {
         grad_prep_body(a, blockIdx.x);
         return;
     }
-    const int n = a.n, npairs = n * (n + 1) / 2, bpg = (npairs + 3) / 4;
-    const int b = (int)blockIdx.x - count;
-    // (blocks of eight consecutive geometries interleaved: each XCD works through one geometry's packed vector at a time)
-    const int nx = count & ~7;
+    extern __shared__ __align__(16) double sm[];
+    const int n = a.n, npairs = n * (n + 1) / 2;
     int geom, blk;
-    if (b < nx * bpg) {
-        const int xcd = b & 7, slot = b >> 3;
-        geom = (slot / bpg) * 8 + xcd;
-        blk = slot % bpg;
-    } else {
-        const int r = b - nx * bpg;
-        geom = nx + r / bpg;
-        blk = r % bpg;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int u = blk * 4 + wave;
-    if (u >= npairs) return;
-    p += (int64_t)geom * sp;
-    double *sb = SB + (int64_t)geom * sws + (int64_t)u * ld;
-    for (int v = lane; v < npairs; v += 64) sb[v] = 4.0 * (u >= v ? p[tri_index(u, v)] : p[tri_index(v, u)]);
+    unpack_tile_geom((int64_t)blockIdx.x - count, count, unpack_tile_count(npairs), geom, blk);
+    unpack8_tile(p + (int64_t)geom * sp, SB + (int64_t)geom * sws, npairs, ld, blk, sm);
 }
 
 static size_t grad_prep_lds(int n) {
@@ -222,10 +209,11 @@ static size_t grad_prep_lds(int n) {
 
 int launch_unpack8_prep(const GradPrepArgs &a, const double *packed, int64_t sp, double *SB, int64_t sws, int count,
                         hipStream_t st) {
-    const int npairs = a.n * (a.n + 1) / 2, bpg = (npairs + 3) / 4;
+    const int npairs = a.n * (a.n + 1) / 2, bpg = unpack_tile_count(npairs);
+    const size_t lds = grad_prep_lds(a.n) > kUtLds ? grad_prep_lds(a.n) : kUtLds;   // (grad_prep's, at every n)
     static LdsAttr attr;
     if (int rc = allow_dynamic_lds(unpack8_prep_kernel, attr, 160 * 1024, "unpack8_prep")) return rc;
-    hipLaunchKernelGGL(unpack8_prep_kernel, dim3((unsigned)(count + bpg * count)), dim3(kThreads), grad_prep_lds(a.n), st, a,
+    hipLaunchKernelGGL(unpack8_prep_kernel, dim3((unsigned)(count + bpg * count)), dim3(kThreads), lds, st, a,
                        packed, sp, SB, sws, count, pair_ld(a.n));
     EVC_LAUNCH_CHECK("unpack8_prep");
     note_kernel(EVC_PROF_UNPACK, "unpack8_prep_kernel");

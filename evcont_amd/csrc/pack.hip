@@ -6,6 +6,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "unpack_tiles.hpp"
 
 namespace evc {
 
@@ -221,36 +222,22 @@ __global__ __launch_bounds__(256) void unpack8_kernel(const double *__restrict__
 }
 
 // Dense (pair, pair) form of the same (lead_half = 2, no G): SB[u][v] = 4 p8[tri(max(u,v), min(u,v))], u = tri(i,j), v = tri(k,l) -- the
-// symmetric matrix the compressed vector is the lower triangle of.  One wave per row u.
+// symmetric matrix the compressed vector is the lower triangle of, rows at the pitch pair_ld(n) of the pipeline's dense
+// forms.  The mirrored-tile copy of unpack_tiles.hpp.
 __global__ __launch_bounds__(256) void unpack8_pairs_kernel(const double *__restrict__ p, int64_t sp, int n,
                                                             double *__restrict__ SB, int64_t sws, int count, int ld) {
+    extern __shared__ __align__(16) double ut_lds[];
     const int npairs = n * (n + 1) / 2;
-    const int bpg = (npairs + 3) / 4;   // workgroups per geometry
-    const int nx = count & ~7;
-    const int64_t nxblocks = (int64_t)nx * bpg;
     int geom, blk;
-    if ((int64_t)blockIdx.x < nxblocks) {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        geom = (slot / bpg) * 8 + xcd;
-        blk = slot % bpg;
-    } else {
-        const int64_t b = (int64_t)blockIdx.x - nxblocks;
-        geom = nx + (int)(b / bpg);
-        blk = (int)(b % bpg);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int u = blk * 4 + wave;
-    if (u >= npairs) return;
-    p += (int64_t)geom * sp;
-    double *sb = SB + (int64_t)geom * sws + (int64_t)u * ld;   // (rows at the pitch pair_ld(n) of the pipeline's dense forms)
-    for (int v = lane; v < npairs; v += 64) sb[v] = 4.0 * (u >= v ? p[tri_index(u, v)] : p[tri_index(v, u)]);
+    unpack_tile_geom(blockIdx.x, count, unpack_tile_count(npairs), geom, blk);
+    unpack8_tile(p + (int64_t)geom * sp, SB + (int64_t)geom * sws, npairs, ld, blk, ut_lds);
 }
 
 int launch_unpack8(const double *packed, int64_t sp, int n, double *SB, int64_t sws, double *G, int64_t sG, int count,
                    int lead_half, hipStream_t st) {
     if (lead_half == 2 && !G) {
-        const int bpg = (n * (n + 1) / 2 + 3) / 4;
-        hipLaunchKernelGGL(unpack8_pairs_kernel, dim3((unsigned)(bpg * count)), dim3(256), 0, st, packed, sp, n, SB,
+        const int bpg = unpack_tile_count(n * (n + 1) / 2);
+        hipLaunchKernelGGL(unpack8_pairs_kernel, dim3((unsigned)(bpg * count)), dim3(256), kUtLds, st, packed, sp, n, SB,
                            sws, count, pair_ld(n));
         EVC_LAUNCH_CHECK("unpack8_pairs");
         note_kernel(EVC_PROF_UNPACK, "unpack8_pairs_kernel");
