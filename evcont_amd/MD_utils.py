@@ -325,18 +325,10 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
                  data_addition=data_addition, **kwargs)
 
 
-def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=(), device_trdms=None):
-    """``evaluate(R (G,A,3)) -> (E (G,nroots), grads (G,nroots,A,3))`` for geometries of the s-Gaussian molecule of
-    ``mols``, device-resident from the coordinates on: the training set and the batched evaluator are built once, every
-    call uploads the coordinates, computes the AO integrals there (``hchain_device.DeviceSGaussians``, or
-    ``gto_device.DeviceGaussians`` for a molecule with ``shells``, ``gto_spd_device.DeviceSpdGaussians`` when the
-    shells contain l = 2) and runs the
-    batched several-roots call on them.  With ``observables``: ``(E, grads (G,1,A,3), props)`` of the highest root alone,
-    forces and observables from one solve (``BatchedEvaluator.multistate_properties``)."""
-    from .ab_initio_eigenvector_continuation import resolve_compression
-    from .ab_initio_gradients_loewdin import _batched_evaluator
-    mol0, G = mols[0], len(mols)
-    # molecules of s and p shells (gto_small.GaussianMol) and of one s function per centre (hchain.HChainMol)
+def _device_producer(mol0):
+    """The device integral producer class of an array-level molecule: molecules of s and p shells
+    (gto_small.GaussianMol), of s, p and d shells (gto_spd.SpdGaussianMol) and of one s function per centre
+    (hchain.HChainMol)."""
     if getattr(mol0, "shells", None) is not None and hasattr(mol0, "charges"):
         if any(sh.l == 2 for atom in mol0.shells for sh in atom):
             # d shells (gto_spd.SpdGaussianMol): the general route, csrc/spdgto.hip
@@ -347,6 +339,24 @@ def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=(), de
         from .hchain_device import DeviceSGaussians as producer
     else:
         raise ValueError('integrals="device" needs s-Gaussian molecules (evcont_amd.hchain.HChainMol)')
+    return producer
+
+
+def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=(), device_trdms=None,
+                     field_origin=(0.0, 0.0, 0.0)):
+    """``evaluate(R (G,A,3)) -> (E (G,nroots), grads (G,nroots,A,3))`` for geometries of the s-Gaussian molecule of
+    ``mols``, device-resident from the coordinates on: the training set and the batched evaluator are built once, every
+    call uploads the coordinates, computes the AO integrals there (``hchain_device.DeviceSGaussians``, or
+    ``gto_device.DeviceGaussians`` for a molecule with ``shells``, ``gto_spd_device.DeviceSpdGaussians`` when the
+    shells contain l = 2) and runs the
+    batched several-roots call on them.  With ``observables``: ``(E, grads (G,1,A,3), props)`` of the highest root alone,
+    forces and observables from one solve (``BatchedEvaluator.multistate_properties``).  ``evaluate(R, field)``: the
+    geometries in the uniform electric fields ``field`` ((3,) or (G,3)) with the origin ``field_origin``, folded into the
+    integrals on the device (``integrals(..., field=)`` of the producer)."""
+    from .ab_initio_eigenvector_continuation import resolve_compression
+    from .ab_initio_gradients_loewdin import _batched_evaluator
+    mol0, G = mols[0], len(mols)
+    producer = _device_producer(mol0)
     if G * nroots > 4096:
         raise ValueError(f"{G} trajectories x {nroots} roots exceed the 4096 slots of one call")
     t = device_trdms if device_trdms is not None else _resident_trdms(
@@ -357,8 +367,9 @@ def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=(), de
     sg = producer.from_mol(mol0, device=t.device)
     packed = t.layout == _lib.LAYOUT_SYM8 and t.n <= 64
 
-    def evaluate(R):
-        aob = sg.integrals(R, packed=packed)
+    def evaluate(R, field=None):
+        aob = sg.integrals(R, packed=packed) if field is None else \
+            sg.integrals(R, packed=packed, field=field, origin=field_origin)
         if not observables:
             E, _, grads = ev.multistate_energies_with_grads(aob, nroots)
             return E, grads
@@ -378,7 +389,7 @@ _OBSERVABLES = {"dipole": "dipole", "mulliken": "mulliken_charges", "loewdin": "
 
 
 def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_veloc=None, integrals="host",
-                observables=None, device_trdms=None):
+                observables=None, device_trdms=None, field=None, field_origin=(0.0, 0.0, 0.0)):
     """Velocity-Verlet NVE of G trajectories on the continuation surface ``root`` (0 = ground state), advanced in lock
     step: every step is ONE batched call for all G geometries (``get_multistate_energies_with_grads``, all trajectories'
     roots 0 .. root in one pass).  ``mols``: the G initial geometries of one array-level molecule that can be rebuilt at
@@ -396,7 +407,12 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
     ``integrals="device"`` that adds the observables' G (3 + A) doubles per kind of charge to the step's download and
     no upload.
     ``device_trdms``: as for ``get_scanner`` (training data already on the device, e.g. a resident container's
-    ``device_trdms()``; the host arrays may then be ``None``)."""
+    ``device_trdms()``; the host arrays may then be ``None``).
+    ``field``: None, or a uniform electric field in atomic units, (3,) for all trajectories or (G,3), or a callable
+    ``time -> `` either (a pulse); ``field_origin``: the origin of the dipole operator.  ``mols`` are then the field-free
+    molecules; every step's geometries are put into the field of the step's time (``with_field`` on the host route,
+    ``integrals(..., field=)`` of the device producer on the device route), ``epot`` of a frame includes the field
+    terms, and a static field conserves ``epot + ekin``."""
     from .ab_initio_gradients_loewdin import get_multistate_energies_with_grads
     mols = list(mols)
     root = int(root)
@@ -414,19 +430,31 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
     # frame key -> (G, ...) array of the propagated root
     observed = lambda props: {_OBSERVABLES[k]: props[_OBSERVABLES[k]][:, 0] for k in observables}
 
-    if integrals == "device":
-        surfaces = _device_surfaces(mols, one_rdm, two_rdm, overlap, root + 1, observables, device_trdms)
+    def field_at(time):
+        """(G,3) fields of the step at ``time``, or None."""
+        if field is None:
+            return None
+        F = np.asarray(field(time) if callable(field) else field, dtype=np.float64)
+        return np.ascontiguousarray(np.broadcast_to(F.reshape(1, 3), (len(mols), 3)) if F.size == 3
+                                    else F.reshape(len(mols), 3))
 
-        def evaluate(ms):
+    if integrals == "device":
+        surfaces = _device_surfaces(mols, one_rdm, two_rdm, overlap, root + 1, observables, device_trdms, field_origin)
+
+        def evaluate(ms, time):
+            F = field_at(time)
             if observables:
-                E, grads, props = surfaces(R)
+                E, grads, props = surfaces(R, F)
                 return E[:, root], grads[:, 0], observed(props)
-            E, grads = surfaces(R)
+            E, grads = surfaces(R, F)
             return E[:, root], grads[:, root], {}
 
         rebuild = lambda ms, R: ms
     else:
-        def evaluate(ms):
+        def evaluate(ms, time):
+            F = field_at(time)
+            if F is not None:
+                ms = [m_.with_field(f, field_origin) for m_, f in zip(ms, F)]
             if observables:
                 from .ab_initio_eigenvector_continuation import get_multistate_properties
                 E, props = get_multistate_properties(ms, one_rdm, two_rdm, overlap, root + 1, [(root, root)],
@@ -438,7 +466,7 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
 
         rebuild = lambda ms, R: [m_.with_coords(r) for m_, r in zip(ms, R)]
 
-    e, g, obs = evaluate(mols)
+    e, g, obs = evaluate(mols, 0.0)
     frames = []
     for k in range(steps):
         frames.append({"coord": R.copy(), "veloc": v.copy(), "epot": e.copy(),
@@ -448,6 +476,6 @@ def state_swarm(mols, one_rdm, two_rdm, overlap, root, dt=10.0, steps=10, init_v
         a = -g / m
         R = _vv_drift(R, v, a, dt)
         mols = rebuild(mols, R)
-        e, g, obs = evaluate(mols)
+        e, g, obs = evaluate(mols, (k + 1) * dt)
         v = _vv_kick(v, a, g, m, dt)
     return frames

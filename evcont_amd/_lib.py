@@ -196,6 +196,13 @@ SIGNATURES = {
     "evc_properties_roots_batch": (C.c_int, [C.POINTER(TrdmSet), C.POINTER(PropertyInputs), C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_int, C.POINTER(PropertyOutputs), C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_sgto_dipole_grad_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "evc_gto_dipole_grad_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "evc_field_fold_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "evc_profile_begin": (C.c_int, [C.c_int]),
     "evc_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int)]),

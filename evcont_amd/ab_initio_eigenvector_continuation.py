@@ -324,3 +324,76 @@ def get_multistate_properties(mols, one_rdm, two_rdm, overlap, nroots=1, pairs=N
     if need_grad:
         out["grads"] = np.concatenate(grads)
     return np.concatenate(E), out
+
+
+def field_points(step) -> np.ndarray:
+    """The seven fields of ``get_multistate_field_response``: 0, then ``+step`` and ``-step`` along x, y and z."""
+    F = np.zeros((7, 3))
+    for c in range(3):
+        F[1 + 2 * c, c], F[2 + 2 * c, c] = float(step), -float(step)
+    return F
+
+
+def field_response_from_points(E, dip, grads, step) -> dict:
+    """The result of ``get_multistate_field_response`` from the energies (7,R), dipoles (7,R,3) and gradients (7,R,A,3)
+    at ``field_points(step)``: first central differences of the dipoles and of the forces."""
+    E, dip, grads, h = np.asarray(E), np.asarray(dip), np.asarray(grads), float(step)
+    alpha = np.stack([(dip[1 + 2 * c] - dip[2 + 2 * c]) / (2.0 * h) for c in range(3)], axis=-1)       # (R,3 mu,3 F)
+    apt = np.stack([-(grads[1 + 2 * c] - grads[2 + 2 * c]) / (2.0 * h) for c in range(3)], axis=-1)    # (R,A,3 x,3 c)
+    return {"energies": np.array(E[0]), "dipole": np.array(dip[0]), "polarizability": alpha, "apt": apt}
+
+
+def get_multistate_field_response(mol, one_rdm, two_rdm, S, nroots, step, origin=(0.0, 0.0, 0.0), integrals="host",
+                                  device_trdms=None):
+    """Dipole, polarisability and atomic polar tensor of the lowest ``nroots`` continuation states of ``mol`` (an
+    array-level molecule with ``with_field``: ``hchain.HChainMol``, ``gto_small.GaussianMol``,
+    ``gto_spd.SpdGaussianMol``) by finite uniform fields: ONE batched ``multistate_properties(..., return_forces=True)``
+    call over seven field points, ``F = 0`` and ``+-step e_x, +-step e_y, +-step e_z`` (atomic units) at the same
+    coordinates.  Returns a dict, ``R = nroots``, ``A`` atoms:
+
+        energies        (R,)       at zero field
+        dipole          (R,3)      the zero-field dipole, taken directly (atomic units, ``origin``)
+        polarizability  (R,3,3)    alpha[i,j] = d mu_i / dF_j, central differences of the DIPOLES
+        apt             (R,A,3,3)  P[A,x,c] = d mu_c / dR_Ax = - d(grad_Ax) / dF_c, central differences of the FORCES
+
+    Both are first differences of quantities the chain gives to ~1e-13; second differences of the energy would lose
+    ``step``^-2 of that and are not used.  ``integrals``: "host" builds the seven molecules with ``with_field`` (numpy);
+    "device" computes the integrals from the coordinates on the device and folds the fields there
+    (``integrals(..., field=)`` of the device producers, ``csrc/field.hip``).  ``device_trdms``: as for
+    ``get_multistate_properties``.
+
+    Degeneracy warning (as for every several-roots call): the seven field points are seven independent solves; at
+    (near-)degenerate roots they need not return the same state, or the same mixture within a degenerate space, and the
+    differences between them are then meaningless for those roots."""
+    nroots, h = int(nroots), float(step)
+    if not h > 0.0:
+        raise ValueError(f"step={step} must be positive")
+    if integrals not in ("host", "device"):
+        raise ValueError(f"unknown integrals={integrals!r} (known: 'host', 'device')")
+    origin = tuple(float(x) for x in origin)
+    F = field_points(h)
+    pairs = [(k, k) for k in range(nroots)]
+    if integrals == "host":
+        base = mol if getattr(mol, "field", None) is None else mol.with_field((0.0, 0.0, 0.0))
+        mols = [base] + [base.with_field(f, origin) for f in F[1:]]
+        E, out = get_multistate_properties(mols, one_rdm, two_rdm, S, nroots, pairs, origin=origin, return_forces=True,
+                                           device_trdms=device_trdms)
+        dip, grads = out["dipole"], out["grads"]
+    else:
+        from . import _lib
+        from .ab_initio_gradients_loewdin import _batched_evaluator
+        from .MD_utils import _device_producer
+        if 7 * nroots > 4096:
+            raise ValueError(f"{nroots} roots at seven field points exceed the 4096 slots of one call")
+        t = device_trdms if device_trdms is not None else _resident_trdms(
+            one_rdm, two_rdm, S, resolve_compression("default", one_rdm, two_rdm, S, ao_arrays(mol, need_grad=True)))
+        natm = int(np.asarray(mol.charges).shape[0])
+        sg = _device_producer(mol).from_mol(mol, device=t.device)
+        R = np.repeat(np.asarray(mol.coords, dtype=np.float64).reshape(1, natm, 3), 7, axis=0)
+        aob = sg.integrals(R, packed=t.layout == _lib.LAYOUT_SYM8 and t.n <= 64, field=F, origin=origin)
+        Rd = sg.staged_coords(7)
+        E, _, props, grads = _batched_evaluator(t, natm, 7).multistate_properties(
+            aob, nroots, pairs, dip=sg.dipole_integrals(Rd, origin), charges=sg.charges, coords=Rd, origin=origin,
+            return_forces=True, observables=("dipole",))
+        dip = props["dipole"]
+    return field_response_from_points(E, dip, grads, h)

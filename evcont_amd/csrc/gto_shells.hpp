@@ -60,6 +60,33 @@ GTO_HD int gto_tri_row(int m) {
     return r;
 }
 
+// ---- monomials of a function of s, p and real spherical d shells (spdgto.hip, field.hip) -----------------------
+// kind: 0: s; 1, 2, 3: p_x, p_y, p_z; 4 ... 8: d_xy, d_yz, d_z2, d_xz, d_x2-y2
+GTO_HD int spd_nmono(int kind) { return kind == 6 ? 3 : (kind == 8 ? 2 : 1); }
+
+// Powers (i0, i1, i2) of x, y, z and weight of monomial k of a function of `kind`, for primitives normalised as
+// x y exp(-a r^2): 2 z^2 - x^2 - y^2 carries 1 / sqrt(12), x^2 - y^2 carries 1 / 2.
+GTO_HD void spd_mono(int kind, int k, int &i0, int &i1, int &i2, double &w) {
+    // 6 bits per kind: power of x | power of y << 2 | power of z << 4, of the first monomial
+    constexpr uint64_t first = (1ull << 6) | (4ull << 12) | (16ull << 18) | (5ull << 24) | (20ull << 30) | (32ull << 36) |
+                               (17ull << 42) | (2ull << 48);
+    int code = (int)(first >> (6 * kind)) & 63;
+    w = 1.0;
+    if (kind == 6) {
+        code = k == 0 ? 32 : (k == 1 ? 2 : 8);
+        w = k == 0 ? 0.57735026918962576 : -0.28867513459481288;
+    }
+    if (kind == 8) {
+        code = k == 0 ? 2 : 8;
+        w = k == 0 ? 0.5 : -0.5;
+    }
+    i0 = code & 3;
+    i1 = (code >> 2) & 3;
+    i2 = (code >> 4) & 3;
+}
+
+GTO_HD double spd_sel3(int i, double v0, double v1, double v2) { return i == 0 ? v0 : (i == 1 ? v1 : v2); }
+
 // ---- Boys functions ------------------------------------------------------------------------
 // Eight more terms of the series of F_L from term K0 on, and eight more while they still count.
 template <int L, int K0>

@@ -29,7 +29,7 @@
 // The basis is a HOST argument and reaches the kernels by value.
 // What lives where: as in spgto.hip.  gto_shells.hpp holds what the two routes share (limits, GtoPrims, gto_boys, gto_raise,
 // gto_conv, gto_dot, gto_overlap_kinetic, the pair-table body, the whole host side), told about this route by SpdRoute at
-// the end of the file.  Here: the monomials, the maths of the powers 0 ... 2 (spd_bra_dim, spd_ket_dim, spd_fold, spd_poly,
+// the end of the file, and the monomials of the d functions (spd_mono, also read by field.hip).  Here: the maths of the powers 0 ... 2 (spd_bra_dim, spd_ket_dim, spd_fold, spd_poly,
 // spd_os_table, spd_st_dim, the one / two / dipole bodies) and the kernels.
 #include "gto_shells.hpp"
 
@@ -43,31 +43,7 @@ struct SpdAos {
     uint8_t atom[kGtoMaxAo];
 };
 
-// ---- monomials of a function ---------------------------------------------------------------
-GTO_HD int spd_nmono(int kind) { return kind == 6 ? 3 : (kind == 8 ? 2 : 1); }
-
-// Powers (i0, i1, i2) of x, y, z and weight of monomial k of a function of `kind`, for primitives normalised as
-// x y exp(-a r^2): 2 z^2 - x^2 - y^2 carries 1 / sqrt(12), x^2 - y^2 carries 1 / 2.
-GTO_HD void spd_mono(int kind, int k, int &i0, int &i1, int &i2, double &w) {
-    // 6 bits per kind: power of x | power of y << 2 | power of z << 4, of the first monomial
-    constexpr uint64_t first = (1ull << 6) | (4ull << 12) | (16ull << 18) | (5ull << 24) | (20ull << 30) | (32ull << 36) |
-                               (17ull << 42) | (2ull << 48);
-    int code = (int)(first >> (6 * kind)) & 63;
-    w = 1.0;
-    if (kind == 6) {
-        code = k == 0 ? 32 : (k == 1 ? 2 : 8);
-        w = k == 0 ? 0.57735026918962576 : -0.28867513459481288;
-    }
-    if (kind == 8) {
-        code = k == 0 ? 2 : 8;
-        w = k == 0 ? 0.5 : -0.5;
-    }
-    i0 = code & 3;
-    i1 = (code >> 2) & 3;
-    i2 = (code >> 4) & 3;
-}
-
-GTO_HD double spd_sel3(int i, double v0, double v1, double v2) { return i == 0 ? v0 : (i == 1 ? v1 : v2); }
+// (the monomials of a function, spd_nmono / spd_mono, and the select spd_sel3: gto_shells.hpp, shared with field.hip)
 
 // ---- Hermite coefficients of one dimension ---------------------------------------------------
 // Hermite coefficients (t <= 5) of one dimension of a primitive pair with the powers i, j (0 ... 2), without the

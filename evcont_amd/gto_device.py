@@ -20,12 +20,13 @@ import torch
 
 from . import _lib
 from .evaluator import DeviceAOBatch, F64, _dev
+from .field_device import FieldProducer
 from .gto_small import contraction_coefficients, flatten_shells
 
 _FIELDS = ("enuc", "S", "hcore", "eri", "ipovlp", "dhcore", "eri_ip1", "gnuc")
 
 
-class DeviceGaussians:
+class DeviceGaussians(FieldProducer):
     """``shells``: per atom a list of ``gto_small.Shell``; ``charges``: the nuclear charges; ``renormalize``: scale every
     contracted function to unit self-overlap (on the host, once), as ``sp_gaussian_mol`` does."""
 
@@ -51,6 +52,8 @@ class DeviceGaussians:
         self._buffers = {}         # (G, need_grad, packed) -> dict of output tensors
         self._coords = {}          # G -> device (G,A,3) staging of host coordinates
         self._dip = {}             # G -> device (G,3,N,N) dipole integrals
+        self._ipdip = {}           # G -> device (G,3,3,N,N) their gradient (field_device.FieldProducer)
+        self._field = {}           # G -> device (G,3) staging of host fields
         self._ws = None
 
     @classmethod
@@ -120,11 +123,25 @@ class DeviceGaussians:
             dip.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream), self._DIPOLE)
         return dip
 
-    def integrals(self, coords, need_grad: bool = True, packed: bool = False, out: Optional[dict] = None) -> DeviceAOBatch:
+    def _nao_now(self) -> int:
+        return self.nao
+
+    def _ipdip_call(self, R, G, origin, ipdip) -> None:
+        """One general kernel for l <= 2 serves this class and ``DeviceSpdGaussians``."""
+        _lib.check(self.lib.evc_gto_dipole_grad_batch(
+            self.natm, int(self.shell_l.shape[0]), G, R.data_ptr(), *self._basis_args(), origin, ipdip.data_ptr(),
+            torch.cuda.current_stream(self.device).cuda_stream), "evc_gto_dipole_grad_batch")
+
+    def integrals(self, coords, need_grad: bool = True, packed: bool = False, out: Optional[dict] = None, field=None,
+                  origin=(0.0, 0.0, 0.0)) -> DeviceAOBatch:
         """The integrals at ``coords`` ((G,A,3) or (A,3), Bohr; numpy or a device tensor), enqueued on the current
         stream of the device.  ``packed``: ``eri`` as the dense (Ms,Ms) s4 matrix and ``eri_ip1`` packed in its last two
         indices (s2kl), what evaluators on the compressed layout read.  ``out``: a dict of tensors as ``allocate``
-        returns to write into, instead of the buffers this object keeps for the shape."""
+        returns to write into, instead of the buffers this object keeps for the shape.
+        ``field``: None, or a uniform electric field ((3,) or one per geometry (G,3), atomic units; numpy or a device
+        tensor) with the dipole operator's ``origin``: behind the integrals the call then enqueues the dipole integrals,
+        their gradient (with ``need_grad``) and the fold of the field into ``hcore``, ``dhcore``, ``enuc`` and ``gnuc``
+        (``evc_field_fold_batch``).  Without a field nothing more than the integrals is enqueued."""
         R = self._device_coords(coords)
         G, A = int(R.shape[0]), self.natm
         need_grad, packed = bool(need_grad), bool(packed)
@@ -146,6 +163,8 @@ class DeviceGaussians:
             A, nshell, G, R.data_ptr(), self._charges.data_ptr(), *self._basis_args(), C.byref(cs), flags,
             self._ws.data_ptr(), int(self._ws.numel()), torch.cuda.current_stream(self.device).cuda_stream),
             self._INTEGRALS)
+        if field is not None:
+            self._fold_field(R, out, need_grad, field, origin)
         return DeviceAOBatch(S=out["S"], hcore=out["hcore"], eri=out["eri"], enuc=out["enuc"], natm=A,
                              ipovlp=out.get("ipovlp"), dhcore=out.get("dhcore"), eri_ip1=out.get("eri_ip1"),
                              gnuc=out.get("gnuc"), aoslices=self._aoslices, ip1_s2kl=packed and need_grad,

@@ -201,6 +201,8 @@ class GaussianMol(AOArrays):
     charges: Optional[np.ndarray] = None
     shells: Optional[list] = None         # per atom: list of Shell
     renormalize: bool = True
+    field: Optional[np.ndarray] = None    # (3,) the uniform electric field the arrays carry (``with_field``)
+    field_origin: Tuple[float, float, float] = (0.0, 0.0, 0.0)
 
     def energy_nuc(self) -> float:
         return float(self.enuc)
@@ -219,8 +221,22 @@ class GaussianMol(AOArrays):
         return np.array(out)
 
     def with_coords(self, coords, need_grad: bool = True) -> "GaussianMol":
-        """The same molecule (basis, charges, electrons) at new nuclear positions (Bohr)."""
-        return sp_gaussian_mol(coords, self.charges, self.shells, need_grad, self.nelec, self.renormalize)
+        """The same molecule (basis, charges, electrons, field) at new nuclear positions (Bohr)."""
+        from .field import keep_field
+        return keep_field(self, sp_gaussian_mol(coords, self.charges, self.shells, need_grad, self.nelec,
+                                                self.renormalize))
+
+    def with_field(self, F, origin=(0.0, 0.0, 0.0)) -> "GaussianMol":
+        """A copy in the uniform electric field ``F`` (3,) (``evcont_amd.field.with_field``)."""
+        from .field import with_field
+        return with_field(self, F, origin)
+
+    def dipole_grad_integrals(self, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """``ipdip[x,c,mu,nu] = <d_x mu| r_c - origin_c |nu>`` (3,3,N,N): the electron-coordinate gradient on the bra
+        (the convention of ``ipovlp``), so ``d dip_c[mu,nu] / dR_Ax = -ipdip[x,c,mu,nu] [mu in A] - ipdip[x,c,nu,mu]
+        [nu in A]``."""
+        pr = _Primitives(self.coords, self.shells, self.renormalize)
+        return dipole_grad_from_primitives(pr, pr.pair_E(3, 1), origin)
 
     def dipole_integrals(self, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
         """AO dipole integrals ``<mu| r - origin |nu>`` (3,N,N) (PySCF: ``int1e_r`` under ``with_common_orig``)."""
@@ -289,6 +305,28 @@ class _Primitives:
         """d/dA_d of a pair quantity given as ``f(di)`` (the first function's power in dimension d shifted by di):
         ``2a f(+1) - l f(-1)``."""
         return 2.0 * self.a[:, None] * f(1) - self.pw[:, d][:, None] * f(-1)
+
+
+def dipole_grad_from_primitives(pr, E, origin) -> np.ndarray:
+    """``<d_x mu| r_c - O_c |nu>`` (3,3,N,N) from the primitive functions ``pr`` (this module's ``_Primitives`` or
+    ``gto_spd``'s) and their ``pair_E(l + 2, l)``: the bra derivative ``2a E^{i+1,j} - i E^{i-1,j}`` in dimension x of
+    the dipole factor ``(x - O) = (x - A) + (A - O)``, one more power on the first function, in dimension c."""
+    O = np.asarray(origin, dtype=np.float64).reshape(3)
+    root = np.sqrt(np.pi / pr.p)
+    # one dimension of the overlap / of the dipole integral with the first function's power shifted by k
+    s = lambda d, k: pr.pick(E, d, k, 0)[0] * root
+    r = lambda d, k: pr.pick(E, d, k + 1, 0)[0] * root + (pr.ctr[:, None, d] - O[d]) * s(d, k)
+    out = np.zeros((3, 3, pr.nao, pr.nao))
+    for x in range(3):
+        for c in range(3):
+            def f(k):
+                val = 1.0
+                for d in range(3):
+                    kd = k if d == x else 0
+                    val = val * (r(d, kd) if d == c else s(d, kd))
+                return val
+            out[x, c] = -pr.contract2(pr.center_derivative(f, x))    # electron gradient = - centre gradient
+    return out
 
 
 def sp_gaussian_mol(coords, charges, shells, need_grad: bool = True, nelec: Optional[Tuple[int, int]] = None,

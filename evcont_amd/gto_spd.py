@@ -193,12 +193,18 @@ class SpdGaussianMol(GaussianMol):
     ``Shell``)."""
 
     def with_coords(self, coords, need_grad: bool = True) -> "SpdGaussianMol":
-        """The same molecule (basis, charges, electrons) at new nuclear positions (Bohr)."""
-        return spd_gaussian_mol(coords, self.charges, self.shells, need_grad, self.nelec, self.renormalize)
+        """The same molecule (basis, charges, electrons, field) at new nuclear positions (Bohr)."""
+        from .field import keep_field
+        return keep_field(self, spd_gaussian_mol(coords, self.charges, self.shells, need_grad, self.nelec,
+                                                 self.renormalize))
 
     def dipole_integrals(self, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
         """AO dipole integrals ``<mu| r - origin |nu>`` (3,N,N)."""
         return dipole_integrals(self.coords, self.shells, origin, self.renormalize)
+
+    def dipole_grad_integrals(self, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """``<d_x mu| r_c - origin_c |nu>`` (3,3,N,N), the convention of ``GaussianMol.dipole_grad_integrals``."""
+        return dipole_grad_integrals(self.coords, self.shells, origin, self.renormalize)
 
 
 def dipole_integrals(coords, shells, origin=(0.0, 0.0, 0.0), renormalize: bool = True) -> np.ndarray:
@@ -212,6 +218,13 @@ def dipole_integrals(coords, shells, origin=(0.0, 0.0, 0.0), renormalize: bool =
         x1 = pr.pick(E, d, 1, 0)[0] * root + (pr.ctr[:, None, d] - float(origin[d])) * s1[d]
         dip[d] = pr.contract2(x1 * s1[(d + 1) % 3] * s1[(d + 2) % 3])
     return 0.5 * (dip + dip.transpose(0, 2, 1))
+
+
+def dipole_grad_integrals(coords, shells, origin=(0.0, 0.0, 0.0), renormalize: bool = True) -> np.ndarray:
+    """``ipdip[x,c,mu,nu] = <d_x mu| r_c - origin_c |nu>`` (3,3,N,N): the electron-coordinate gradient on the bra, first
+    index up to l + 2 = 4 (``gto_small.dipole_grad_from_primitives`` on this module's primitive functions)."""
+    pr = _Primitives(coords, shells, renormalize)
+    return gto_small.dipole_grad_from_primitives(pr, pr.pair_E(4, 2), origin)
 
 
 def spd_gaussian_mol(coords, charges, shells, need_grad: bool = True, nelec: Optional[Tuple[int, int]] = None,

@@ -30,10 +30,14 @@ class DeviceMadeMol(SpdGaussianMol):
     producer: Optional["DeviceSpdGaussians"] = None
 
     def with_coords(self, coords, need_grad: bool = True) -> "DeviceMadeMol":
-        return self.producer.to_mol(coords, need_grad)
+        from .field import keep_field
+        return keep_field(self, self.producer.to_mol(coords, need_grad))
 
     def dipole_integrals(self, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
         return self.producer.dipole_integrals(self.coords, origin)[0].cpu().numpy()
+
+    def dipole_grad_integrals(self, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
+        return self.producer.dipole_grad_integrals(self.coords, origin)[0].cpu().numpy()
 
 
 class DeviceSpdGaussians(DeviceGaussians):

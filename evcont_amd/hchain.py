@@ -67,6 +67,8 @@ class HChainMol(AOArrays):
     charges: Optional[np.ndarray] = None
     exponents: Tuple[float, ...] = STO3G_H_EXPONENTS
     coefficients: Tuple[float, ...] = STO3G_H_COEFFICIENTS
+    field: Optional[np.ndarray] = None    # (3,) the uniform electric field the arrays carry (``with_field``)
+    field_origin: Tuple[float, float, float] = (0.0, 0.0, 0.0)
 
     def energy_nuc(self) -> float:
         return float(self.enuc)
@@ -101,9 +103,44 @@ class HChainMol(AOArrays):
         dip = np.einsum("pi,xpq,qj->xij", Cm, Dp, Cm, optimize=True)
         return 0.5 * (dip + dip.transpose(0, 2, 1))
 
+    def dipole_grad_integrals(self, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """``ipdip[x,c,mu,nu] = <d_x mu| r_c - origin_c |nu>`` (3,3,N,N): the electron-coordinate gradient on the bra
+        (the convention of ``ipovlp``), so ``d dip_c[mu,nu] / dR_Ax = -ipdip[x,c,mu,nu] [mu in A] - ipdip[x,c,nu,mu]
+        [nu in A]``.  Closed form per primitive pair: ``d/dA_x (P_c - O_c) S = delta_xc (a/p) S - 2 mu (A - B)_x
+        (P_c - O_c) S``, with the pair centre of ``dipole_integrals``."""
+        R = np.asarray(self.coords, dtype=np.float64).reshape(-1, 3)
+        A = R.shape[0]
+        ex = np.asarray(self.exponents, dtype=np.float64)
+        K = len(ex)
+        a = np.tile(ex, A)
+        owner = np.repeat(np.arange(A), K)
+        Rp = R[owner]
+        cn = np.tile(np.asarray(self.coefficients, dtype=np.float64), A) * (2.0 * a / np.pi) ** 0.75
+        Cm = np.zeros((A * K, A))
+        Cm[np.arange(A * K), owner] = cn
+        pp = a[:, None] + a[None, :]
+        mu = a[:, None] * a[None, :] / pp
+        AB = Rp[:, None, :] - Rp[None, :, :]
+        Sp = (np.pi / pp) ** 1.5 * np.exp(-mu * np.sum(AB * AB, axis=-1))
+        P = np.where(AB == 0.0, Rp[:, None, :],
+                     (a[:, None, None] * Rp[:, None, :] + a[None, :, None] * Rp[None, :, :]) / pp[:, :, None])
+        PO = np.moveaxis(P - np.asarray(origin, dtype=np.float64), -1, 0)          # (c,Np,Np)
+        ABx = np.moveaxis(AB, -1, 0)                                               # (x,Np,Np)
+        dA = -2.0 * mu[None, None] * ABx[:, None] * PO[None, :] * Sp[None, None]   # (x,c,Np,Np) d/dA_x
+        for x in range(3):
+            dA[x, x] += (a[:, None] / pp) * Sp
+        return -np.einsum("pi,xcpq,qj->xcij", Cm, dA, Cm, optimize=True)
+
+    def with_field(self, F, origin=(0.0, 0.0, 0.0)) -> "HChainMol":
+        """A copy in the uniform electric field ``F`` (3,) (``evcont_amd.field.with_field``)."""
+        from .field import with_field
+        return with_field(self, F, origin)
+
     def with_coords(self, coords, need_grad: bool = True) -> "HChainMol":
-        """The same molecule (basis, charges, electrons) at new nuclear positions (Bohr)."""
-        return s_gaussian_mol(coords, self.charges, self.exponents, self.coefficients, need_grad, self.nelec)
+        """The same molecule (basis, charges, electrons, field) at new nuclear positions (Bohr)."""
+        from .field import keep_field
+        return keep_field(self, s_gaussian_mol(coords, self.charges, self.exponents, self.coefficients, need_grad,
+                                               self.nelec))
 
 
 def s_gaussian_mol(coords, charges: Optional[Sequence[float]] = None,

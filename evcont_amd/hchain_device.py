@@ -19,12 +19,13 @@ import torch
 
 from . import _lib
 from .evaluator import DeviceAOBatch, F64, _dev
+from .field_device import FieldProducer
 from .hchain import STO3G_H_COEFFICIENTS, STO3G_H_EXPONENTS
 
 _FIELDS = ("enuc", "S", "hcore", "eri", "ipovlp", "dhcore", "eri_ip1", "gnuc")
 
 
-class DeviceSGaussians:
+class DeviceSGaussians(FieldProducer):
     """One contracted s function (``exponents``, ``coefficients`` of normalised primitives) on every centre of a molecule
     with nuclear ``charges`` (default: 1 on each of the centres of the first ``integrals`` call)."""
 
@@ -44,6 +45,8 @@ class DeviceSGaussians:
         self._buffers = {}         # (G, need_grad, packed) -> dict of output tensors
         self._coords = {}          # G -> device (G,A,3) staging of host coordinates
         self._dip = {}             # G -> device (G,3,N,N) dipole integrals
+        self._ipdip = {}           # G -> device (G,3,3,N,N) their gradient (field_device.FieldProducer)
+        self._field = {}           # G -> device (G,3) staging of host fields
         self._ws = None
 
     @classmethod
@@ -121,11 +124,25 @@ class DeviceSGaussians:
             "evc_sgto_dipole_batch")
         return dip
 
-    def integrals(self, coords, need_grad: bool = True, packed: bool = False, out: Optional[dict] = None) -> DeviceAOBatch:
+    def _nao_now(self) -> int:
+        return self.natm
+
+    def _ipdip_call(self, R, G, origin, ipdip) -> None:
+        _lib.check(self.lib.evc_sgto_dipole_grad_batch(
+            int(R.shape[1]), int(self.exponents.shape[0]), G, R.data_ptr(), self.exponents.ctypes.data,
+            self.coefficients.ctypes.data, origin, ipdip.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
+            "evc_sgto_dipole_grad_batch")
+
+    def integrals(self, coords, need_grad: bool = True, packed: bool = False, out: Optional[dict] = None, field=None,
+                  origin=(0.0, 0.0, 0.0)) -> DeviceAOBatch:
         """The integrals at ``coords`` ((G,A,3) or (A,3), Bohr; numpy or a device tensor), enqueued on the current
         stream of the device.  ``packed``: ``eri`` as the dense (Ms,Ms) s4 matrix and ``eri_ip1`` packed in its last two
         indices (s2kl), what evaluators on the compressed layout read (at most 64 centres).  ``out``: a dict of tensors
-        as ``allocate`` returns to write into, instead of the buffers this object keeps for the shape."""
+        as ``allocate`` returns to write into, instead of the buffers this object keeps for the shape.
+        ``field``: None, or a uniform electric field ((3,) or one per geometry (G,3), atomic units; numpy or a device
+        tensor) with the dipole operator's ``origin``: behind the integrals the call then enqueues the dipole integrals,
+        their gradient (with ``need_grad``) and the fold of the field into ``hcore``, ``dhcore``, ``enuc`` and ``gnuc``
+        (``evc_field_fold_batch``).  Without a field nothing more than the integrals is enqueued."""
         if torch.is_tensor(coords):
             R = coords.to(device=self.device, dtype=F64).reshape((-1,) + tuple(coords.shape[-2:])).contiguous()
             G, A = int(R.shape[0]), int(R.shape[1])
@@ -160,6 +177,8 @@ class DeviceSGaussians:
             A, nprim, G, R.data_ptr(), self._charges.data_ptr(), self.exponents.ctypes.data,
             self.coefficients.ctypes.data, C.byref(cs), flags, self._ws.data_ptr(), int(self._ws.numel()),
             torch.cuda.current_stream(self.device).cuda_stream), "evc_sgto_integrals_batch")
+        if field is not None:
+            self._fold_field(R, out, need_grad, field, origin)
         return DeviceAOBatch(S=out["S"], hcore=out["hcore"], eri=out["eri"], enuc=out["enuc"], natm=A,
                              ipovlp=out.get("ipovlp"), dhcore=out.get("dhcore"), eri_ip1=out.get("eri_ip1"),
                              gnuc=out.get("gnuc"), aoslices=self._aoslices, ip1_s2kl=packed and need_grad,

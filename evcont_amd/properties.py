@@ -101,3 +101,17 @@ def properties_host(one_RDM, X, C, pairs, S, dip_ao, aoslices, charges, coords, 
         out["mulliken"].append(mulliken_pop(P, S, aoslices))
         out["loewdin"].append(loewdin_pop(D, aoslices))
     return {k: np.array(v) for k, v in out.items()}
+
+
+def ir_intensities(apt, modes, masses) -> np.ndarray:
+    """Infrared intensities ``|d mu / dQ_k|^2 = |sum_Ax P[A,x,:] L[Ax,k] / sqrt(m_A)|^2`` per normal mode, in atomic
+    units (e^2 / m_e when ``masses`` are in electron masses).  ``apt`` (A,3,3) = ``P[A,x,c] = d mu_c / dR_Ax`` (the
+    atomic polar tensor of ONE state, ``get_multistate_field_response``), ``modes`` (3A,K) the columns ``L[:,k]`` of the
+    eigenvectors of the mass-weighted Hessian (rows ordered atom-major, x y z), ``masses`` (A,).  No unit conversion is
+    applied (none is tabulated here); relative stick heights need none."""
+    P = np.asarray(apt, dtype=np.float64)
+    A = P.shape[0]
+    L = np.asarray(modes, dtype=np.float64).reshape(3 * A, -1)
+    m = np.repeat(np.asarray(masses, dtype=np.float64).reshape(A), 3)
+    dmu = np.einsum("rc,rk->ck", P.reshape(3 * A, 3), L / np.sqrt(m)[:, None])
+    return np.sum(dmu * dmu, axis=0)

@@ -53,7 +53,8 @@ extern "C" {
                                  evc_spgto_dipole_batch; additive: evc_spdgto_workspace_bytes,
                                  evc_spdgto_integrals_batch, evc_spdgto_dipole_batch; additive:
                                  evc_fci_rotate_block, evc_fci_rotate_block_workspace_bytes; additive:
-                                 evc_fci_trdm_rows_block, evc_fci_rows_block_workspace_bytes */
+                                 evc_fci_trdm_rows_block, evc_fci_rows_block_workspace_bytes; additive:
+                                 evc_sgto_dipole_grad_batch, evc_gto_dipole_grad_batch, evc_field_fold_batch */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -780,6 +781,48 @@ size_t evc_properties_workspace_bytes(int n, int ntrain, int natm, int count, in
 int evc_properties_roots_batch(const evc_trdm_set *t, const evc_property_inputs *in, const double *coeffs, int nvec,
                                const int32_t *pairs, int npairs, const evc_property_outputs *out, const void *ws,
                                size_t ws_bytes, void *scratch, size_t scratch_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * A uniform electric field on the device (csrc/field.hip; host statement: evcont_amd/field.py).  H(F) = H0 - mu . F changes
+ * four arrays of an evc_geometry_batch and nothing else of the chain:
+ *   hcore += sum_c F_c dip_c      dhcore[A,x] += sum_c F_c d dip_c / dR_Ax
+ *   enuc  -= sum_A Z_A F . (R_A - origin)         gnuc[A] -= Z_A F
+ * with dip (count,3,N,N) = <mu| r - origin |nu> of the dipole calls above and its nuclear derivative from
+ *   ipdip (count,3,3,N,N),  ipdip[x,c,mu,nu] = <d_x mu| r_c - origin_c |nu>
+ * (the electron-coordinate gradient on the bra, the convention of ipovlp):
+ *   d dip_c[mu,nu] / dR_Ax = - ipdip[x,c,mu,nu] [mu in A] - ipdip[x,c,nu,mu] [nu in A].
+ * evc_sgto_dipole_grad_batch: ipdip of the s-Gaussian molecules of evc_sgto_integrals_batch, with the argument list, the
+ *   limits and the refusals of evc_sgto_dipole_batch (natm <= 96, nprim <= 8, positive exponents, 8-byte aligned device
+ *   pointers).  Closed form per primitive pair, delta_xc (a/p) S - 2 mu (A - B)_x (P_c - origin_c) S, with P as in
+ *   s_gaussian_mol (on coincident coordinates the centre exactly).
+ * evc_gto_dipole_grad_batch: ipdip of molecules of contracted shells with l <= 2 (the AO order and the d functions of
+ *   evc_spdgto_integrals_batch), with the argument list, the limits and the refusals of evc_spdgto_dipole_batch; it
+ *   serves the molecules of evc_spgto_* as well.  The bra derivative 2a (i + 1) - i (i - 1) in the powers of dimension x
+ *   of the dipole factor, whose operator adds one more power in dimension c.
+ * Both: coords DEVICE (count,natm,3); the basis and origin HOST; one thread per ORDERED pair (mu, nu), one sum over the
+ *   primitive pairs (and monomials) in one fixed ascending order; ipdip[x,c] + ipdip[x,c]^T = - delta_xc S to rounding.
+ * evc_field_fold_batch: adds the four terms IN PLACE to arrays an integrals call has written.
+ *   n, natm, count   N <= 96, 1 <= natm <= 65535, 1 <= count <= 65535.
+ *   dip, ipdip, aoslices (A,2) int64, charges (A), coords (count,A,3), field (count,3): DEVICE; one field per geometry.
+ *   origin           HOST; the origin dip and ipdip were computed for.
+ *   flags            0, or EVC_FLAG_ENERGY_ONLY: hcore and enuc alone; ipdip, aoslices, dhcore and gnuc may then be NULL
+ *                    and are not touched.  Any other flag is refused.
+ *   hcore (count,N,N), dhcore (count,A,3,N,N), enuc (count), gnuc (count,A,3): DEVICE, read and written.
+ *   One thread owns an element pair mu >= nu, reads the element (mu, nu) and writes it and its mirror: hcore stays
+ *   exactly symmetric, dhcore in its last two indices.  A zero field leaves every array as it was.
+ * All three: a null required pointer, a shape outside the limits, an l outside {0, 1, 2}, a non-positive exponent, a
+ * misaligned pointer or an unknown flag is refused before anything is launched (rc < 0, evc_last_error starts with the
+ * function's name).  Caller's stream, no allocation, no library state, no workspace, no profile stage.  No sum is split
+ * between threads and nothing is accumulated between threads: the same bits from run to run and for every batch size.
+ * --------------------------------------------------------------------------------- */
+int evc_sgto_dipole_grad_batch(int natm, int nprim, int count, const double *coords, const double *ex, const double *co,
+                               const double origin[3], double *ipdip, void *stream);
+int evc_gto_dipole_grad_batch(int natm, int nshell, int count, const double *coords, const int *shell_atom,
+                              const int *shell_l, const int *shell_prim_offset, const double *exponents,
+                              const double *coefficients, const double origin[3], double *ipdip, void *stream);
+int evc_field_fold_batch(int n, int natm, int count, const double *dip, const double *ipdip, const int64_t *aoslices,
+                         const double *charges, const double *coords, const double *field, const double origin[3],
+                         int flags, double *hcore, double *dhcore, double *enuc, double *gnuc, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Measurement hook (bench.py): while enabled, the fused pipeline records hipEvents on the launch
