@@ -8,7 +8,7 @@ molecule of contracted s, p and real spherical d Gaussian shells, computed on th
 
 The interface, the buffers kept per shape and the staging of host coordinates are those of
 ``gto_device.DeviceGaussians`` (which stays the route for molecules of s and p shells alone); this class names its own C
-calls and the normalisation of ``gto_spd``.  ``to_mol`` downloads one geometry into the host molecule class of
+calls.  ``to_mol`` downloads one geometry into the host molecule class of
 ``gto_spd`` without running the numpy statement, which takes minutes at N = 24.
 """
 from __future__ import annotations
@@ -19,7 +19,7 @@ from typing import Optional
 import numpy as np
 
 from .gto_device import DeviceGaussians
-from .gto_spd import SpdGaussianMol, contraction_coefficients
+from .gto_spd import SpdGaussianMol
 
 _HOST_FIELDS = ("S", "hcore", "eri", "ipovlp", "dhcore", "eri_ip1", "gnuc")
 
@@ -46,7 +46,6 @@ class DeviceSpdGaussians(DeviceGaussians):
 
     _WORKSPACE, _INTEGRALS, _DIPOLE = ("evc_spdgto_workspace_bytes", "evc_spdgto_integrals_batch",
                                        "evc_spdgto_dipole_batch")
-    _coefficients = staticmethod(contraction_coefficients)
 
     def __init__(self, charges, shells, nelec=None, renormalize: bool = True, device=None):
         for atom in shells:

@@ -90,7 +90,7 @@ def boys_grid_errors(nmax=9):
     """(nmax + 1,) worst relative error of ``gto_small.boys`` over ``boys_grid`` per order, against mpmath at 50
     digits."""
     from mpmath import mp, mpf
-    from evcont_amd.gto_small import boys
+    from evcont_amd.gto_host import boys
     t = boys_grid()
     got = boys(nmax, t)
     worst = np.zeros(nmax + 1)

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from evcont_amd import _lib
-from evcont_amd.gto_small import contraction_coefficients, flatten_shells
+from evcont_amd.gto_host import contraction_coefficients, flatten_shells
 from sgto_harness import DEV, FENCE, GUARD, Fenced                      # noqa: F401 (FENCE, GUARD: for the tests)
 
 S4, S2KL, ENERGY = _lib.FLAG_ERI_S4, _lib.FLAG_IP1_S2KL, _lib.FLAG_ENERGY_ONLY
@@ -18,15 +18,15 @@ GRAD_FIELDS = ("ipovlp", "dhcore", "eri_ip1", "gnuc")
 
 class Basis:
     """The flattened basis of a molecule as the C calls take it: ``charges`` (A,), ``shells`` per atom a list of
-    ``gto_small.Shell`` (an empty list: a nucleus without functions).  The coefficients go through
-    ``gto_small.contraction_coefficients``, so the device and ``sp_gaussian_mol`` see the same numbers."""
-    route, contraction = "spgto", staticmethod(contraction_coefficients)     # a subclass names another route
+    ``Shell`` (an empty list: a nucleus without functions).  The coefficients go through
+    ``gto_host.contraction_coefficients``, so the device and the host statement see the same numbers."""
+    route = "spgto"                                                          # a subclass names another route
 
     def __init__(self, charges, shells, renormalize=True):
         self.charges = np.ascontiguousarray(charges, dtype=np.float64).reshape(-1)
         assert len(shells) == self.charges.shape[0]
         (self.shell_atom, self.shell_l, self.shell_prim_offset, self.exponents, self.coefficients, self.aoslices,
-         self.nao) = flatten_shells(shells, self.contraction(shells, renormalize))
+         self.nao) = flatten_shells(shells, contraction_coefficients(shells, renormalize))
         self.natm, self.nshell, self.nprim = len(shells), len(self.shell_l), int(self.shell_prim_offset[-1])
         self.shells = shells
 

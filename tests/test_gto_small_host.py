@@ -162,6 +162,16 @@ def test_tables_are_normalised(table):
         gs.Shell(2, (1.0,), (1.0,))
 
 
+def test_the_sp_entry_refuses_a_d_shell():
+    """``sp_gaussian_mol`` runs the Hermite orders of lmax = 1: a d shell (built with ``gto_spd.Shell``, since
+    ``gto_small.Shell`` refuses l = 2 itself) is an error, not five truncated functions."""
+    from evcont_amd import gto_spd
+    shells = [[gs.Shell(0, (1.1,), (1.0,))], [gs.Shell(1, (0.9,), (1.0,)), gto_spd.Shell(2, (0.8,), (1.0,))]]
+    with pytest.raises(ValueError, match="sp_gaussian_mol: shell with l=2"):
+        gs.sp_gaussian_mol([[0.0, 0.0, 0.0], [0.0, 0.0, 1.4]], [1.0, 1.0], shells, need_grad=False)
+    assert gto_spd.spd_gaussian_mol([[0.0, 0.0, 0.0], [0.0, 0.0, 1.4]], [1.0, 1.0], shells, need_grad=False).nao == 9
+
+
 def test_water_rhf_known_answer():
     """RHF of STO-3G water at the geometry of a public SCF tutorial: recorded and printed, not a gate on the energy (the
     expected value, about -74.942079928 Ha with enuc about 8.002367061810, is quoted from memory)."""

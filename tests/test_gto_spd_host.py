@@ -7,6 +7,7 @@ import pytest
 
 import spdgto_cases as dc
 import spgto_cases as sc
+from evcont_amd import gto_host
 from evcont_amd import gto_small as gs
 from evcont_amd import gto_spd as gd
 
@@ -144,7 +145,7 @@ def test_cartesian_d_against_the_p_derivative_of_the_sp_statement(monkeypatch):
     Z = np.array([2.0, 1.0])
     ref = gs.sp_gaussian_mol(R, Z, [[gs.Shell(1, [a], [1.0])], [gs.Shell(0, [0.6], [1.0]), gs.Shell(1, [1.3], [1.0])]],
                              renormalize=False)
-    monkeypatch.setattr(gd, "D_MONOMIALS", ((((2, 0, 0), 1.0),),) * 5)
+    monkeypatch.setattr(gto_host, "D_MONOMIALS", ((((2, 0, 0), 1.0),),) * 5)     # where ``monomials`` reads it
     new = gd.spd_gaussian_mol(R, Z, [[gd.Shell(2, [a], [1.0]), gd.Shell(0, [a], [1.0])],
                                      [gd.Shell(0, [0.6], [1.0]), gd.Shell(1, [1.3], [1.0])]], need_grad=False,
                               renormalize=False)
