@@ -327,10 +327,13 @@ def converge_EVCont_MD(EVCont_obj, init_mol, steps=100, dt=1, convergence_thresh
 
 def _device_producer(mol0):
     """The device integral producer class of an array-level molecule: molecules of s and p shells
-    (gto_small.GaussianMol), of s, p and d shells (gto_spd.SpdGaussianMol) and of one s function per centre
-    (hchain.HChainMol)."""
+    (gto_small.GaussianMol), of s, p and d shells (gto_spd.SpdGaussianMol), of shells up to f
+    (gto_spdf.SpdfGaussianMol) and of one s function per centre (hchain.HChainMol)."""
     if getattr(mol0, "shells", None) is not None and hasattr(mol0, "charges"):
-        if any(sh.l == 2 for atom in mol0.shells for sh in atom):
+        if any(sh.l == 3 for atom in mol0.shells for sh in atom):
+            # f shells (gto_spdf.SpdfGaussianMol): csrc/spdfgto.hip
+            from .gto_spdf_device import DeviceSpdfGaussians as producer
+        elif any(sh.l == 2 for atom in mol0.shells for sh in atom):
             # d shells (gto_spd.SpdGaussianMol): the general route, csrc/spdgto.hip
             from .gto_spd_device import DeviceSpdGaussians as producer
         else:
@@ -348,7 +351,7 @@ def _device_surfaces(mols, one_rdm, two_rdm, overlap, nroots, observables=(), de
     ``mols``, device-resident from the coordinates on: the training set and the batched evaluator are built once, every
     call uploads the coordinates, computes the AO integrals there (``hchain_device.DeviceSGaussians``, or
     ``gto_device.DeviceGaussians`` for a molecule with ``shells``, ``gto_spd_device.DeviceSpdGaussians`` when the
-    shells contain l = 2) and runs the
+    shells contain l = 2, ``gto_spdf_device.DeviceSpdfGaussians`` when they contain l = 3) and runs the
     batched several-roots call on them.  With ``observables``: ``(E, grads (G,1,A,3), props)`` of the highest root alone,
     forces and observables from one solve (``BatchedEvaluator.multistate_properties``).  ``evaluate(R, field)``: the
     geometries in the uniform electric fields ``field`` ((3,) or (G,3)) with the origin ``field_origin``, folded into the

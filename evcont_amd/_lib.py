@@ -192,6 +192,14 @@ SIGNATURES = {
                                              C.c_void_p, C.c_size_t, C.c_void_p]),
     "evc_spdgto_dipole_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "evc_spdfgto_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "evc_spdfgto_integrals_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SgtoOutputs), C.c_int,
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "evc_spdfgto_dipole_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "evc_spdfgto_dipole_grad_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "evc_properties_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "evc_properties_roots_batch": (C.c_int, [C.POINTER(TrdmSet), C.POINTER(PropertyInputs), C.c_void_p, C.c_int,
                                              C.c_void_p, C.c_int, C.POINTER(PropertyOutputs), C.c_void_p, C.c_size_t,

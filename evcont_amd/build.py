@@ -18,7 +18,7 @@ if os.environ.get("EVC_DEBUG_STAMPS") and not TAG:
 LIB = os.path.join(HERE, f"libevcont_hip_{TAG}.so" if TAG else "libevcont_hip.so")
 OBJDIR = os.path.join(CSRC, f"_build_{TAG}") if TAG else CSRC
 SOURCES = ["gemv_dispatch.hip", "gemv_stream.hip", "gemv_mfma.hip", "gemv_lds.hip", "gemv_cols_lds.hip", "quarter.hip", "pair_transform.hip", "pair_pipe.hip", "pack.hip", "y2.hip", "ip1.hip", "pair_dma.hip", "pair64.hip", "loewdin.hip", "loewdin_big.hip", "subspace_small.hip",
-           "grad_tail.hip", "subspace_big.hip", "response.hip", "fci.hip", "fci_solve.hip", "fci_spin.hip", "fci_rotate.hip", "fci_pack.hip", "cas_expand.hip", "sgto.hip", "spgto.hip", "spdgto.hip", "properties.hip", "field.hip",
+           "grad_tail.hip", "subspace_big.hip", "response.hip", "fci.hip", "fci_solve.hip", "fci_spin.hip", "fci_rotate.hip", "fci_pack.hip", "cas_expand.hip", "sgto.hip", "spgto.hip", "spdgto.hip", "spdfgto.hip", "properties.hip", "field.hip",
            "profile.hip", "workspace.hip", "side_stream.hip", "pipeline.hip", "roots.hip", "standalone.hip"]
 HEADERS = ["common.hpp", "kernels.hpp", "route.hpp", "pair_plan.hpp", "pair_rows.hpp", "pair_dma.hpp", "pt_stamps.hpp", "lds_dma.hpp", "big_block.hpp", "big_few_roots.hpp", "pipeline.hpp", "few_roots.hpp", "small_mm.hpp", "eigh_small.hpp", "tridiag_f32.hpp", "loewdin.hpp", "gto_shells.hpp", "unpack_tiles.hpp",
            os.path.join("..", "..", "include", "evcont_hip.h")]

@@ -237,8 +237,9 @@ static int gto_describe(const char *who, int natm, int nshell, int count, const 
         for (int k = shell_prim_offset[s]; k < shell_prim_offset[s + 1]; ++k) {
             const double a = exponents[k];
             EVC_REQUIRE(a > 0.0 && isfinite(a), "%s: exponent %d is %g, must be positive", who, k, a);
-            // the norm of exp(-a r^2), x exp(-a r^2), x y exp(-a r^2)
-            const double norm = pow(2.0 * a / kGtoPi, 0.75) * (l == 0 ? 1.0 : (l == 1 ? 2.0 * sqrt(a) : 4.0 * a));
+            // the norm of exp(-a r^2), x exp(-a r^2), x y exp(-a r^2), x y z exp(-a r^2)
+            const double norm = pow(2.0 * a / kGtoPi, 0.75) *
+                                (l == 3 ? 8.0 * a * sqrt(a) : (l == 0 ? 1.0 : (l == 1 ? 2.0 * sqrt(a) : 4.0 * a)));
             bs.ex[k] = a;
             bs.cn[k] = coefficients[k] * norm;
             bs.atom[k] = (uint8_t)shell_atom[s];

@@ -1,8 +1,9 @@
 """The host statement of the AO integrals (and their first nuclear derivatives) of molecules built from contracted
-Gaussian shells with l <= 2, with nothing third-party: s and p as Cartesian functions, d as the five REAL SPHERICAL
-functions.  ``evcont_amd.gto_small`` (s and p: water, the H2O-H3O+ dimer and Zundel in STO-3G or 6-31G) and
-``evcont_amd.gto_spd`` (s, p and d: water in cc-pVDZ) are its two entry points; each calls ``gaussian_arrays`` with a
-fixed ``lmax`` of its own (1 and 2), which sets the Hermite orders and with them the rounding and the run time.  The
+Gaussian shells, with nothing third-party: s and p as Cartesian functions, d and f as the five and seven REAL SPHERICAL
+functions.  ``evcont_amd.gto_small`` (s and p: water, the H2O-H3O+ dimer and Zundel in STO-3G or 6-31G),
+``evcont_amd.gto_spd`` (s, p and d: water in cc-pVDZ) and ``evcont_amd.gto_spdf`` (up to f) are its entry points; each
+calls ``gaussian_arrays`` with a fixed ``lmax`` of its own (1, 2 and 3), which sets the Hermite orders and with them the
+rounding and the run time.  The
 arrays, their meanings and their signs are those of ``evcont_amd.hchain`` (which remains the statement, and the fast
 route, for one s function per centre):
 
@@ -31,7 +32,6 @@ This is numpy, clarity over speed (water / cc-pVDZ takes minutes); ``evcont_amd.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from functools import lru_cache
 from typing import Optional, Tuple
 
 import numpy as np
@@ -50,13 +50,14 @@ class Shell:
     l: int
     exponents: Tuple[float, ...]
     coefficients: Tuple[float, ...]
+    _LS = (0, 1, 2)                       # the accepted l (``gto_spdf.Shell`` accepts 3 as well)
 
     def __post_init__(self):
         object.__setattr__(self, "l", int(self.l))
         object.__setattr__(self, "exponents", tuple(float(x) for x in self.exponents))
         object.__setattr__(self, "coefficients", tuple(float(x) for x in self.coefficients))
-        if self.l not in (0, 1, 2):
-            raise ValueError(f"Shell: l={self.l}, supported 0, 1 and 2")
+        if self.l not in self._LS:
+            raise ValueError(f"Shell: l={self.l}, supported {', '.join(map(str, self._LS[:-1]))} and {self._LS[-1]}")
         if len(self.exponents) != len(self.coefficients) or not self.exponents:
             raise ValueError("Shell: exponents and coefficients must have one length >= 1")
         if min(self.exponents) <= 0.0:
@@ -73,6 +74,18 @@ D_MONOMIALS = (
     (((1, 0, 1), 1.0),),                                              # xz
     (((2, 0, 0), 0.5), ((0, 2, 0), -0.5)),                            # x^2 - y^2
 )
+# Per component of an f shell (m = -3 ... 3, PySCF's order), for primitives normalised as x y z exp(-a r^2)
+# (``primitive_norm(3, a)``); used by the entry point ``evcont_amd.gto_spdf`` alone.
+_R24, _R40, _R60 = 1.0 / np.sqrt(24.0), 1.0 / np.sqrt(40.0), 1.0 / np.sqrt(60.0)
+F_MONOMIALS = (
+    (((2, 1, 0), 3.0 * _R24), ((0, 3, 0), -_R24)),                              # y (3 x^2 - y^2)
+    (((1, 1, 1), 1.0),),                                                        # x y z
+    (((0, 1, 2), 4.0 * _R40), ((2, 1, 0), -_R40), ((0, 3, 0), -_R40)),          # y (4 z^2 - x^2 - y^2)
+    (((0, 0, 3), 2.0 * _R60), ((2, 0, 1), -3.0 * _R60), ((0, 2, 1), -3.0 * _R60)),   # z (2 z^2 - 3 x^2 - 3 y^2)
+    (((1, 0, 2), 4.0 * _R40), ((3, 0, 0), -_R40), ((1, 2, 0), -_R40)),          # x (4 z^2 - x^2 - y^2)
+    (((2, 0, 1), 0.5), ((0, 2, 1), -0.5)),                                      # z (x^2 - y^2)
+    (((3, 0, 0), _R24), ((1, 2, 0), -3.0 * _R24)),                              # x (x^2 - 3 y^2)
+)
 
 
 def monomials(l: int, comp: int):
@@ -81,7 +94,7 @@ def monomials(l: int, comp: int):
         return (((0, 0, 0), 1.0),)
     if l == 1:
         return ((tuple(int(comp == d) for d in range(3)), 1.0),)
-    return D_MONOMIALS[comp]
+    return F_MONOMIALS[comp] if l == 3 else D_MONOMIALS[comp]
 
 
 def element_shells(table, symbol: str):
@@ -100,8 +113,11 @@ def element_shells(table, symbol: str):
 
 
 def primitive_norm(l: int, a):
-    """Norm of a Cartesian primitive: exp(-a r^2), x exp(-a r^2) or x y exp(-a r^2) for l = 0, 1, 2."""
+    """Norm of a Cartesian primitive: exp(-a r^2), x exp(-a r^2), x y exp(-a r^2) or x y z exp(-a r^2) for
+    l = 0, 1, 2, 3."""
     a = np.asarray(a, dtype=np.float64)
+    if l == 3:
+        return (2.0 * a / np.pi) ** 0.75 * (8.0 * a * np.sqrt(a))
     return (2.0 * a / np.pi) ** 0.75 * (1.0, 2.0 * np.sqrt(a), 4.0 * a)[l]
 
 
@@ -110,7 +126,7 @@ def shell_self_overlap(shell) -> float:
     a = np.asarray(shell.exponents)
     c = np.asarray(shell.coefficients) * primitive_norm(shell.l, a)
     p = a[:, None] + a[None, :]
-    s = (np.pi / p) ** 1.5 * (1.0, 0.5 / p, 0.25 / (p * p))[shell.l]
+    s = (np.pi / p) ** 1.5 * (1.0, 0.5 / p, 0.25 / (p * p), 0.125 / (p * p * p))[shell.l]
     return float(c @ s @ c)
 
 
@@ -189,23 +205,32 @@ def hermite_E(imax: int, jmax: int, a, b, AB):
 
 
 def hermite_R(L: int, alpha, X, Y, Z):
-    """Hermite Coulomb integrals ``R_tuv`` = d^t_X d^u_Y d^v_Z F0(alpha R^2) for t + u + v <= L, as a dict."""
+    """Hermite Coulomb integrals ``R_tuv`` = d^t_X d^u_Y d^v_Z F0(alpha R^2) for t + u + v <= L, as a dict.  The
+    auxiliary ``R_tuv^n`` of total order k = t + u + v (n <= L - k) come from those of the orders k - 1 and k - 2 alone,
+    so they are made order by order and an order is dropped once the next two are done, instead of keeping all 2 380
+    auxiliaries of L = 13 to the end (the arithmetic of an entry is the same either way)."""
     F = boys(L, alpha * (X * X + Y * Y + Z * Z))
-
-    @lru_cache(maxsize=None)
-    def R(t, u, v, n):
-        if t == u == v == 0:
-            return (-2.0 * alpha) ** n * F[n]
-        if t > 0:
-            r = X * R(t - 1, u, v, n + 1)
-            return r + (t - 1) * R(t - 2, u, v, n + 1) if t > 1 else r
-        if u > 0:
-            r = Y * R(t, u - 1, v, n + 1)
-            return r + (u - 1) * R(t, u - 2, v, n + 1) if u > 1 else r
-        r = Z * R(t, u, v - 1, n + 1)
-        return r + (v - 1) * R(t, u, v - 2, n + 1) if v > 1 else r
-
-    return {(t, u, v): R(t, u, v, 0) for t in range(L + 1) for u in range(L + 1 - t) for v in range(L + 1 - t - u)}
+    below, last = {}, {(0, 0, 0, n): (-2.0 * alpha) ** n * F[n] for n in range(L + 1)}
+    out = {(0, 0, 0): last[(0, 0, 0, 0)]}
+    for k in range(1, L + 1):
+        level = {}
+        for t in range(k, -1, -1):
+            for u in range(k - t, -1, -1):
+                v = k - t - u
+                for n in range(L - k + 1):
+                    if t > 0:
+                        r = X * last[(t - 1, u, v, n + 1)]
+                        r = r + (t - 1) * below[(t - 2, u, v, n + 1)] if t > 1 else r
+                    elif u > 0:
+                        r = Y * last[(t, u - 1, v, n + 1)]
+                        r = r + (u - 1) * below[(t, u - 2, v, n + 1)] if u > 1 else r
+                    else:
+                        r = Z * last[(t, u, v - 1, n + 1)]
+                        r = r + (v - 1) * below[(t, u, v - 2, n + 1)] if v > 1 else r
+                    level[(t, u, v, n)] = r
+                out[(t, u, v)] = level[(t, u, v, 0)]
+        below, last = last, level
+    return out
 
 
 class _Primitives:

@@ -46,12 +46,16 @@ class DeviceSpdGaussians(DeviceGaussians):
 
     _WORKSPACE, _INTEGRALS, _DIPOLE = ("evc_spdgto_workspace_bytes", "evc_spdgto_integrals_batch",
                                        "evc_spdgto_dipole_batch")
+    # what ``gto_spdf_device.DeviceSpdfGaussians`` sets anew: the accepted l and the molecule class of ``to_mol``
+    _LS = (0, 1, 2)
+    _MOL = DeviceMadeMol
 
     def __init__(self, charges, shells, nelec=None, renormalize: bool = True, device=None):
         for atom in shells:
             for sh in atom:
-                if sh.l not in (0, 1, 2):
-                    raise ValueError(f"DeviceSpdGaussians: shell with l={sh.l}, supported 0, 1 and 2")
+                if sh.l not in self._LS:
+                    raise ValueError(f"{type(self).__name__}: shell with l={sh.l}, supported "
+                                     f"{', '.join(map(str, self._LS[:-1]))} and {self._LS[-1]}")
         super().__init__(charges, shells, nelec=nelec, renormalize=renormalize, device=device)
 
     def to_mol(self, coords, need_grad: bool = True) -> DeviceMadeMol:
@@ -69,7 +73,7 @@ class DeviceSpdGaussians(DeviceGaussians):
         if nelec is None:
             ne = int(round(float(self._charges_host.sum())))
             nelec = ((ne + 1) // 2, ne // 2)
-        return DeviceMadeMol(aoslices=self._aoslices.cpu().numpy(), enuc=float(out["enuc"][0].cpu()),
-                             integral_symmetry=True, coords=R[0].copy(), nelec=tuple(nelec),
-                             charges=self._charges_host.copy(), shells=self.shells, renormalize=self.renormalize,
-                             producer=self, **host)
+        return self._MOL(aoslices=self._aoslices.cpu().numpy(), enuc=float(out["enuc"][0].cpu()),
+                         integral_symmetry=True, coords=R[0].copy(), nelec=tuple(nelec),
+                         charges=self._charges_host.copy(), shells=self.shells, renormalize=self.renormalize,
+                         producer=self, **host)

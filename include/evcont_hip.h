@@ -54,7 +54,9 @@ extern "C" {
                                  evc_spdgto_integrals_batch, evc_spdgto_dipole_batch; additive:
                                  evc_fci_rotate_block, evc_fci_rotate_block_workspace_bytes; additive:
                                  evc_fci_trdm_rows_block, evc_fci_rows_block_workspace_bytes; additive:
-                                 evc_sgto_dipole_grad_batch, evc_gto_dipole_grad_batch, evc_field_fold_batch */
+                                 evc_sgto_dipole_grad_batch, evc_gto_dipole_grad_batch, evc_field_fold_batch;
+                                 additive: evc_spdfgto_workspace_bytes, evc_spdfgto_integrals_batch,
+                                 evc_spdfgto_dipole_batch, evc_spdfgto_dipole_grad_batch */
 
 /* t-RDM storage layouts = ndim of the reference's two_RDM argument
  * (ab_initio_eigenvector_continuation.py:41-68). */
@@ -730,6 +732,33 @@ int evc_spdgto_integrals_batch(int natm, int nshell, int count, const double *co
 int evc_spdgto_dipole_batch(int natm, int nshell, int count, const double *coords, const int *shell_atom,
                             const int *shell_l, const int *shell_prim_offset, const double *exponents,
                             const double *coefficients, const double origin[3], double *dip, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * AO integrals of molecules of contracted s, p, REAL SPHERICAL d and REAL SPHERICAL f Gaussian shells on the device
+ * (csrc/spdfgto.hip; the host statement is evcont_amd/gto_spdf.py spdf_gaussian_mol): the shape of water in cc-pVTZ from
+ * the coordinates.  The argument lists, the outputs (evc_sgto_outputs), the three flags, the forms, the refusals and the
+ * guarantees are those of the evc_spdgto_* calls above; shell_l may be 0, 1, 2 or 3 and nao counts 2l + 1 functions per
+ * shell (at most 7 nshell, at most 64).  AO order: an f shell as its seven real spherical functions in the order
+ * m = -3 ... 3: y(3x^2 - y^2)/sqrt(24), xyz, y(4z^2 - x^2 - y^2)/sqrt(40), z(2z^2 - 3x^2 - 3y^2)/sqrt(60),
+ * x(4z^2 - x^2 - y^2)/sqrt(40), z(x^2 - y^2)/2, x(x^2 - 3y^2)/sqrt(24), each times the norm of the normalised primitive
+ * x y z exp(-a r^2) and its coefficient.  The two-electron kernel runs a body specialised on the highest l of the bra
+ * pair and of the ket pair of an element; which body computes an element depends on the basis alone, so the same bits
+ * come out from run to run, for every batch size and in the packed and full forms.  Molecules with l <= 2 are served by
+ * both families and the two need not agree in the last bits.
+ * evc_spdfgto_dipole_grad_batch: ipdip[g,x,c,mu,nu] = <d_x mu| r_c - origin_c |nu> of these molecules, with the argument
+ * list, the alignment rule and the refusals of evc_gto_dipole_grad_batch (which stops at l = 2).
+ * --------------------------------------------------------------------------------- */
+size_t evc_spdfgto_workspace_bytes(int natm, int nshell, int nprim_total, int nao, int count);
+int evc_spdfgto_integrals_batch(int natm, int nshell, int count, const double *coords, const double *charges,
+                                const int *shell_atom, const int *shell_l, const int *shell_prim_offset,
+                                const double *exponents, const double *coefficients, const evc_sgto_outputs *out, int flags,
+                                void *ws, size_t ws_bytes, void *stream);
+int evc_spdfgto_dipole_batch(int natm, int nshell, int count, const double *coords, const int *shell_atom,
+                             const int *shell_l, const int *shell_prim_offset, const double *exponents,
+                             const double *coefficients, const double origin[3], double *dip, void *stream);
+int evc_spdfgto_dipole_grad_batch(int natm, int nshell, int count, const double *coords, const int *shell_atom,
+                                  const int *shell_l, const int *shell_prim_offset, const double *exponents,
+                                  const double *coefficients, const double origin[3], double *ipdip, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Observables of continuation states (csrc/properties.hip; host statement: evcont_amd/properties.py; the reference's
